@@ -11,11 +11,15 @@ Launch: `python bench.py --gpus N` starts its own N ranks (one per GPU, `torch.d
 is not already running under a launcher; under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it uses
 the launcher's ranks.  It refuses to run when the node has fewer GPUs than `--gpus`, or when WORLD_SIZE != --gpus.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what its headline figure needs: set up,
+warm up, time --steps steps, write the last step's outputs (--dump-outputs DIR), print the line.  With --full the line also
+carries (each of them takes runs of its own; the --no-* flags still drop single parts):
   roofline     — dominant kernel (implicit-GEMM conv / GEMM on the MFMA datapath): algorithmic FLOPs / event-timed duration
+  extra.hbm_kernels — event-timed HBM-bound kernels (DDIM step, PPO forward + backward, gradient norm, AdamW) against the HBM peak
   cpu_baseline — the CPU oracle (oracle/, torch-CPU) timed on a bounded sample of the same workload (rank 0, N=1)
   extra.train  — PPO train sample-timesteps/s of the same model (fused micro-steps, one AdamW update), rank-0 view
-  rccl_ranks, allreduce — N > 1: world size seen by RCCL and a timed all-reduce of the flat fp32 gradient buffer
+  extra.<datapath>, extra.f16x1 — the same workload on the other fp32-class datapath / without the f16mx cross terms (N=1)
+  allreduce    — N > 1: a timed all-reduce of the flat fp32 gradient buffer (rccl_ranks, the world size seen by RCCL, is always there)
 
 Modes: sample (headline) | train (PPO micro-steps) | epoch (one sample batch + its PPO micro-steps + optimizer updates with
 the gradient all-reduce: what a DDPO epoch costs per GPU) | comm (the collective alone; also runs on CPU/gloo for the tests).
@@ -72,6 +76,13 @@ def parse(argv=None):
                          "max-over-ranks timing, the gradient all-reduce and the mode's JSON line with value = null and \"dry_run\": true — "
                          "NO engine work runs and nothing is measured (tests/test_bench_launch_cpu.py)")
     ap.add_argument("--no-graph", action="store_true", help="launch the U-Net kernels eagerly instead of replaying a HIP graph")
+    ap.add_argument("--full", action="store_true",
+                    help="--mode sample: after the headline, also measure the roofline pass, the HBM-bound kernels, extra.train, the other "
+                         "fp32-class datapath (and extra.f16x1), the CPU baseline and (N > 1) the gradient all-reduce; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--mode sample: write what the timed path returned in its last step (images, final latents, latent trajectory, log-probs, "
+                         "timesteps) as DIR/<name>.npy, float32 (timesteps float64), at most 64 MB in all: an array over its share is replaced by "
+                         "a fixed, seeded sample of its flattened elements")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-train-extra", action="store_true", help="skip the short train-step measurement attached to the headline line")
@@ -116,7 +127,36 @@ def maybe_self_launch(args, argv):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + list(argv)
-    os.execvpe(cmd[0], cmd, env)
+    raise SystemExit(subprocess.call(cmd, env=env))      # a child process: this one may already have opened the GPU runtime
+
+
+DUMP_BUDGET_BYTES = 60_000_000                         # --dump-outputs: under the 64 MB cap
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Writes `arrays` (name -> tensor) as <outdir>/<name>.npy: floating point as float32, integers as float64.  Arrays are taken smallest
+    first, each against an equal share of what is left of `budget`; one larger than its share is replaced by a sample of its flattened
+    elements at sorted indices drawn from a fixed seed, so the same shapes give the same indices in every run and every build."""
+    os.makedirs(outdir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.float() if t.is_floating_point() else t.double()).numpy()
+    left, written = budget, {}
+    order = sorted(host, key=lambda k: host[k].nbytes)
+    for i, name in enumerate(order):
+        a = host[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+            a = np.ascontiguousarray(a.reshape(-1)[idx])
+            written[name] = f"{n} of {host[name].size} elements of {tuple(host[name].shape)}, seeded sample"
+        else:
+            written[name] = f"{tuple(a.shape)}"
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes
+    print(f"bench.py: outputs of the last timed step in {outdir}: " + "; ".join(f"{k} {v}" for k, v in written.items()), file=sys.stderr, flush=True)
 
 
 def cpu_baseline(args):
@@ -601,6 +641,8 @@ def dry_run(args, comm):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse(argv)
+    if args.dump_outputs and (args.mode != "sample" or args.dry_run):
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the sampling steps (--mode sample, not a dry run)")
     maybe_self_launch(args, argv)
     if args.mode != "comm" and not args.dry_run and not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the DDPO engine has no CPU path)")
@@ -630,22 +672,27 @@ def main(argv=None):
                                         height=args.resolution, width=args.resolution, guidance_scale=5.0, eta=1.0,
                                         jit=not args.no_graph)
         img = vae.decode(final)
-        return img, lps
+        return {"images": img, "final_latents": final, "latents": lat, "next_latents": nxt, "log_probs": lps, "timesteps": ts}
 
     for _ in range(args.warmup):
         one_step()
     comm.sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        img, lps = one_step()
+        out = one_step()
     comm.sync()
     dt = comm.max_over_ranks(time.perf_counter() - t0)
+    img, lps = out["images"], out["log_probs"]
     assert torch.isfinite(img).all() and torch.isfinite(lps).all()
     images = world * B * args.steps
     value = images / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    del out
+    full = args.full
 
     roofline = None
-    if not args.no_roofline:
+    if full and not args.no_roofline:
         # event-timed pass over the dominant kernel family (every ddpo_gemm_conv_fwd launch of one U-Net forward
         # on 2B latents); events are recorded on the stream the kernels are launched on.
         lat2 = torch.randn(2 * B, 4, args.resolution // 8, args.resolution // 8, device=dev)
@@ -690,15 +737,15 @@ def main(argv=None):
                                              if (v[2] and k in SUSTAINED_MFMA_ONLY_TFLOPS) else None} for k, v in by_fam.items()},
                     # context, NOT the roofline: what a pure stream of this datapath's MFMAs (no memory traffic, random operands) sustains on this chip
                     "sustained_mfma_only": {"tflops": SUSTAINED_MFMA_ONLY_TFLOPS, "source": SUSTAINED_MFMA_ONLY_NOTE}}
-    ar = time_allreduce(comm, unet.params.flat.numel()) if comm.dist is not None else None
+    ar = time_allreduce(comm, unet.params.flat.numel()) if (full and comm.dist is not None) else None
     extra = {}
-    if not args.no_train_extra and args.model in ("sd15", "sd21"):
+    if full and not args.no_train_extra and args.model in ("sd15", "sd21"):
         # the PPO half of an epoch (the wall-clock bottleneck of "reward vs wall-clock"), reported next to the headline number
         try:
             extra["train"] = measure_train(args, comm, L, unet, sched, state, emb, neg, steps=12, warmup=2)
         except Exception as exc:          # the headline line must survive a failure of the secondary measurement
             extra["train"] = {"error": f"{type(exc).__name__}: {exc}"}
-    if not args.no_roofline:
+    if full and not args.no_roofline:
         try:
             extra["hbm_kernels"] = measure_hbm_kernels(args, comm, L, ucfg, sched, state, unet)
         except Exception as exc:
@@ -707,7 +754,7 @@ def main(argv=None):
         comm.close()
         return
     alt = {"f16mx": "bf16x3", "bf16x3": "f16mx"}.get(args.datapath)
-    if world == 1 and alt and not args.no_alt_extra and not args.no_train_extra and args.model == "sd15":
+    if full and world == 1 and alt and not args.no_alt_extra and not args.no_train_extra and args.model == "sd15":
         # the OTHER fp32-class datapath on the same workload, in a fresh process: reported NEXT to the headline, never as it
         # (f16mx ships since round 4; bf16x3 is the selectable three-pass datapath)
         try:
@@ -721,7 +768,7 @@ def main(argv=None):
                           "note": f"the same workload with --datapath {alt} (U-Net forward error against float64: f16mx 4.2e-5, bf16x3 2.0e-5)"}
         except Exception as exc:
             extra[alt] = {"error": f"{type(exc).__name__}: {exc}"}
-    if world == 1 and args.datapath == "f16mx" and L.MX_CROSS and not args.no_alt_extra and not args.no_train_extra and args.model == "sd15":
+    if full and world == 1 and args.datapath == "f16mx" and L.MX_CROSS and not args.no_alt_extra and not args.no_train_extra and args.model == "sd15":
         # opt-in, NOT the headline and not what ships: the f16mx layers without their cross terms (one f16 pass per product: the reference's own
         # arithmetic class — its TPUs run one bf16 pass — at 11 significant bits).  What the cross terms' matrix work and bytes cost on this
         # power-bound chip; its parity margins (outside the 1e-3 contract on the gradients) are in profiles/r06_parity_f16x1.log.
@@ -741,7 +788,7 @@ def main(argv=None):
         except Exception as exc:
             extra["f16x1"] = {"error": f"{type(exc).__name__}: {exc}"}
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
     print(json.dumps(sample_line(args, comm, value, dt, roofline, ar, extra, cpu)), flush=True)
     comm.close()

@@ -1,6 +1,5 @@
 """RWR baseline plumbing: the local sample store, maskers and dataset weights (CPU), the VAE encoder and the two
 entrypoints pipeline/sample.py -> pipeline/finetune.py end to end on the tiny architecture (GPU)."""
-import ast
 import json
 import os
 
@@ -8,9 +7,6 @@ import numpy as np
 import pytest
 
 from ddpo_amd.utils import bucket
-
-REF = "/root/reference"
-
 
 def _rows(n, seed=0):
     r = np.random.RandomState(seed)
@@ -110,19 +106,20 @@ def test_maskers_and_dataset_weights(tmp_path):
         assert np.isclose(rd.weights[prompts == p].sum(), (prompts == p).sum())             # expected weight 1 per item inside every prompt group
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference tree is only present in the build container")
 def test_maskers_equal_the_reference_classes():
-    tree = ast.parse(open(os.path.join(REF, "ddpo/utils/logger.py")).read())
-    ns = {"np": np}
-    for node in tree.body:
-        if isinstance(node, (ast.ClassDef, ast.FunctionDef)) and node.name in ("Masker", "StreamingAverage", "StreamingPercentile", "Percentile", "Threshold", "make_masker"):
-            exec(compile(ast.Module(body=[node], type_ignores=[]), "logger.py", "exec"), ns)
-    r = np.random.RandomState(4)
-    for mode, param in (("percentile", 90), ("streaming_percentile", 95), ("streaming_percentile", 0), ("threshold", 0.1)):
-        a, b = ns["make_masker"](mode, param), bucket.make_masker(mode, param)
-        for _ in range(3):
-            xs = r.randn(16, 1)
-            assert np.array_equal(np.asarray(a(xs)).reshape(-1), np.asarray(b(xs)).reshape(-1)) and repr(a) == repr(b)
+    """The reference's own masker classes (ddpo/utils/logger.py, lifted with `ast`) ran on these inputs: their masks and reprs are stored in
+    tests/golden/reference_contracts.json (tests/golden/make_reference_contract_goldens.py)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_contracts.json")) as f:
+        ref = json.load(f)["maskers"]
+    assert [[c["mode"], c["param"]] for c in ref["cases"]] == [["percentile", 90], ["streaming_percentile", 95], ["streaming_percentile", 0],
+                                                             ["threshold", 0.1]]
+    r = np.random.RandomState(ref["seed"])
+    for case in ref["cases"]:
+        b = bucket.make_masker(case["mode"], case["param"])
+        assert len(case["masks"]) == ref["draws"] == 3
+        for mask, rep in zip(case["masks"], case["reprs"]):
+            xs = r.randn(ref["rows"], 1)
+            assert np.array_equal(np.asarray(b(xs)).reshape(-1), np.asarray(mask, dtype=bool)) and repr(b) == rep
 
 
 def test_parser_evaluates_fstring_expressions_and_the_train_experiment(tmp_path, monkeypatch):

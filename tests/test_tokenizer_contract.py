@@ -4,11 +4,12 @@ No CLIP vocabulary is reachable offline, so the directory is synthesised here: C
 and with the end-of-word marker), a handful of merges, and the two special tokens.  What is pinned is everything that does not depend
 on WHICH merges the real vocabulary holds: `prepare_inputs` (reference ddpo/diffusers_patch/pipeline_flax_stable_diffusion.py:148-161)
 pads to `model_max_length` = 77 with the end-of-text id, truncates long prompts to 77 keeping <bos> ... <eos>, returns numpy ids, and
-`make_uncond_text` (reference ddpo/datasets/bucket.py:66-73) is the padded empty prompt.  Where /root/reference exists (this container,
-not the GPU box) the reference's own `prepare_inputs` body is lifted with `ast` and run on the same tokenizer: ids must be equal."""
-import ast
+`make_uncond_text` (reference ddpo/datasets/bucket.py:66-73) is the padded empty prompt.  The ids that the reference's own `prepare_inputs`
+body (lifted with `ast`) returns on the same tokenizer are stored in tests/golden/reference_contracts.json
+(tests/golden/make_reference_contract_goldens.py): ours must be equal."""
 import json
 import os
+import pathlib
 
 import numpy as np
 import pytest
@@ -16,13 +17,12 @@ import pytest
 from ddpo_amd.diffusers_patch.pipeline_stable_diffusion import StableDiffusionPipeline
 from ddpo_amd.models.text import load_tokenizer, make_uncond_text
 
-REF = "/root/reference/ddpo/diffusers_patch/pipeline_flax_stable_diffusion.py"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_contracts.json")
 
 
-@pytest.fixture(scope="module")
-def tok_dir(tmp_path_factory):
-    root = tmp_path_factory.mktemp("sd")
-    d = root / "tokenizer"
+def write_tokenizer(root):
+    """Writes the synthetic `tokenizer/` directory under `root` (also used by tests/golden/make_reference_contract_goldens.py)."""
+    d = pathlib.Path(root) / "tokenizer"
     d.mkdir()
     # byte-level BPE alphabet: printable bytes map to themselves, the other bytes to code points from 256 upwards
     keep = [b for b in range(256) if 33 <= b <= 126 or 161 <= b <= 172 or 174 <= b <= 255]
@@ -37,6 +37,12 @@ def tok_dir(tmp_path_factory):
     (d / "tokenizer_config.json").write_text(json.dumps({"model_max_length": 77, "tokenizer_class": "CLIPTokenizer"}))
     (d / "special_tokens_map.json").write_text(json.dumps({"bos_token": "<|startoftext|>", "eos_token": "<|endoftext|>",
                                                            "unk_token": "<|endoftext|>", "pad_token": "<|endoftext|>"}))
+
+
+@pytest.fixture(scope="module")
+def tok_dir(tmp_path_factory):
+    root = tmp_path_factory.mktemp("sd")
+    write_tokenizer(root)
     return str(root)
 
 
@@ -67,20 +73,12 @@ def test_prepare_inputs_pads_and_truncates_like_the_reference(tok_dir):
     assert un.shape == (3, 77) and all(np.array_equal(r, ids[1]) for r in un)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference tree is only present in the build container")
 def test_prepare_inputs_equals_the_reference_method_on_the_same_tokenizer(tok_dir):
-    tok = load_tokenizer(tok_dir)
-    tree = ast.parse(open(REF).read())
-    fn = next(n for c in tree.body if isinstance(c, ast.ClassDef) and c.name == "FlaxStableDiffusionPipeline"
-              for n in c.body if isinstance(n, ast.FunctionDef) and n.name == "prepare_inputs")
-    ns = {"Union": __import__("typing").Union, "List": __import__("typing").List}
-    exec(compile(ast.Module(body=[fn], type_ignores=[]), REF, "exec"), ns)
-
-    class Self:
-        tokenizer = tok
-    ref_ids = ns["prepare_inputs"](Self(), PROMPTS)
-    ours = StableDiffusionPipeline(None, None, None, tokenizer=tok).prepare_inputs(PROMPTS)
-    assert ref_ids.dtype == ours.dtype and np.array_equal(ref_ids, ours)
+    with open(GOLDEN) as f:
+        ref = json.load(f)["prepare_inputs"]
+    assert ref["prompts"] == PROMPTS
+    ours = StableDiffusionPipeline(None, None, None, tokenizer=load_tokenizer(tok_dir)).prepare_inputs(PROMPTS)
+    assert str(ours.dtype) == ref["dtype"] and np.array_equal(ours, np.asarray(ref["ids"]))
 
 
 def test_mu_decay_env_is_honoured_when_the_flag_is_not_given(monkeypatch):

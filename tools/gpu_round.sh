@@ -4,6 +4,7 @@
 #   AB=1 appends the in-model fp32-fed vs plane-fed per-layer comparison and a DDPO_PLANES=1 bench line.
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+BENCH_OUT=${BENCH_OUT:-$PWD/bench_out}; mkdir -p "$BENCH_OUT"      # logs of the bench.py --full lines
 if [ "${PROBE:-0}" = "1" ]; then bash tools/probe_round.sh; fi
 python -c "import torch; print(torch.cuda.get_device_name(0))" > gpurun_out/device.txt 2>&1
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
@@ -13,7 +14,7 @@ tail -25 gpurun_out/pytest_gpu.log
 timeout 300 python __graft_entry__.py smoke > gpurun_out/smoke.log 2>&1; echo "smoke exit $?" >> gpurun_out/smoke.log; tail -3 gpurun_out/smoke.log
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-timeout 900 python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1; echo "bench exit $?" >> gpurun_out/bench.log; tail -5 gpurun_out/bench.log
+timeout 900 python bench.py --full ${BENCH_ARGS:-} > "$BENCH_OUT/bench.log" 2>&1; echo "bench exit $?" >> "$BENCH_OUT/bench.log"; tail -5 "$BENCH_OUT/bench.log"
 fi
 if [ "${AB:-0}" = "1" ]; then
 timeout 300 python tools/unet_gemm_breakdown.py 16 --ab > gpurun_out/gemm_breakdown_ab.log 2>&1; tail -40 gpurun_out/gemm_breakdown_ab.log

@@ -8,7 +8,7 @@ echo "== pytest"; timeout 900 python -m pytest tests/test_gpu_bf16_planes.py -m 
 for r in 1 2; do
 for e in 0 1; do
   echo "== C5 bench DDPO_BF16_PLANES=$e (round $r)"
-  DDPO_BF16_PLANES=$e timeout 900 python bench.py --model sd21 --resolution 768 --datapath bf16 --steps 1 --warmup 1 --no-cpu-baseline --no-train-extra --no-alt-datapath-extra 2>&1 | grep '^{"metric"' | python -c "
+  DDPO_BF16_PLANES=$e timeout 900 python bench.py --full --model sd21 --resolution 768 --datapath bf16 --steps 1 --warmup 1 --no-cpu-baseline --no-train-extra --no-alt-datapath-extra 2>&1 | grep '^{"metric"' | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d.get('roofline') or {}
 print(d['value'], d['unit'], d['ms_per_step'], 'ms | gemm family', r.get('achieved'), 'TF frac', r.get('frac'), '| dtype', d['dtype'])"

@@ -5,6 +5,7 @@
 # The PMC traffic pass stamps profiles/roofline_traffic.json with the hashes of csrc/: it must be the LAST thing that happens to the kernel sources
 # of the round — commit the stamped json and nothing under ddpo_amd/csrc after it.
 mkdir -p gpurun_out; export TMPDIR=/tmp
+BENCH_OUT=${BENCH_OUT:-$PWD/bench_out}; mkdir -p "$BENCH_OUT"      # logs of the bench.py --full lines
 R=$GRAFT_REPO_ROOT
 python -c "import torch; print(torch.cuda.get_device_name(0))" > gpurun_out/device.txt 2>&1
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
@@ -20,7 +21,7 @@ timeout 300 python __graft_entry__.py smoke > gpurun_out/r06_smoke.log 2>&1; ech
 N=2 timeout 900 bash tools/pmc_unet_traffic.sh > gpurun_out/r06_pmc_traffic.log 2>&1; tail -12 gpurun_out/r06_pmc_traffic.log | cut -c1-200
 # stamp it into profiles/roofline_traffic.json ON THE BOX so the bench line below carries it (re-run tools/stamp_traffic.py locally afterwards: adds the git commit)
 python tools/stamp_traffic.py f16mx > /dev/null 2>&1 && cp profiles/roofline_traffic.json gpurun_out/roofline_traffic_stamped.json
-timeout 900 python bench.py > gpurun_out/r06_bench_final.log 2>&1; echo "exit $?" >> gpurun_out/r06_bench_final.log; tail -2 gpurun_out/r06_bench_final.log | cut -c1-1500
+timeout 900 python bench.py --full > "$BENCH_OUT/r06_bench_final.log" 2>&1; echo "exit $?" >> "$BENCH_OUT/r06_bench_final.log"; tail -2 "$BENCH_OUT/r06_bench_final.log" | cut -c1-1500
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_s6 -o bench -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-train-extra --no-alt-datapath-extra > $R/gpurun_out/prof_s6.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_t6 -o bench -- python $R/bench.py --mode train --steps 1 --warmup 0 --no-cpu-baseline --no-roofline > $R/gpurun_out/prof_t6.log 2>&1
@@ -37,8 +38,8 @@ DDPO_FORCE_DIST=1 timeout 500 python -m torch.distributed.run --nnodes=1 --nproc
 DDPO_FORCE_DIST=1 DDPO_GRAD_OVERLAP=0 timeout 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 1 --mode epoch --steps 1 --warmup 1 --no-cpu-baseline --no-roofline > gpurun_out/r06_bench_epoch_rccl1_blocking.log 2>&1; tail -1 gpurun_out/r06_bench_epoch_rccl1_blocking.log | cut -c1-400
 (cd tools/native && timeout 120 ./kernel_probe attn 16 10 > ../../gpurun_out/r06_final_probe_attn.log 2>&1; tail -3 ../../gpurun_out/r06_final_probe_attn.log; for m in gemm2 mx x1; do PROBE_WKBLK=1 timeout 300 ./kernel_probe $m 16 10 > ../../gpurun_out/r06_final_probe_$m.log 2>&1; tail -1 ../../gpurun_out/r06_final_probe_$m.log; done)
 # BASELINE configs[4] (C5): SD-2.1 768^2 on the shipped datapath and on the config's named dtype (bfloat16 -> single-pass bf16 MFMA)
-timeout 500 python bench.py --model sd21 --resolution 768 --no-cpu-baseline --no-train-extra --no-alt-datapath-extra > gpurun_out/r06_bench_c5_sd21_768_f16mx.log 2>&1; tail -1 gpurun_out/r06_bench_c5_sd21_768_f16mx.log | cut -c1-300
-timeout 500 python bench.py --model sd21 --resolution 768 --datapath bf16 --no-cpu-baseline --no-train-extra --no-alt-datapath-extra > gpurun_out/r06_bench_c5_sd21_768_bf16.log 2>&1; tail -1 gpurun_out/r06_bench_c5_sd21_768_bf16.log | cut -c1-300
+timeout 500 python bench.py --full --model sd21 --resolution 768 --no-cpu-baseline --no-train-extra --no-alt-datapath-extra > "$BENCH_OUT/r06_bench_c5_sd21_768_f16mx.log" 2>&1; tail -1 "$BENCH_OUT/r06_bench_c5_sd21_768_f16mx.log" | cut -c1-300
+timeout 500 python bench.py --full --model sd21 --resolution 768 --datapath bf16 --no-cpu-baseline --no-train-extra --no-alt-datapath-extra > "$BENCH_OUT/r06_bench_c5_sd21_768_bf16.log" 2>&1; tail -1 "$BENCH_OUT/r06_bench_c5_sd21_768_bf16.log" | cut -c1-300
 timeout 300 python tools/unet_gemm_breakdown.py 16 --ab > gpurun_out/r06_gemm_breakdown_ab.log 2>&1; head -30 gpurun_out/r06_gemm_breakdown_ab.log | cut -c1-200
 timeout 300 bash tools/pmc_unet_clock.sh > /dev/null 2>&1; cp gpurun_out/pmc_unet_clock.md gpurun_out/r06_final_pmc_unet_clock.md; head -12 gpurun_out/pmc_unet_clock.md | cut -c1-200
 timeout 300 bash tools/pmc_unet_l2_mfma.sh > /dev/null 2>&1; cp gpurun_out/pmc_unet_l2_mfma.md gpurun_out/r06_final_pmc_unet_l2_mfma.md
