@@ -26,6 +26,10 @@ _PG_DEFAULTS = (
     # False: decay in f32, one rounding when mu is stored.  optax is not installable here, so the reading is a derivation, not a measurement.
     # None = not given on the command line: the entrypoint then takes DDPO_MU_DECAY_IN_BF16 (default 1 = True).
     ("mu_decay_in_bf16", None),
+    # engine-specific addition: LoRA adapters on the U-Net attention projections (ddpo_amd/models/lora.py).  lora_rank 0 = full fine-tuning
+    # (the reference's only mode); lora_alpha None = lora_rank (scale alpha / rank = 1).  LoRA usually wants a far higher learning_rate than
+    # the 1e-5 default of full fine-tuning; the default is not changed here.
+    ("lora_rank", 0), ("lora_alpha", None),
 )
 
 _SAMPLE_DEFAULTS = (

@@ -17,6 +17,10 @@ LIB_PATH = os.path.join(_HERE, "libddpo_hip.so")
 PRED_TYPES = {"epsilon": 0, "v_prediction": 1, "sample": 2}
 
 
+class LoraLayer(ctypes.Structure):
+    _fields_ = [("w0", c_void_p), ("w", c_void_p), ("a", c_void_p), ("b", c_void_p), ("K", c_int), ("N", c_int), ("r", c_int), ("s", c_float)]
+
+
 class DdimConsts(ctypes.Structure):
     _fields_ = [("alphas_cumprod", c_void_p), ("num_train_timesteps", c_int), ("step_ratio", c_int),
                 ("final_alpha_cumprod", c_float), ("eta", c_float), ("pred_type", c_int)]
@@ -131,6 +135,11 @@ _SIGS = {
     "ddpo_stage_cfg_inputs": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "ddpo_softmax_rows": (c_int, [c_void_p, c_int64, c_int, c_float, c_void_p]),
     "ddpo_scale_shift_clip": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p]),
+    # LoRA adapters (additive to ABI v14; csrc/lora.hip)
+    "ddpo_lora_merge": (c_int, [c_void_p, c_int, c_int64, c_void_p]),
+    "ddpo_lora_wgrad_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ddpo_lora_wgrad": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1459,3 +1468,61 @@ def scale_shift_clip(x, scale, shift, lo, hi):
     _check(load().ddpo_scale_shift_clip(_p(x), _p(out), x.numel(), float(scale), float(shift), float(lo), float(hi), _stream()),
            "ddpo_scale_shift_clip")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ LoRA adapters
+LORA_MAX_RANK = 64
+
+
+def lora_table(layers):
+    """[(w0, w, A, B, s)] -> (device uint8 tensor holding the ddpo_lora_layer descriptors, n_layers, max K * N) for lora_merge.  Build it once per
+    adapter store: the descriptors hold raw device pointers, so every tensor named must outlive the table."""
+    arr = (LoraLayer * len(layers))()
+    max_kn = 0
+    for i, (w0, w, a, b, s) in enumerate(layers):
+        K, N = w.shape[0], w.shape[-1]
+        r = a.shape[1]
+        if w0.shape != w.shape or a.shape != (K, r) or b.shape != (r, N) or N % 4 or not 1 <= r <= LORA_MAX_RANK:
+            raise DdpoHipError(f"lora layer {i}: W {tuple(w.shape)}, W0 {tuple(w0.shape)}, A {tuple(a.shape)}, B {tuple(b.shape)} "
+                               f"(need A (K, r), B (r, N), N % 4 == 0, 1 <= r <= {LORA_MAX_RANK})")
+        for t in (w0, w, a, b):
+            _f32(t)
+            if not t.is_contiguous() or (t is not a and t.data_ptr() % 16):
+                raise DdpoHipError("lora_table: W0, W' and B must be contiguous and 16-byte aligned, A contiguous")
+        arr[i] = LoraLayer(w0.data_ptr(), w.data_ptr(), a.data_ptr(), b.data_ptr(), int(K), int(N), int(r), float(s))
+        max_kn = max(max_kn, K * N)
+    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+    return host.to(layers[0][1].device), len(layers), max_kn
+
+
+def lora_merge(table):
+    """W' = W0 + s * A B for every layer of `table` (lora_table's result) in one launch."""
+    dev, n, max_kn = table
+    _check(load().ddpo_lora_merge(_p(dev), int(n), int(max_kn), _stream()), "ddpo_lora_merge")
+
+
+def lora_wgrad(x, dy, A, B, dA, dB, s):
+    """dA (K, r) += s * x^T (dY B^T), dB (r, N) += s * (x A)^T dY — the adapter gradients of y = x (W0 + s A B).  x: fp32 (M, K) (a row-strided view
+    is taken as is) or the `Planes` a norm wrote in front of the layer (read natively, x = hi + lo: the operand the forward GEMM consumed)."""
+    M, N = dy.shape
+    K, r = A.shape
+    for t, nm in ((dy, "dy"), (A, "A"), (B, "B"), (dA, "dA"), (dB, "dB")):
+        _f32(t, nm)
+    if B.shape != (r, N) or dA.shape != A.shape or dB.shape != B.shape or not 1 <= r <= LORA_MAX_RANK:
+        raise DdpoHipError(f"lora_wgrad: A {tuple(A.shape)}, B {tuple(B.shape)}, dA {tuple(dA.shape)}, dB {tuple(dB.shape)}, dY {tuple(dy.shape)}")
+    if isinstance(x, Planes):
+        if x.fmt != 0 or x.rows != M or x.C != K:
+            raise DdpoHipError("lora_wgrad: the planes must be bf16 hi / lo planes of shape (M, K)")
+        xp, ldx, hi, lo, ldp = None, 0, _p(x.hi), _p(x.lo), x.ld
+    else:
+        _f32(x, "x")
+        if tuple(x.shape) != (M, K):
+            raise DdpoHipError(f"lora_wgrad: x {tuple(x.shape)} vs dY {tuple(dy.shape)} and A {tuple(A.shape)}")
+        ldx = int(x.stride(0)) if M > 1 else K
+        xp, hi, lo, ldp = _p_rows(x), None, None, 0
+    lddy = int(dy.stride(0)) if M > 1 else N
+    nb = int(load().ddpo_lora_wgrad_ws_bytes(M, K, N, r))
+    ws = _scratch(nb, dy.device, "lora")
+    _check(load().ddpo_lora_wgrad(xp, ldx, hi, lo, int(ldp), _p_rows(dy), lddy, _p(A), _p(B), _p(dA), _p(dB), int(M), int(K), int(N), int(r),
+                                  float(s), _p(ws), ws.numel(), _stream()), "ddpo_lora_wgrad")
+    return dA, dB

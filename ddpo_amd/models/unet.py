@@ -9,6 +9,7 @@ Activations are NHWC rows (B*H*W, C) in fp32; contractions run on the datapath s
 bf16 MFMA with the fp32 operands split into hi + lo planes: weights registered by `ParamStore.pack_bf16`).
 """
 import math
+import re
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Tuple
@@ -81,9 +82,26 @@ class ParamStore:
                 raise ValueError(f"{n}: expected {self.shapes[n]}, got {tuple(t.shape)}")
             v.copy_(t)
 
-    def pack_bf16(self, bwd=True):
+    def pack_bf16(self, bwd=True, names=None):
         """(Re)build the bf16 hi/lo planes of every contraction weight for the bf16 MFMA datapaths (lib.DATAPATH).
-        Call after loading weights and after every optimizer update."""
+        Call after loading weights and after every optimizer update.
+        names: repack only these kernels (the adapted tensors of a LoRA merge) — the same per-tensor packs as the full repack, so the same
+        planes; the fused q/k/v image of a self-attention is rebuilt when any of its attn1 to_q / to_k / to_v is among them."""
+        if names is not None:
+            sel = set(names)
+            qkv = []
+            for n, v in self.views.items():
+                if n not in sel or not n.endswith(".kernel"):
+                    continue
+                L.pack_weights(v, bwd=bwd)
+                if n.endswith(".ff.net_0.proj.kernel"):
+                    L.pack_weights_geglu(v, self.views[n[:-len("kernel")] + "bias"])
+                m = re.search(r"\.attn1\.to_[qkv]\.kernel$", n)
+                if QKV_FUSED and m and n[:m.start()] + ".attn1." not in qkv:
+                    qkv.append(n[:m.start()] + ".attn1.")
+            for pre in qkv:
+                self._pack_fused_qkv(pre)
+            return
         for n, v in self.views.items():
             if n.endswith(".kernel"):
                 L.pack_weights(v, bwd=bwd)
@@ -99,13 +117,17 @@ class ParamStore:
                     # order differs there, ~1e-7 relative; tests/test_gpu_model.py holds both to the tolerance).  The training forward keeps the
                     # three launches (its backward wants q, k, v as tensors), so sampler and training forward differ by that much in the
                     # self-attention inputs at such shapes — far below the 7e-5 margin of a first-update ratio to the clip boundary.
-                    pre = n[:-len("to_q.kernel")]
-                    parts = [v, self.views[pre + "to_k.kernel"], self.views[pre + "to_v.kernel"]]
-                    buf = self.fused_qkv.get(pre)
-                    if buf is None:
-                        buf = self.fused_qkv[pre] = torch.empty(v.shape[0], sum(t.shape[1] for t in parts), dtype=torch.float32, device=v.device)
-                    torch.cat(parts, dim=1, out=buf)
-                    L.pack_weights(buf, bwd=False)
+                    self._pack_fused_qkv(n[:-len("to_q.kernel")])
+
+    def _pack_fused_qkv(self, pre):
+        """The (K, 3C) fp32 copy [to_q | to_k | to_v] of the self-attention `pre` ("<…>.attn1.") and its planes."""
+        v = self.views[pre + "to_q.kernel"]
+        parts = [v, self.views[pre + "to_k.kernel"], self.views[pre + "to_v.kernel"]]
+        buf = self.fused_qkv.get(pre)
+        if buf is None:
+            buf = self.fused_qkv[pre] = torch.empty(v.shape[0], sum(t.shape[1] for t in parts), dtype=torch.float32, device=v.device)
+        torch.cat(parts, dim=1, out=buf)
+        L.pack_weights(buf, bwd=False)
 
     def init_synthetic(self, seed=0):
         """Random-init weights of the right architecture (no checkpoints are reachable offline)."""
@@ -275,29 +297,58 @@ def resnet_forward(P, name, x: Act, temb_act, groups, eps, tape=None, emit_plane
     return Act(out, x.B, x.H, x.W, cout, opl)
 
 
+class LoraGrads:
+    """The gradient view of the backward under LoRA (UNet2DCondition.lora set): no base parameter is trained.  `trains(name)` is False for every
+    parameter (its weight gradient, bias gradient and the launches feeding only them are skipped); the norms' dgamma / dbeta, which the
+    validated norm-backward kernels write next to dx, land in a small scratch sink."""
+
+    def __init__(self, shapes, device):
+        self.shapes = shapes
+        cmax = max(s[0] for n, s in shapes.items() if n.endswith(".scale"))
+        self.sink = torch.zeros(2, cmax, dtype=torch.float32, device=device)
+
+    def trains(self, name):
+        return False
+
+    def __getitem__(self, name):
+        stem, leaf = name.rsplit(".", 1)
+        if leaf == "scale" or (leaf == "bias" and stem + ".scale" in self.shapes):
+            return self.sink[0 if leaf == "scale" else 1, :self.shapes[name][0]]
+        raise KeyError(f"{name}: frozen under LoRA (no gradient)")
+
+
+def _trains(G):
+    """False under LoRA: the base parameters take no gradient."""
+    return not isinstance(G, LoraGrads)
+
+
 def resnet_backward(P, G, r, d_out, tctx):
     """Returns d_x (rows of x).  Parameter grads are accumulated into G; the time-embedding grad into tctx."""
     name, x, cout = r["name"], r["x"], r["cout"]
     B, H, W, HW = x.B, x.H, x.W, x.HW
+    tr = _trains(G)                  # False under LoRA: only data gradients (and the norms' sunk dgamma / dbeta) run here
     # out = conv2(h2) + res
-    L.conv2d_wgrad(r["h2"], d_out, G[name + ".conv2.kernel"], B, H, W, cout, cout, 3, dbias=G[name + ".conv2.bias"])
+    if tr:
+        L.conv2d_wgrad(r["h2"], d_out, G[name + ".conv2.kernel"], B, H, W, cout, cout, 3, dbias=G[name + ".conv2.bias"])
     d_h2 = L.conv2d_dgrad(d_out, P[name + ".conv2.kernel"], B, H, W, cout, cout, 3)
     if r["shortcut"]:
-        L.conv2d_wgrad(x.t, d_out, G[name + ".conv_shortcut.kernel"], B, H, W, x.C, cout, 1, dbias=G[name + ".conv_shortcut.bias"])
+        if tr:
+            L.conv2d_wgrad(x.t, d_out, G[name + ".conv_shortcut.kernel"], B, H, W, x.C, cout, 1, dbias=G[name + ".conv_shortcut.bias"])
         d_res = L.conv2d_dgrad(d_out, P[name + ".conv_shortcut.kernel"], B, H, W, x.C, cout, 1)
     else:
         d_res = d_out
     d_c1 = L.groupnorm_bwd(r["c1"], d_h2, r["st2"], P[name + ".norm2.scale"], B, HW, r["groups"], True,
                            G[name + ".norm2.scale"], G[name + ".norm2.bias"])
-    L.conv2d_wgrad(r["h1"], d_c1, G[name + ".conv1.kernel"], B, H, W, x.C, cout, 3)
-    if r["temb"]:
-        d_tproj = torch.zeros(B, cout, dtype=torch.float32, device=d_c1.device)
-        L.colsum_accum(d_c1, d_tproj, rows_per_seg=HW)                      # d(time_emb_proj output)[b] = sum over pixels of b
-        L.colsum_accum(d_tproj, G[name + ".conv1.bias"])                    # conv1 bias sees the same sums
-        L.linear_wgrad(tctx["temb_act"], d_tproj, G[name + ".time_emb_proj.kernel"], dbias=G[name + ".time_emb_proj.bias"])
-        tctx["d_temb_act"] = L.linear_dgrad(d_tproj, P[name + ".time_emb_proj.kernel"], residual=tctx["d_temb_act"])
-    else:
-        L.colsum_accum(d_c1, G[name + ".conv1.bias"])
+    if tr:                                 # (under LoRA the time path is frozen: no conv1 / time_emb_proj gradient, no d_temb_act)
+        L.conv2d_wgrad(r["h1"], d_c1, G[name + ".conv1.kernel"], B, H, W, x.C, cout, 3)
+        if r["temb"]:
+            d_tproj = torch.zeros(B, cout, dtype=torch.float32, device=d_c1.device)
+            L.colsum_accum(d_c1, d_tproj, rows_per_seg=HW)                      # d(time_emb_proj output)[b] = sum over pixels of b
+            L.colsum_accum(d_tproj, G[name + ".conv1.bias"])                    # conv1 bias sees the same sums
+            L.linear_wgrad(tctx["temb_act"], d_tproj, G[name + ".time_emb_proj.kernel"], dbias=G[name + ".time_emb_proj.bias"])
+            tctx["d_temb_act"] = L.linear_dgrad(d_tproj, P[name + ".time_emb_proj.kernel"], residual=tctx["d_temb_act"])
+        else:
+            L.colsum_accum(d_c1, G[name + ".conv1.bias"])
     d_h1 = L.conv2d_dgrad(d_c1, P[name + ".conv1.kernel"], B, H, W, x.C, cout, 3)
     return L.groupnorm_bwd(x.t, d_h1, r["st1"], P[name + ".norm1.scale"], B, HW, r["groups"], True,
                            G[name + ".norm1.scale"], G[name + ".norm1.bias"], dx_add=d_res)
@@ -309,10 +360,19 @@ class UNet2DCondition:
         self.device = torch.device(device)
         self.params = ParamStore(unet_param_shapes(cfg), self.device)
         self.grads = None
+        self.lora = None                  # models/lora.LoraStore when LoRA adapters are trained (backward: adapter gradients only)
         self._ctx_kv = {}                 # (cross-attention name, context rows) -> (K, V) of the text context (precompute_context)
         self._ctx_kv_active = False
         self._temb = None                 # time-projection table of a sampling call (precompute_timesteps)
         self._temb_active = False
+
+    def _grad_view(self):
+        """Where the running backward puts parameter gradients: the flat buffer, or under LoRA the frozen view (LoraGrads)."""
+        if self.lora is None:
+            return self.grads
+        if getattr(self, "_lora_grads", None) is None:
+            self._lora_grads = LoraGrads(self.params.shapes, self.device)
+        return self._lora_grads
 
     def ensure_grads(self):
         """Flat fp32 gradient-accumulation buffer with the parameter layout (AccumulatingTrainState.grad_acc)."""
@@ -351,16 +411,28 @@ class UNet2DCondition:
 
     def _attention_backward(self, name, rec, x_in, kv_in, d_o, B, N, C, heads, self_attn):
         """d_o: grad of the attention output (before to_out).  Returns the grad w.r.t. the (normed) attention input."""
-        P, G = self.params, self.grads
+        P, G = self.params, self._grad_view()
         dq, dk, dv = L.attention_bwd(rec["q"], rec["k"], rec["v"], rec["o"], d_o, rec["lse"], B, heads, N, rec["Nk"], C // heads)
-        L.linear_wgrad(x_in, dq, G[name + ".to_q.kernel"])
-        L.linear_wgrad(kv_in, dk, G[name + ".to_k.kernel"])
-        L.linear_wgrad(kv_in, dv, G[name + ".to_v.kernel"])
+        if _trains(G):
+            L.linear_wgrad(x_in, dq, G[name + ".to_q.kernel"])
+            L.linear_wgrad(kv_in, dk, G[name + ".to_k.kernel"])
+            L.linear_wgrad(kv_in, dv, G[name + ".to_v.kernel"])
+        else:
+            self._lora_wgrad(x_in, dq, name + ".to_q.kernel")
+            self._lora_wgrad(kv_in, dk, name + ".to_k.kernel")
+            self._lora_wgrad(kv_in, dv, name + ".to_v.kernel")
         d_x = L.linear_dgrad(dq, P[name + ".to_q.kernel"])
         if self_attn:
             d_x = L.linear_dgrad(dk, P[name + ".to_k.kernel"], residual=d_x)
             d_x = L.linear_dgrad(dv, P[name + ".to_v.kernel"], residual=d_x)
         return d_x
+
+    def _lora_wgrad(self, x, dy, kernel_name):
+        """Adapter gradients of an adapted layer (x: its forward input, fp32 or the norm's bf16 planes; dy: the gradient of its output)."""
+        A, B_, dA, dB = self.lora.layer(kernel_name)
+        if isinstance(x, L.Planes) and x.fmt != 0:
+            x = x.float()
+        L.lora_wgrad(x, dy, A, B_, dA, dB, self.lora.scale)
 
     def _transformer(self, name, x: Act, ctx, ctx_len, heads, tape=None, emit_planes=0, dest=None):
         """dest / strided x.t: as in resnet_forward (sampling: the block output lands in its consumer's concat buffer)."""
@@ -430,41 +502,54 @@ class UNet2DCondition:
         return Act(out, B, x.H, x.W, C, opl)
 
     def _transformer_backward(self, r, d_out):
-        P, G, cfg = self.params, self.grads, self.cfg
+        P, G, cfg = self.params, self._grad_view(), self.cfg
         name, x, heads = r["name"], r["x"], r["heads"]
         C, B, N, H, W = x.C, x.B, x.HW, x.H, x.W
         tb = name + ".transformer_blocks_0"
         gw = lambda n: G[n + ".kernel"]
+        tr = _trains(G)                    # False under LoRA: adapter gradients of the four projections, no base-weight gradient
         # out = proj_out(h3) + x
         if cfg.use_linear_projection:
-            L.linear_wgrad(r["h3"], d_out, gw(name + ".proj_out"), dbias=G[name + ".proj_out.bias"])
+            if tr:
+                L.linear_wgrad(r["h3"], d_out, gw(name + ".proj_out"), dbias=G[name + ".proj_out.bias"])
             d_h3 = L.linear_dgrad(d_out, P[name + ".proj_out.kernel"])
         else:
-            L.conv2d_wgrad(r["h3"], d_out, gw(name + ".proj_out"), B, H, W, C, C, 1, dbias=G[name + ".proj_out.bias"])
+            if tr:
+                L.conv2d_wgrad(r["h3"], d_out, gw(name + ".proj_out"), B, H, W, C, C, 1, dbias=G[name + ".proj_out.bias"])
             d_h3 = L.conv2d_dgrad(d_out, P[name + ".proj_out.kernel"], B, H, W, C, C, 1)
         # h3 = ff2(geglu(ff1(LN3(h2)))) + h2
-        L.linear_wgrad(r["gg"], d_h3, gw(tb + ".ff.net_2"), dbias=G[tb + ".ff.net_2.bias"])
+        if tr:
+            L.linear_wgrad(r["gg"], d_h3, gw(tb + ".ff.net_2"), dbias=G[tb + ".ff.net_2.bias"])
         d_gg = L.linear_dgrad(d_h3, P[tb + ".ff.net_2.kernel"])
         d_f = L.geglu_bwd(r["f"], d_gg)
-        L.linear_wgrad(r["l3"], d_f, gw(tb + ".ff.net_0.proj"), dbias=G[tb + ".ff.net_0.proj.bias"])
+        if tr:
+            L.linear_wgrad(r["l3"], d_f, gw(tb + ".ff.net_0.proj"), dbias=G[tb + ".ff.net_0.proj.bias"])
         d_l3 = L.linear_dgrad(d_f, P[tb + ".ff.net_0.proj.kernel"])
         d_h2 = L.layernorm_bwd(r["h2"], d_l3, P[tb + ".norm3.scale"], G[tb + ".norm3.scale"], G[tb + ".norm3.bias"], 1e-5, dx_add=d_h3)
         # h2 = to_out(attn2(LN2(h1), ctx)) + h1
-        L.linear_wgrad(r["a2r"]["o"], d_h2, gw(tb + ".attn2.to_out_0"), dbias=G[tb + ".attn2.to_out_0.bias"])
+        if tr:
+            L.linear_wgrad(r["a2r"]["o"], d_h2, gw(tb + ".attn2.to_out_0"), dbias=G[tb + ".attn2.to_out_0.bias"])
+        else:
+            self._lora_wgrad(r["a2r"]["o"], d_h2, tb + ".attn2.to_out_0.kernel")
         d_a2 = L.linear_dgrad(d_h2, P[tb + ".attn2.to_out_0.kernel"])
         d_l2 = self._attention_backward(tb + ".attn2", r["a2r"], r["l2"], r["ctx"], d_a2, B, N, C, heads, False)
         d_h1 = L.layernorm_bwd(r["h1"], d_l2, P[tb + ".norm2.scale"], G[tb + ".norm2.scale"], G[tb + ".norm2.bias"], 1e-5, dx_add=d_h2)
         # h1 = to_out(attn1(LN1(h0))) + h0
-        L.linear_wgrad(r["a1r"]["o"], d_h1, gw(tb + ".attn1.to_out_0"), dbias=G[tb + ".attn1.to_out_0.bias"])
+        if tr:
+            L.linear_wgrad(r["a1r"]["o"], d_h1, gw(tb + ".attn1.to_out_0"), dbias=G[tb + ".attn1.to_out_0.bias"])
+        else:
+            self._lora_wgrad(r["a1r"]["o"], d_h1, tb + ".attn1.to_out_0.kernel")
         d_a1 = L.linear_dgrad(d_h1, P[tb + ".attn1.to_out_0.kernel"])
         d_l1 = self._attention_backward(tb + ".attn1", r["a1r"], r["l1"], r["l1"], d_a1, B, N, C, heads, True)
         d_h0 = L.layernorm_bwd(r["h0"], d_l1, P[tb + ".norm1.scale"], G[tb + ".norm1.scale"], G[tb + ".norm1.bias"], 1e-5, dx_add=d_h1)
         # h0 = proj_in(GN(x))
         if cfg.use_linear_projection:
-            L.linear_wgrad(r["hn"], d_h0, gw(name + ".proj_in"), dbias=G[name + ".proj_in.bias"])
+            if tr:
+                L.linear_wgrad(r["hn"], d_h0, gw(name + ".proj_in"), dbias=G[name + ".proj_in.bias"])
             d_hn = L.linear_dgrad(d_h0, P[name + ".proj_in.kernel"])
         else:
-            L.conv2d_wgrad(r["hn"], d_h0, gw(name + ".proj_in"), B, H, W, C, C, 1, dbias=G[name + ".proj_in.bias"])
+            if tr:
+                L.conv2d_wgrad(r["hn"], d_h0, gw(name + ".proj_in"), B, H, W, C, C, 1, dbias=G[name + ".proj_in.bias"])
             d_hn = L.conv2d_dgrad(d_h0, P[name + ".proj_in.kernel"], B, H, W, C, C, 1)
         return L.groupnorm_bwd(x.t, d_hn, r["st"], P[name + ".norm.scale"], B, N, cfg.norm_groups, False,
                                G[name + ".norm.scale"], G[name + ".norm.bias"], dx_add=d_out)
@@ -841,7 +926,10 @@ class UNet2DCondition:
         on this stream (the backward runs through the parameters from the end of the buffer to its start); the data-parallel
         trainer hangs the bucketed all-reduce on it (training/distributed.GradBucketer)."""
         P, cfg = self.params, self.cfg
-        G = self.ensure_grads()
+        if self.lora is None:
+            self.ensure_grads()
+        G = self._grad_view()
+        tr = _trains(G)
         prog = UNet2DCondition._Progress(self.params.offsets) if on_ready is not None else None
 
         def done(prefix):
@@ -857,7 +945,8 @@ class UNet2DCondition:
         x = tail["x"]
         B, H, W = x.B, x.H, x.W
         d = L.nchw_to_nhwc(d_out.contiguous())                                 # (B*H*W, C_out)
-        L.conv2d_wgrad(tail["hn"], d, G["conv_out.kernel"], B, H, W, x.C, cfg.out_channels, 3, dbias=G["conv_out.bias"])
+        if tr:
+            L.conv2d_wgrad(tail["hn"], d, G["conv_out.kernel"], B, H, W, x.C, cfg.out_channels, 3, dbias=G["conv_out.bias"])
         d = L.conv2d_dgrad(d, P["conv_out.kernel"], B, H, W, x.C, cfg.out_channels, 3)
         d = L.groupnorm_bwd(x.t, d, tail["st"], P["conv_norm_out.scale"], B, x.HW, cfg.norm_groups, True,
                             G["conv_norm_out.scale"], G["conv_norm_out.bias"])
@@ -881,13 +970,15 @@ class UNet2DCondition:
                 d = d_h
             elif kind == "up":
                 xx, name = r["x"], r["name"]
-                L.conv2d_wgrad(xx.t, d, G[name + ".kernel"], xx.B, xx.H, xx.W, xx.C, xx.C, 3, upsample=True, dbias=G[name + ".bias"])
+                if tr:
+                    L.conv2d_wgrad(xx.t, d, G[name + ".kernel"], xx.B, xx.H, xx.W, xx.C, xx.C, 3, upsample=True, dbias=G[name + ".bias"])
                 d_up = L.conv2d_dgrad(d, P[name + ".kernel"], xx.B, 2 * xx.H, 2 * xx.W, xx.C, xx.C, 3)
                 d = L.sumpool2x2(d_up, xx.B, xx.H, xx.W, xx.C)
                 done(name)
             elif kind == "down":
                 xx, name = r["x"], r["name"]
-                L.conv2d_wgrad(xx.t, d, G[name + ".kernel"], xx.B, xx.H, xx.W, xx.C, xx.C, 3, stride=2, pad=1, dbias=G[name + ".bias"])
+                if tr:
+                    L.conv2d_wgrad(xx.t, d, G[name + ".kernel"], xx.B, xx.H, xx.W, xx.C, xx.C, 3, stride=2, pad=1, dbias=G[name + ".bias"])
                 d = L.conv2d_dgrad(d, P[name + ".kernel"], xx.B, xx.H, xx.W, xx.C, xx.C, 3, stride=2)
                 done(name)
             elif kind == "skip_push":
@@ -895,6 +986,8 @@ class UNet2DCondition:
                 d = L.add(d, skip_grads.pop())
             else:
                 raise RuntimeError(kind)
+        if not tr:
+            return                       # LoRA: nothing below the U-Net body trains (conv_in, the time-embedding MLP)
         # conv_in output was the first skip
         d = L.add(d, skip_grads.pop())
         assert not skip_grads

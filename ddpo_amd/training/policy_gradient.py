@@ -54,18 +54,24 @@ class AccumulatingTrainState:
     """TrainState that accumulates gradients over several steps before applying them (reference :13-57).
 
     fields: step, params (the U-Net's flat ParamStore), opt_state {count, mu (bf16), nu (fp32)}, grad_acc (flat), n_acc.
+    LoRA mode (`lora`: a models/lora.LoraStore attached to the U-Net): the optimizer state, the gradient buffer and the update are the
+    adapters' (`trainable` = lora.params); after each update lora.merge() rewrites the adapted U-Net weights and repacks only those.
     """
 
-    def __init__(self, unet, tx: AdamWConfig, process_group=None):
+    def __init__(self, unet, tx: AdamWConfig, process_group=None, lora=None):
         self.unet = unet
         self.apply_fn = unet.forward
         self.params = unet.params
+        self.lora = lora
+        if lora is not None and unet.lora is not lora:
+            raise ValueError("the LoraStore must be attached to this U-Net (LoraStore(unet, ...))")
+        self.trainable = unet.params if lora is None else lora.params
         self.tx = tx
         self.step = 0
         self.n_acc = 0
-        self.grad_acc = unet.ensure_grads()
-        n = self.params.flat.numel()
-        dev = self.params.flat.device
+        self.grad_acc = unet.ensure_grads() if lora is None else lora.grads
+        n = self.trainable.flat.numel()
+        dev = self.trainable.flat.device
         self.opt_state = {"count": 0, "mu": torch.zeros(n, dtype=torch.bfloat16, device=dev),
                           "nu": torch.zeros(n, dtype=torch.float32, device=dev)}
         self._sqnorm = torch.zeros(1, dtype=torch.float64, device=dev)
@@ -90,7 +96,8 @@ class AccumulatingTrainState:
         from .distributed import GradBucketer, _through_backend
         # world 1 only under DDPO_FORCE_DIST=1 (a one-rank RCCL group: the side stream, the per-bucket async all_reduce and finish() all
         # execute on hardware, tests/test_gpu_rccl_single_rank.py); a plain single process has no process group and keeps graph replay
-        if not _through_backend() or os.environ.get("DDPO_GRAD_OVERLAP", "1") == "0":
+        if self.lora is not None or not _through_backend() or os.environ.get("DDPO_GRAD_OVERLAP", "1") == "0":
+            # (LoRA: a few MB of adapter gradients — one blocking all-reduce in apply_gradients)
             return None
         mib = float(os.environ.get("DDPO_GRAD_BUCKET_MIB", "256"))      # 256 MiB = 14 buckets over the 3.44 GB SD-1.5 gradient
         return GradBucketer(self.grad_acc.flat, bucket_numel=int(mib * (1 << 20)) // 4, group=self.process_group)
@@ -111,11 +118,13 @@ class AccumulatingTrainState:
         L.grad_sqnorm(g, self._sqnorm)
         t = self.opt_state["count"] + 1
         tx = self.tx
-        L.adamw_bf16mu_step(self.params.flat, g, self.opt_state["mu"], self.opt_state["nu"], self._sqnorm, inv,
+        L.adamw_bf16mu_step(self.trainable.flat, g, self.opt_state["mu"], self.opt_state["nu"], self._sqnorm, inv,
                             tx.learning_rate, tx.b1, tx.b2, tx.eps, tx.weight_decay, tx.max_grad_norm, t,
                             mu_decay_in_bf16=tx.mu_decay_in_bf16, zero_grad=True)
         self.last_grad_norm = torch.sqrt(self._sqnorm.clone()) * inv       # device scalar, no host sync
-        if L.current_datapath() != "fp32":
+        if self.lora is not None:
+            self.lora.merge()                                              # W' = W0 + s A B; repack of the adapted tensors only
+        elif L.current_datapath() != "fp32":
             self.params.pack_bf16()                                        # refresh the bf16 hi/lo weight planes
         self.opt_state["count"] = t
         self.step += 1
@@ -156,7 +165,8 @@ def _graphed_fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale
     """Replay of _fwd_bwd as a captured HIP graph (one per batch geometry / hyper-parameter set): ~3000 kernel launches per
     micro-step become one graph launch.  Gradients still accumulate into the same flat buffer."""
     key = (tuple(batch["latents"].shape), tuple(batch["prompt_embeds"].shape), bool(train_cfg), float(guidance_scale), float(eta),
-           float(clip_range), sched_state.num_inference_steps, L.current_datapath(), group)
+           float(clip_range), sched_state.num_inference_steps, L.current_datapath(), group,
+           0 if state.lora is None else state.lora.rank)
     cache = state.__dict__.setdefault("_graphs", {})
     ent = cache.get(key)
     if ent == "eager":

@@ -310,11 +310,16 @@ def save_checkpoint(ckpt_dir, params, step, resume_state=None, flax_format=True,
         from .flax_msgpack import save_flax_checkpoint
         save_flax_checkpoint(ckpt_dir, {n: v.numpy() for n, v in host.items()}, step)
     if synthetic_weights:             # a run on random-init weights must not pass for a fine-tuned model
-        with open(os.path.join(ckpt_dir, "SYNTHETIC_WEIGHTS"), "w") as f:
-            f.write("this run started from deterministic random-init weights (DDPO_ALLOW_SYNTHETIC=1), not from a pretrained model\n")
+        mark_synthetic(ckpt_dir)
     if resume_state is not None:
         torch.save(dict(resume_state, synthetic_weights=bool(synthetic_weights)), os.path.join(ckpt_dir, f"resume_{step}.pt"))
     return path
+
+
+def mark_synthetic(ckpt_dir):
+    """The SYNTHETIC_WEIGHTS marker of a checkpoint directory whose run started from random-init weights."""
+    with open(os.path.join(ckpt_dir, "SYNTHETIC_WEIGHTS"), "w") as f:
+        f.write("this run started from deterministic random-init weights (DDPO_ALLOW_SYNTHETIC=1), not from a pretrained model\n")
 
 
 def save_rank_resume(ckpt_dir, step, rank, rank_state):

@@ -402,6 +402,29 @@ int ddpo_sumpool2x2(const float* x, float* y, int B, int H, int W, int C, void* 
 int ddpo_add(const float* a, const float* b, float* out, int64_t n, void* stream);
 int ddpo_scale_shift_clip(const float* x, float* y, int64_t n, float scale, float shift, float lo, float hi, void* stream);
 
+/* ---- LoRA adapters on the attention projections (additive to ABI v14; csrc/lora.hip).
+ * One adapted dense layer with Flax kernel W (K = in, N = out): W' = W0 + s * A B, A (K, r), B (r, N), all fp32 row-major. */
+typedef struct ddpo_lora_layer {
+  const float* w0;   /* frozen base weight (K, N), 16-byte aligned */
+  float* w;          /* merged weight W' (K, N), 16-byte aligned (may not alias w0) */
+  const float* a;    /* (K, r) */
+  const float* b;    /* (r, N), 16-byte aligned */
+  int K, N, r;       /* N % 4 == 0, 1 <= r <= 64 */
+  float s;           /* alpha / r */
+} ddpo_lora_layer;
+/* W' = W0 + s * A B for n_layers layers in ONE launch; `table_dev` is a DEVICE array of n_layers descriptors, max_kn >= every K * N (< 2^33).
+ * Per element: acc = sum_{j = 0..r-1} A[k, j] B[j, n] (fp32 fma, j ascending); W' = W0 bit for bit where s * acc == 0 (B == 0), else W0 + s * acc. */
+int ddpo_lora_merge(const ddpo_lora_layer* table_dev, int n_layers, int64_t max_kn, void* stream);
+/* Adapter gradients of one layer y = x W': dA (K, r) += s * x^T (dY B^T), dB (r, N) += s * (x A)^T dY, fp32, bitwise reproducible (fixed-order
+ * partial slabs in ws, no atomics; two launches on `stream`).  x is EITHER fp32 rows (x, row stride ldx; x_hi = x_lo = NULL) OR, x == NULL, the
+ * bf16 hi / lo activation planes (x = hi + lo) with the plane convention of the norms: ld_planes > 0 row-major, 0 k-blocked (K / 32, M, 32).
+ * dY (M, N) fp32 with row stride lddy.  K % 4 == N % 4 == 0, K, N <= 2048, K + N <= 4064, 1 <= r <= 64; fp32 pointers 16-byte aligned.
+ * ws: 16-byte aligned scratch of ddpo_lora_wgrad_ws_bytes(M, K, N, r) bytes. */
+size_t ddpo_lora_wgrad_ws_bytes(int M, int K, int N, int r);
+int ddpo_lora_wgrad(const float* x, int ldx, const uint16_t* x_hi, const uint16_t* x_lo, int ld_planes, const float* dy, int lddy,
+                    const float* A, const float* B, float* dA, float* dB, int M, int K, int N, int r, float s, void* ws, size_t ws_bytes,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,8 @@ class Parser(utils.Parser):
 
 
 def main(argv=None):
+    from ddpo_amd.models.lora import reject_lora_flags
+    reject_lora_flags(sys.argv[1:] if argv is None else argv)
     worker_id, n_workers = D.init()
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():

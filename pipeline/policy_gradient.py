@@ -38,7 +38,7 @@ from ddpo_amd.training.dp import DataParallel
 from ddpo_amd.training.policy_gradient import (AccumulatingTrainState, AdamWConfig, train_fuse_default, train_step,
                                                train_steps_fused)
 from ddpo_amd.utils import prng
-from ddpo_amd.utils.serialization import load_params_file, load_resume, load_unet, save_checkpoint, save_rank_resume
+from ddpo_amd.utils.serialization import load_params_file, load_resume, load_unet, mark_synthetic, save_checkpoint, save_rank_resume
 from ddpo_amd.utils.stat_tracking import PerPromptStatTracker
 from ddpo_amd.models.text import make_uncond_text
 
@@ -53,6 +53,11 @@ def _flag(value, default):
 class Parser(utils.Parser):
     config: str = "config.base"
     dataset: str = "consistent_imagenet"
+
+
+def lora_seed(args, dp):
+    """Seed of the LoRA adapters' initialisation: the configured seed without the per-process offset parser.set_seed added (the same on every rank)."""
+    return int(args.seed) - int(dp.seed_process_index)
 
 
 def main(argv=None):
@@ -110,6 +115,13 @@ def main(argv=None):
     print("initializing train state...")
     if args.optimizer != "adamw":
         raise NotImplementedError("only the adamw optimizer of the reference configs is implemented")
+    lora = None
+    if args.lora_rank:
+        # adapters on the attention projections; the pretrained weights are W0.  Drawn on the host from the BASE seed (args.seed carries the
+        # per-process offset of parser.set_seed), so every rank starts from the same adapters and applies the same all-reduced updates to them
+        from ddpo_amd.models.lora import LoraStore
+        lora = LoraStore(unet, args.lora_rank, alpha=args.lora_alpha, seed=lora_seed(args, dp))
+        print(f"[ policy_gradient ] LoRA rank {lora.rank}, scale {lora.scale:g}: {lora.n_params} trainable parameters on {len(lora.targets)} layers")
     state = AccumulatingTrainState(unet, AdamWConfig(learning_rate=args.learning_rate, b1=args.beta1, b2=args.beta2,
                                                      eps=args.epsilon, weight_decay=args.weight_decay,
                                                      max_grad_norm=args.max_grad_norm,
@@ -119,7 +131,8 @@ def main(argv=None):
                                                      # oracle/optim.py.  `--mu_decay_in_bf16 False` / DDPO_MU_DECAY_IN_BF16=0 selects the all-f32
                                                      # reading (decay in f32, one rounding at the store) should a real optax run disagree.
                                                      mu_decay_in_bf16=_flag(getattr(args, "mu_decay_in_bf16", None),
-                                                                            os.environ.get("DDPO_MU_DECAY_IN_BF16", "1") != "0")))
+                                                                            os.environ.get("DDPO_MU_DECAY_IN_BF16", "1") != "0")),
+                                   lora=lora)
     sampling_scheduler_params = params["scheduler"]
 
     timer = utils.Timer()
@@ -148,9 +161,24 @@ def main(argv=None):
         # not in the reference (it never loads a policy-gradient run): continue from <run>/checkpoints — parameters, AdamW moments
         # and count, the sampling key, the host RNG streams of this rank, the per-prompt tracker and the reward history
         rs = load_resume(os.environ["DDPO_RESUME"], worker_id, os.environ.get("DDPO_RESUME_EPOCH"))
-        load_params_file(state.params, rs["params_path"])
-        if L.DATAPATH != "fp32":
-            state.params.pack_bf16()
+        if lora is not None:
+            # LoRA: the base weights are the pretrained ones already loaded (W0); the bundle carries the adapters
+            if "lora_params" not in rs:
+                raise SystemExit(f"DDPO_RESUME: epoch {rs['epoch']} of {os.environ['DDPO_RESUME']} is a full fine-tuning checkpoint; "
+                                 f"it cannot continue with --lora_rank {lora.rank}")
+            if int(rs["lora_rank"]) != lora.rank or rs["lora_alpha"] != lora.alpha:
+                raise SystemExit(f"DDPO_RESUME: the run was trained with lora_rank {rs['lora_rank']}, lora_alpha {rs['lora_alpha']}; "
+                                 f"this one asks for lora_rank {lora.rank}, lora_alpha {lora.alpha}")
+            lora.params.flat.copy_(rs["lora_params"])
+            lora.merge()
+            rs["params_path"] = os.path.join(os.environ["DDPO_RESUME"], f"lora_{rs['epoch']}.safetensors")
+        else:
+            if "lora_params" in rs:
+                raise SystemExit(f"DDPO_RESUME: epoch {rs['epoch']} of {os.environ['DDPO_RESUME']} is a LoRA checkpoint (lora_rank "
+                                 f"{rs['lora_rank']}); pass the same --lora_rank / --lora_alpha to continue it")
+            load_params_file(state.params, rs["params_path"])
+            if L.DATAPATH != "fp32":
+                state.params.pack_bf16()
         state.opt_state["mu"].copy_(rs["mu"])
         state.opt_state["nu"].copy_(rs["nu"])
         state.opt_state["count"] = state.step = int(rs["opt_count"])
@@ -288,8 +316,18 @@ def main(argv=None):
                           "nu": state.opt_state["nu"].cpu(), "sample_rng": sample_rng,
                           "tracker": None if per_prompt_stats is None else per_prompt_stats.state_dict(),
                           "mean_rewards": list(mean_rewards), "std_rewards": list(std_rewards), "wall": list(wall)}
-                save_checkpoint(os.path.join(args.savepath, "checkpoints"), state.params, step=epoch, resume_state=resume,
-                                synthetic_weights=pipeline.synthetic_weights)
+                if lora is not None:           # adapters only (diffusers attention-processor keys) + the resume bundle
+                    ckdir = os.path.join(args.savepath, "checkpoints")
+                    os.makedirs(ckdir, exist_ok=True)
+                    lora.save(os.path.join(ckdir, f"lora_{epoch}.safetensors"), synthetic_weights=pipeline.synthetic_weights)
+                    if pipeline.synthetic_weights:        # as save_checkpoint does: adapters of random-init weights must not pass for a fine-tune
+                        mark_synthetic(ckdir)
+                    resume.update(lora_params=lora.params.flat.cpu(), lora_rank=lora.rank, lora_alpha=lora.alpha,
+                                  synthetic_weights=bool(pipeline.synthetic_weights))
+                    torch.save(resume, os.path.join(ckdir, f"resume_{epoch}.pt"))
+                else:
+                    save_checkpoint(os.path.join(args.savepath, "checkpoints"), state.params, step=epoch, resume_state=resume,
+                                    synthetic_weights=pipeline.synthetic_weights)
             D.barrier()
 
         if worker_id == 0:
