@@ -95,6 +95,9 @@ llava_vqa = _dataset("llava-vqa-v2", "vqa_dataset", "llava_vqa", {"loadpath": "a
 llava_counting = _dataset("llava-counting-v0-8", "counting", "llava_vqa",
                           {"nouns_path": "assets/very_simple_animals.txt", "number_range": (2, 8)})
 llava_bertscore = _dataset("llava-bertscore-2-simple-animals", "nouns_activities", "llava_bertscore", _NOUNS_ACTIVITIES)
+# prompt alignment without a server: CLIPScore on the engine's own CLIP towers (ddpo_amd/models/clip_score.py)
+clip_nouns_activities = _dataset("clip-score-nouns-activities", "nouns_activities", "clip_score", _NOUNS_ACTIVITIES)
+clip_animals = _dataset("clip-score-simple-animals", "from_file", "clip_score", _ANIMALS)
 a_dog_1 = _dataset("aesthetic_dogs_sweep/one", "manual", "aesthetic", {"prompts": ["a dog"]}, per_prompt_stats_bufsize=None,
                    per_prompt_stats_min_count=None, train_batch_size=1, train_accumulation_steps=2)
 a_dog_2 = _dataset("aesthetic_dogs_sweep/imagenet", "imagenet_dogs", "aesthetic", {}, train_batch_size=1,

@@ -140,6 +140,10 @@ _SIGS = {
     "ddpo_lora_wgrad_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "ddpo_lora_wgrad": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
+    # CLIP text tower + CLIPScore reward (additive to ABI v14; csrc/clip_text.hip)
+    "ddpo_attention_causal_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "ddpo_gather_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "ddpo_cosine_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1131,6 +1135,21 @@ def attention(q, k, v, B, heads, Nq, Nk, d, scale=None, out=None, ldq=None, ldk=
     return (out, lse) if return_lse else out
 
 
+CAUSAL_MAX_N = 80       # ddpo_attention_causal_fwd holds all keys of a (batch, head) in LDS
+
+
+def attention_causal(q, k, v, B, heads, N, d, scale=None, out=None, ldq=None, ldk=None, ldv=None, ldo=None):
+    """Causal self-attention (mask key <= query) of the CLIP text tower: N <= CAUSAL_MAX_N tokens, d in (16, 64), exact-fp32 MFMA on every
+    datapath (ddpo_attention_causal_fwd).  q / k / v may be column blocks of one fused buffer (ld* = its row stride)."""
+    C = heads * d
+    sc = float(scale if scale is not None else d ** -0.5)
+    if out is None:
+        out = torch.empty(B * N, C, dtype=torch.float32, device=q.device)
+    _check(load().ddpo_attention_causal_fwd(_pr(q, ldq), int(ldq or C), _pr(k, ldk), int(ldk or C), _pr(v, ldv), int(ldv or C), _pr(out, ldo), int(ldo or C),
+                                            B, heads, N, d, sc, _stream()), "ddpo_attention_causal_fwd")
+    return out
+
+
 def attention_kv_images(k, v, B, heads, Nk, d, out=None, ldk=None, ldv=None):
     """Pack K / V (B*Nk, heads*d) once into the per-tile images of the bf16x3 attention kernels (uint8 tensor), for keys / values that
     stay constant over many attention calls (the text context over the DDIM steps).  Returns None where the datapath / head dim has no
@@ -1410,6 +1429,43 @@ def l2_normalize_rows(x):
     rows, cols = x.shape
     out = torch.empty_like(x)
     _check(load().ddpo_l2_normalize_rows(_p(x), _p(out), rows, cols, _stream()), "ddpo_l2_normalize_rows")
+    return out
+
+
+def gather_rows(table, idx, add=None, out=None):
+    """out[r] = table[idx[r]] (+ add[r % len(add)]): table (T, cols) row-major (a row-strided view is fine), idx int32 on the device, add
+    (period, cols) contiguous.  The kernel clamps an out-of-range index into the table; callers that build `idx` from user data validate it
+    on the host first (`check_indices`)."""
+    if table.dim() != 2 or idx.dtype != torch.int32 or idx.dim() != 1:
+        raise DdpoHipError("gather_rows needs a 2-D table and a 1-D int32 index tensor")
+    rows, cols = idx.numel(), table.shape[1]
+    if add is not None and (add.dim() != 2 or add.shape[1] != cols):
+        raise DdpoHipError(f"gather_rows: add must be (period, {cols}), got {tuple(add.shape)}")
+    if out is None:
+        out = torch.empty(rows, cols, dtype=torch.float32, device=table.device)
+    _check(load().ddpo_gather_rows(_p_rows(_f32(table, "table")), int(table.stride(0)), int(table.shape[0]), _p(idx), rows, cols, _p(add),
+                                   int(add.shape[0]) if add is not None else 0, _p(out), _stream()), "ddpo_gather_rows")
+    return out
+
+
+def check_indices(idx, table_rows, what="index"):
+    """Host-side validation of gather indices (a numpy array) before they are uploaded: raises on anything outside [0, table_rows)."""
+    import numpy as np
+    idx = np.asarray(idx)
+    if idx.size and (idx.min() < 0 or idx.max() >= table_rows):
+        bad = idx[(idx < 0) | (idx >= table_rows)]
+        raise ValueError(f"{what} {int(bad.flat[0])} outside [0, {table_rows})")
+    return idx
+
+
+def cosine_rows(a, b, scale=1.0, out=None):
+    """out[r] = scale * cos(a_r, b_r) for two (rows, cols) tensors, one wave per row (ddpo_cosine_rows)."""
+    if a.shape != b.shape or a.dim() != 2:
+        raise DdpoHipError(f"cosine_rows needs two equal 2-D shapes, got {tuple(a.shape)} and {tuple(b.shape)}")
+    rows, cols = a.shape
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=a.device)
+    _check(load().ddpo_cosine_rows(_p(_f32(a, "a")), _p(_f32(b, "b")), rows, cols, float(scale), _p(out), _stream()), "ddpo_cosine_rows")
     return out
 
 

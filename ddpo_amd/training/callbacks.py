@@ -6,9 +6,10 @@ Behavioural mirror of the registry / calling convention of /root/reference/ddpo/
 images: float32 (N,H,W,3) in [0,1]; scores: (N,) or (N,1) numpy; info: dict of numpy arrays.
 Callbacks run in a worker thread of the entrypoint (ThreadPoolExecutor, max_workers=2) next to the sampling of the
 following batch, so they must not touch the sampler's HIP stream: the host ones below are pure CPU code and the
-on-device one (aesthetic) uses its own stream.
+on-device ones (aesthetic, clip_score) use their own streams.
 
-In scope (BASELINE.json configs): jpeg, neg_jpeg, aesthetic, llava_bertscore (+ its sibling llava_vqa wire format).
+In scope (BASELINE.json configs): jpeg, neg_jpeg, aesthetic, llava_bertscore (+ its sibling llava_vqa wire format), and clip_score: the
+prompt-alignment reward that needs no server (CLIPScore on the engine's own CLIP towers; not in the reference, which aligns through LLaVA).
 The other reward ideas of the reference (rotational / mirror symmetry, thumbnail, BLIP-2 vqa, ...) are not part of
 any benchmark config; add them as plugins with `register`.
 """
@@ -78,6 +79,25 @@ def aesthetic_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None)
         del prompts, metadata
         scores = scorer(np.asarray(images, dtype=np.float32))
         return scores[:, None], {"synthetic_weights": np.array(scorer.synthetic)}
+
+    return _wrapper
+
+
+# ------------------------------------------------------------------------------------------------ CLIPScore prompt alignment
+def clip_score_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None):
+    """reward = exp(logit_scale) * cos(CLIP image embedding, CLIP text embedding of the prompt) — the diagonal of transformers'
+    `CLIPModel.logits_per_image` — on the engine's own kernels (models/clip_score.py), on a private HIP stream.  Weights: the
+    `openai/clip-vit-large-patch14` checkpoint, looked up exactly like the aesthetic reward's (`weights_dir` or $DDPO_AESTHETIC_WEIGHTS
+    `/clip`, else the HF cache); nothing is downloaded.  Missing weights RAISE unless DDPO_ALLOW_SYNTHETIC=1, in which case
+    info['synthetic_weights'] is True.  Uses `prompts` (one string per image); `metadata` is ignored.  info['cosine'] is the raw cosine."""
+    del devices, jit
+    from ..models.clip_score import ClipScorer
+    scorer = ClipScorer(weights_dir=weights_dir, cache=cache, seed=rng)
+
+    def _wrapper(images, prompts, metadata):
+        del metadata
+        scores, cosine = scorer(np.asarray(images, dtype=np.float32), [str(p) for p in prompts], return_cosine=True)
+        return scores[:, None], {"cosine": cosine, "synthetic_weights": np.array(scorer.synthetic)}
 
     return _wrapper
 
@@ -185,6 +205,7 @@ callback_fns = {
     "jpeg": jpeg_fn,
     "neg_jpeg": neg_jpeg_fn,
     "aesthetic": aesthetic_fn,
+    "clip_score": clip_score_fn,
     "llava_bertscore": llava_bertscore,
     "llava_vqa": llava_vqa_satisfaction,
 }

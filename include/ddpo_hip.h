@@ -381,6 +381,21 @@ int ddpo_silu_fwd(const float* x, float* y, int64_t n, void* stream);
  * L2 normalisation of the image features (:80-82). */
 int ddpo_quick_gelu_fwd(const float* x, float* y, int64_t n, void* stream);
 int ddpo_l2_normalize_rows(const float* x, float* y, int rows, int cols, void* stream);
+/* CLIP text tower + CLIPScore reward (clip_score_fn; csrc/clip_text.hip; additive to ABI v14).
+ * ddpo_attention_causal_fwd: self-attention softmax(mask(q k^T * scale)) v with the mask key <= query, on fp32 MFMA (16x16x4).  Row layouts
+ *   and alignment rules of ddpo_attention_fwd: q, k, v, o are (B, N, .) with head h in columns [h*d, (h+1)*d), ld* = row strides (multiples of
+ *   4, >= heads*d), pointers 16-byte aligned.  One workgroup per (batch, head) holds all of K and V in LDS, so 1 <= N <= 80 (every CLIP text
+ *   tower has 77 positions) and d is 16 or 64; anything else returns DDPO_EINVAL and launches nothing.  Forward only: no lse output.
+ * ddpo_gather_rows: out[r, :] = table[idx[r], :] (+ add[r % add_period, :] when add != NULL), r < rows.  table has table_rows rows of row
+ *   stride ld; out (rows, cols) and add (add_period, cols) are contiguous; cols and ld are multiples of 4, pointers 16-byte aligned, idx int32.
+ *   An index outside [0, table_rows) is CLAMPED into the table: nothing outside it is ever read (callers validate indices on the host).
+ * ddpo_cosine_rows: out[r] = scale * <a_r, b_r> / (|a_r| |b_r|) for contiguous (rows, cols) a, b (cols a multiple of 4, 16-byte aligned):
+ *   one wave per row, fp32 accumulation in a fixed order (bit-reproducible, no atomics).  A zero row gives NaN. */
+int ddpo_attention_causal_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
+                              int B, int heads, int N, int d, float scale, void* stream);
+int ddpo_gather_rows(const float* table, int ld, int table_rows, const int32_t* idx, int rows, int cols, const float* add, int add_period,
+                     float* out, void* stream);
+int ddpo_cosine_rows(const float* a, const float* b, int rows, int cols, float scale, float* out, void* stream);
 int ddpo_timestep_embedding(const int32_t* ts, float* out, int B, int dim, void* stream); /* concat([cos, sin]) */
 int ddpo_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, void* stream);
 int ddpo_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, void* stream);
