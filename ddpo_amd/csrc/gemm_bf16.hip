@@ -112,6 +112,13 @@ __device__ __forceinline__ void store_planes4(const ddpo_gemm_desc& d, int64_t r
 //            (same lane reads and writes it: wave-private, in-order LDS access, no barrier).  No store is in flight in this phase, so its
 //            waits only ever cover loads.  Skipped when there is nothing to combine (alpha == 1, no bias / row bias / residual: q, k, v).
 //   emit:    LDS -> fp32 rows and / or planes; no loads, so no vmcnt wait: the stores of all iterations stream.
+// Folded nearest-2x up-sampler (ddpo_conv_up2x_folded_fwd): a launch computes phase (py, px) = (ph >> 1, ph & 1) of the up-sampled 3x3
+// convolution as a 2x2 convolution on the SOURCE grid; GEMM row m = source pixel (b, y, x) is output pixel (b, 2y + py, 2x + px), i.e. row
+// (b 2H + 2y + py) 2W + 2x + px = 2 m + 2 W (m / W) + 2 py W + px of the (4 M, ld_out) output (m / W = b H + y).
+__device__ __forceinline__ int64_t fold_row(const ddpo_gemm_desc& d, int row, int ph) {
+  return 2 * (int64_t)row + 2 * (int64_t)d.W * (row / d.W) + (ph >> 1) * 2 * d.W + (ph & 1);
+}
+
 constexpr int epi_gcd(int a, int b) { return b == 0 ? a : epi_gcd(b, a % b); }
 template <int NIT, int LPR, int WTN, int NBMAX = 10>
 struct EpiRows {
@@ -177,7 +184,8 @@ struct EpiRows {
     }
   }
   // LDS -> fp32 rows and / or planes
-  __device__ __forceinline__ static void emit(const ddpo_gemm_desc& d, const float* cw, int row_base, int col_base, int lane) {
+  template <bool FOLD = false>
+  __device__ __forceinline__ static void emit(const ddpo_gemm_desc& d, const float* cw, int row_base, int col_base, int lane, int ph = 0) {
 #pragma unroll
     for (int b0 = 0; b0 < NIT; b0 += LB) {
       asm volatile("" : "+v"(lane));
@@ -192,6 +200,7 @@ struct EpiRows {
         const int e = (b0 + i) * 64 + lane, rr = e / LPR;
         const int row = row_base + rr, col = col_base + (e - rr * LPR) * 4;
         if (row >= d.M || col >= d.N) continue;
+        if constexpr (FOLD) { st_out4(d.out + fold_row(d, row, ph) * d.ld_out + col, v[i]); continue; }      // (fp32 rows only: the host rejects planes)
         if (d.out) st_out4(d.out + (int64_t)row * d.ld_out + col, v[i]);
         if (d.out_hi) store_planes4(d, row, col, v[i]);
       }
@@ -514,9 +523,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
 // VGPRs, no v_cvt / v_sub split, no ds_write.  A wave instruction fills 16 rows x 64 B lane-linearly, so the XOR swizzle of
 // swz_off() is applied to the SOURCE chunk each lane fetches.  Same tiles, same k order, same three MFMA passes as the
 // register-staged path: results are bit-identical to it.
-template <int BM, int BN, int NPASS, int ABL = 0, int WM = 2, int WN = 2, bool DEEP = true, int APL = 0>     // ABL: timing ablations (tools/ablate_gemm.py; wrong results)
-__global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) gemm_conv_bf16_buf_kernel(const ddpo_gemm_desc d, const uint16_t* __restrict__ w_hi,
-                                                                       const uint16_t* __restrict__ w_lo, int ldw, int tiles_m,
+//
+// FOLD (plane-fed only): one phase of a folded nearest-2x up-sampler per blockIdx.z (fold_row above): four taps with offsets {-1, 0} (phase 0) /
+// {0, +1} (phase 1) per axis on the source grid, the phase's own weight planes (K * N elements apart) and E8M0 scales (N apart), rows stored
+// through fold_row.  A compile-time switch: the instantiations without it are the same code as before it existed.
+template <int BM, int BN, int NPASS, int ABL = 0, int WM = 2, int WN = 2, bool DEEP = true, int APL = 0, bool FOLD = false>     // ABL: timing ablations (tools/ablate_gemm.py; wrong results)
+__global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) gemm_conv_bf16_buf_kernel(const ddpo_gemm_desc d, const uint16_t* __restrict__ w_hi_,
+                                                                       const uint16_t* __restrict__ w_lo_, int ldw, int tiles_m,
                                                                        int tiles_n, int nblk, int kt_per_split,
                                                                        float* __restrict__ part) {
   constexpr int BK = BF_BK;
@@ -530,6 +543,10 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
   static_assert(BM % AR == 0 && WTM % 32 == 0 && WTN % 32 == 0, "tile / wave-grid mismatch");
   constexpr bool MX = NPASS == 4;                       // f16mx datapath (plane-fed only): f16 plane + 8-bit plane per operand
   static_assert(!MX || APL == 3 || APL == 7, "the f16mx datapath exists on the plane-fed 128-row tiles (APL 3) and on the tall tile (APL 7)");
+  static_assert(!FOLD || (APL != 0 && APL != 6), "folded up-sampler phases exist on the plane-fed kernels");
+  const int ph = FOLD ? (int)blockIdx.z : 0;                                   // phase (py, px) = (ph >> 1, ph & 1)
+  const uint16_t* __restrict__ w_hi = FOLD ? w_hi_ + (int64_t)ph * d.K * d.N : w_hi_;
+  const uint16_t* __restrict__ w_lo = (FOLD && w_lo_) ? w_lo_ + (int64_t)ph * d.K * d.N : w_lo_;
   constexpr int NPL = (NPASS == 3 || NPASS == 4) ? 2 : 1;          // NPASS = 5: single-pass f16 (plane-fed only; the f16mx planes' 16-bit plane alone)
   constexpr int A_BYTES = BM * 64, B_BYTES = BN * 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -554,8 +571,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
   const bool conv = d.ksize > 0;
-  const int VH = d.upsample ? d.H * 2 : d.H, VW = d.upsample ? d.W * 2 : d.W;
-  const bool zins = d.upsample == 2;
+  const int VH = (!FOLD && d.upsample) ? d.H * 2 : d.H, VW = (!FOLD && d.upsample) ? d.W * 2 : d.W;
+  const bool zins = !FOLD && d.upsample == 2;
   const int cin = conv ? d.Cin : d.K;            // reduction channels per tap (dense: one "tap" spanning K)
   const int ntaps = conv ? d.ksize * d.ksize : 1;
 
@@ -619,7 +636,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int n = n0 + wn * WTN + j * 32 + (lane & 31);
-      const int sc = n < d.N ? (int)d.w_scale[n] : 127;
+      const int sc = n < d.N ? (int)d.w_scale[(FOLD ? ph * d.N : 0) + n] : 127;
       mx_sbp[j >> 2] |= (khalf ? sc : sc - 11) << (8 * (j & 3));
     }
   }
@@ -683,8 +700,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         const int mm = valid ? m : 0;
         const int b = mm / ohw, rem = mm - b * ohw;
         const int oy = rem / d.OW, ox = rem - oy * d.OW;
-        aiy0[i] = valid ? oy * d.stride - d.pad : -(1 << 24);
-        aix0[i] = ox * d.stride - d.pad;
+        aiy0[i] = valid ? (FOLD ? oy - 1 + (ph >> 1) : oy * d.stride - d.pad) : -(1 << 24);
+        aix0[i] = FOLD ? ox - 1 + (ph & 1) : ox * d.stride - d.pad;
         apix[i] = b * d.H * d.W;
         avoff[i] = BUF_OOB;
       } else {
@@ -693,13 +710,13 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
       }
     }
     auto set_tap = [&](int tap) {
-      const int ky = d.ksize == 3 ? (tap * 11) >> 5 : 0;
-      const int kx = d.ksize == 3 ? tap - ky * 3 : 0;
+      const int ky = FOLD ? tap >> 1 : (d.ksize == 3 ? (tap * 11) >> 5 : 0);
+      const int kx = FOLD ? tap & 1 : (d.ksize == 3 ? tap - ky * 3 : 0);
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         const int iy = aiy0[i] + ky, ix = aix0[i] + kx;
         const bool ok = (unsigned)iy < (unsigned)VH && (unsigned)ix < (unsigned)VW && !(zins && ((iy | ix) & 1));
-        const int sy = d.upsample ? (iy >> 1) : iy, sx = d.upsample ? (ix >> 1) : ix;
+        const int sy = (!FOLD && d.upsample) ? (iy >> 1) : iy, sx = (!FOLD && d.upsample) ? (ix >> 1) : ix;
         const uint32_t off = (uint32_t)(apix[i] + sy * d.W + sx) * a_row_b + lc16;
         avoff[i] = ok ? off : BUF_OOB;
       }
@@ -1231,7 +1248,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
       static_assert((32 * LPR) % 64 == 0, "32-row pass must be a whole number of wave instructions");
       __syncthreads();
       float* cw = reinterpret_cast<float*>(smem) + wid * (32 * WTN);
-      float* pp = part ? part + (int64_t)blockIdx.y * d.M * d.N : nullptr;
+      float* pp = part ? part + ((int64_t)ph * gridDim.y + blockIdx.y) * d.M * d.N : nullptr;
       using Epi = EpiRows<NIT, LPR, WTN, 5>;
       Epi ep;
       const int colb = n0 + wn * WTN;
@@ -1304,7 +1321,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         } else {
           if (ih == 0) { ep.init(d, colb, lane); ep.fetch(d, 0, rowb, colb, lane); }
           ep.combine_all(d, cw, rowb, colb, lane);
-          Epi::emit(d, cw, rowb, colb, lane);
+          Epi::template emit<FOLD>(d, cw, rowb, colb, lane, ph);
         }
       };
       pass(std::integral_constant<int, 0>{});
@@ -1359,16 +1376,16 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
       return;
     }
     if (part) {
-      Epi::partials(d, cw, part + (int64_t)blockIdx.y * d.M * d.N, rowb, colb, lane);
+      Epi::partials(d, cw, part + ((int64_t)ph * gridDim.y + blockIdx.y) * d.M * d.N, rowb, colb, lane);
     } else {
       ep.combine_all(d, cw, rowb, colb, lane);
-      Epi::emit(d, cw, rowb, colb, lane);
+      Epi::template emit<FOLD>(d, cw, rowb, colb, lane, ph);
     }
     DBG_T(3);
     return;
   }
   if (part) {
-    float* pp = part + (int64_t)blockIdx.y * d.M * d.N;
+    float* pp = part + ((int64_t)ph * gridDim.y + blockIdx.y) * d.M * d.N;
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1399,7 +1416,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         float v = d.alpha * acc[i][j][r] + bv;
         if (d.rowbias) v += d.rowbias[(int64_t)(row / d.rows_per_batch) * d.ld_rowbias + col];
         if (d.residual) v += d.residual[(int64_t)row * d.ld_res + col];
-        d.out[(int64_t)row * d.ld_out + col] = v;
+        d.out[(FOLD ? fold_row(d, row, ph) : (int64_t)row) * d.ld_out + col] = v;
       }
     }
   }
@@ -1407,9 +1424,13 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
 }
 
 // fixed-order reduction of the split-K partials + the fused epilogue (bit-reproducible: no atomics)
+// (folded up-sampler, d.upsample == 3: blockIdx.y is the phase — its partials follow the previous phase's, its rows go through fold_row)
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ddpo_gemm_desc d, const float* __restrict__ part, int splits) {
   const int n4 = d.N >> 2;
   const int64_t total = (int64_t)d.M * n4, mn = (int64_t)d.M * d.N;
+  const bool fold = d.upsample == 3;
+  const int ph = blockIdx.y;
+  part += (int64_t)ph * splits * mn;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int row = (int)(i / n4), col = (int)(i - (int64_t)row * n4) << 2;
     float4 a = *reinterpret_cast<const float4*>(part + (int64_t)row * d.N + col);
@@ -1424,7 +1445,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ddpo_gemm_desc
       if (d.rowbias) x += d.rowbias[(int64_t)(row / d.rows_per_batch) * d.ld_rowbias + col + e];
       if (d.residual) x += d.residual[(int64_t)row * d.ld_res + col + e];
       v[e] = x;
-      if (d.out) d.out[(int64_t)row * d.ld_out + col + e] = x;
+      if (d.out) d.out[(fold ? fold_row(d, row, ph) : (int64_t)row) * d.ld_out + col + e] = x;
     }
     if (d.out_hi) store_planes4(d, row, col, make_float4(v[0], v[1], v[2], v[3]));
   }
@@ -1478,19 +1499,23 @@ static bool buf_path_ok(const ddpo_gemm_desc& d, int ldw) {
 extern "C" void ddpo_debug_force_generic_gemm(int on) { g_force_generic = on != 0; }
 #endif
 
-template <int BM, int BN, int NPASS, int WM = 2, int WN = 2, int APL = 0>
+// FOLD (all launchers below): the four phases of a folded up-sampler as blockIdx.z of the launch (ddpo_conv_up2x_folded_fwd) — the tile grid, and
+// with it every fill / split-K rule, counts NPH = 4 times the tiles of one phase; the partial sums of all phases must fit the scratch.
+template <int BM, int BN, int NPASS, int WM = 2, int WN = 2, int APL = 0, bool FOLD = false>
 static int launch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, float* ws, size_t ws_bytes,
                        hipStream_t st) {
+  constexpr int NPH = FOLD ? 4 : 1;
   const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
   const int nblk = tiles_m * tiles_n;
+  const int ngrid = nblk * NPH;
   // split-K when the tile grid under-fills the 256 CUs and the reduction is long (8x8 / 16x16 latent levels)
   const int nk_total = (d.K + BF_BK - 1) / BF_BK;
   int splits = 1;
-  if (ws && nblk < 192 && nk_total >= 32 && (d.N & 3) == 0 && d.epilogue == 0) {
-    splits = (384 + nblk - 1) / nblk;
+  if (ws && ngrid < 192 && nk_total >= 32 && (d.N & 3) == 0 && d.epilogue == 0) {
+    splits = (384 + ngrid - 1) / ngrid;
     if (splits > 8) splits = 8;
     if (splits > nk_total / 8) splits = nk_total / 8;
-    while (splits > 1 && (size_t)splits * d.M * d.N * sizeof(float) > ws_bytes) --splits;
+    while (splits > 1 && (size_t)NPH * splits * d.M * d.N * sizeof(float) > ws_bytes) --splits;
   }
   int ktps = (nk_total + splits - 1) / splits;
   ktps = (ktps + 1) & ~1;                                  // the pipelined loop consumes k-tiles in pairs
@@ -1507,14 +1532,14 @@ static int launch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_kernel<BM, BN, NPASS, false>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
   count_tile(BN == 128 ? TC_128 : TC_64);
   if constexpr (NPASS == 4) count_tile(TC_MX);
   if constexpr (APL != 0) {                // the plane-fed entry points have already checked buf_path_ok
-    hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL>), dim3(nblk, splits), dim3(64 * WM * WN), lds, st, d, w_hi,
+    hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>), dim3(nblk, splits, NPH), dim3(64 * WM * WN), lds, st, d, w_hi,
                        w_lo, ldw, tiles_m, tiles_n, nblk, ktps, part);
   } else {
     if (!buf_path_ok(d, ldw)) count_tile(TC_GENERIC);
@@ -1533,7 +1558,7 @@ static int launch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint
     int64_t blocks = ((int64_t)d.M * (d.N >> 2) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     count_tile(TC_SPLITK_REDUCE);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, st, d, part, splits);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks, NPH), dim3(256), 0, st, d, part, splits);
     DDPO_LAUNCH_CHECK();
   }
   return DDPO_OK;
@@ -1543,8 +1568,8 @@ static int launch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint
 // 128x320 tiles, 8 waves (4 x 2), one workgroup per CU: buffer-addressed kernel only (caller checked buf_path_ok).
 // Tile counts of the U-Net layers are multiples of the 256 CUs at the 64x64 and 32x32 levels; below that the reduction is
 // split so that ~256 workgroups exist.
-static int wide_splits(const ddpo_gemm_desc& d, bool have_ws, size_t ws_bytes) {
-  const int nblk = ((d.M + 127) / 128) * ((d.N + 319) / 320);
+static int wide_splits(const ddpo_gemm_desc& d, bool have_ws, size_t ws_bytes, int nph = 1) {
+  const int nblk = nph * ((d.M + 127) / 128) * ((d.N + 319) / 320);
   const int nk_total = d.K / BF_BK;
   int splits = 1;
   if (have_ws && nblk <= 192 && nk_total >= 16) {
@@ -1552,19 +1577,20 @@ static int wide_splits(const ddpo_gemm_desc& d, bool have_ws, size_t ws_bytes) {
     if (splits > 8) splits = 8;
     if (splits > nk_total / 8) splits = nk_total / 8;
     if (splits < 1) splits = 1;
-    while (splits > 1 && (size_t)splits * d.M * d.N * sizeof(float) > ws_bytes) --splits;
+    while (splits > 1 && (size_t)nph * splits * d.M * d.N * sizeof(float) > ws_bytes) --splits;
   }
   return splits;
 }
 
-template <int NPASS, int APL = 0>
+template <int NPASS, int APL = 0, bool FOLD = false>
 static int launch_bf16_wide(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, float* ws, size_t ws_bytes,
                             hipStream_t st) {
   constexpr int BM = 128, BN = 320, WM = 4, WN = 2;      // 8 waves of 32x160, two per SIMD
+  constexpr int NPH = FOLD ? 4 : 1;
   const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
   const int nblk = tiles_m * tiles_n;
   const int nk_total = d.K / BF_BK;
-  int splits = wide_splits(d, ws != nullptr, ws_bytes);
+  int splits = wide_splits(d, ws != nullptr, ws_bytes, NPH);
   int ktps = (nk_total + splits - 1) / splits;
   ktps = (ktps + 1) & ~1;
   splits = (nk_total + ktps - 1) / ktps;
@@ -1572,20 +1598,20 @@ static int launch_bf16_wide(const ddpo_gemm_desc& d, const uint16_t* w_hi, const
   const size_t lds = (size_t)BM * BN * 4;                  // epilogue image (160 KB) > 2 stages of operand tiles (112 KB)
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
   count_tile(TC_WIDE);
   if constexpr (NPASS == 4) count_tile(TC_MX);
-  hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL>), dim3(nblk, splits), dim3(64 * WM * WN), lds, st, d, w_hi,
+  hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>), dim3(nblk, splits, NPH), dim3(64 * WM * WN), lds, st, d, w_hi,
                      w_lo, ldw, tiles_m, tiles_n, nblk, ktps, part);
   DDPO_LAUNCH_CHECK();
   if (splits > 1) {
     int64_t blocks = ((int64_t)d.M * (d.N >> 2) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     count_tile(TC_SPLITK_REDUCE);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, st, d, part, splits);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks, NPH), dim3(256), 0, st, d, part, splits);
     DDPO_LAUNCH_CHECK();
   }
   return DDPO_OK;
@@ -1593,7 +1619,7 @@ static int launch_bf16_wide(const ddpo_gemm_desc& d, const uint16_t* w_hi, const
 
 // Tall 256x320 tiles (plane-fed path only, 8 waves of 64x160, one workgroup per CU, plain k-loop APL = 4): for layers whose tile
 // grid still covers the chip — the 64x64-latent level of the U-Net (M = 65536: 256 tiles per 320 columns).  No split-K.
-template <int APL, int NPASS = 3>
+template <int APL, int NPASS = 3, bool FOLD = false>
 static int launch_bf16_tall(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, hipStream_t st) {
   constexpr int BM = 256, BN = 320, WM = 4, WN = 2;
   const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
@@ -1602,18 +1628,19 @@ static int launch_bf16_tall(const ddpo_gemm_desc& d, const uint16_t* w_hi, const
   const size_t lds = 8 * 32 * 160 * 4;                     // epilogue slices (160 KB) > 2 stages of operand tiles (144 KB)
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
   count_tile(TC_TALL);
-  hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL>), dim3(nblk, 1), dim3(64 * WM * WN), lds, st, d, w_hi, w_lo, ldw,
+  hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>), dim3(nblk, 1, FOLD ? 4 : 1), dim3(64 * WM * WN), lds, st, d, w_hi, w_lo, ldw,
                      tiles_m, tiles_n, nblk, nk_total, (float*)nullptr);
   DDPO_LAUNCH_CHECK();
   return DDPO_OK;
 }
 
 // f16mx on the tall tile: eight waves of 64x160 (APL = 7), 144 KB of operand stages, no split-K (launched only where the grid fills the chip).
+template <bool FOLD = false>
 static int launch_mx_tall(const ddpo_gemm_desc& d, const uint16_t* w16, const uint16_t* w8, hipStream_t st) {
   constexpr int BM = 256, BN = 320, WM = 4, WN = 2;
   const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
@@ -1622,13 +1649,13 @@ static int launch_mx_tall(const ddpo_gemm_desc& d, const uint16_t* w16, const ui
   const size_t lds = 8 * 32 * 160 * 4;                      // the output stage's slices (160 KB) > two stages of [A16 | A8 | W16 | W8] (144 KB)
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, 4, 0, WM, WN, true, 7>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, 4, 0, WM, WN, true, 7, FOLD>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
   count_tile(TC_TALL);
   count_tile(TC_MX);
-  hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, 4, 0, WM, WN, true, 7>), dim3(nblk, 1), dim3(64 * WM * WN), lds, st, d, w16, w8, 0,
+  hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, 4, 0, WM, WN, true, 7, FOLD>), dim3(nblk, 1, FOLD ? 4 : 1), dim3(64 * WM * WN), lds, st, d, w16, w8, 0,
                      tiles_m, tiles_n, nblk, nk_total, (float*)nullptr);
   DDPO_LAUNCH_CHECK();
   return DDPO_OK;
@@ -1636,10 +1663,14 @@ static int launch_mx_tall(const ddpo_gemm_desc& d, const uint16_t* w16, const ui
 
 // Tile-shape / split-K selection shared by the fp32-fed and the plane-fed entry points: the SAME rules, so both produce
 // bit-identical results for the same layer (APL is only instantiated for npass == 3).
-template <int APL>
+// FOLD (APL = 3 only; npass 3 / 4 / 1): the same rules on the tile counts of all four phases of a folded up-sampler.
+template <int APL, bool FOLD = false>
 static int dispatch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, int npass, void* ws, size_t ws_bytes,
                          hipStream_t st) {
-  if (d.epilogue != 0) {       // GEGLU output stage: 128-wide tiles of the buffer-addressed kernel, vector epilogue only
+  static_assert(!FOLD || APL == 3, "folded up-sampler phases exist on the plane-fed kernels");
+  constexpr int NPH = FOLD ? 4 : 1;
+  if constexpr (FOLD) { if (d.epilogue != 0 || (npass != 1 && npass != 3 && npass != 4)) return DDPO_EINVAL; }
+  if constexpr (!FOLD) if (d.epilogue != 0) {       // GEGLU output stage: 128-wide tiles of the buffer-addressed kernel, vector epilogue only
     if ((d.epilogue != 1 && d.epilogue != 2) || (d.N & 127) || !buf_path_ok(d, ldw) || d.rowbias || d.residual || d.alpha != 1.0f || d.w_dgrad) return DDPO_EINVAL;
     if ((d.ld_out & 3) || (reinterpret_cast<uintptr_t>(d.out) & 15) || (d.bias && (reinterpret_cast<uintptr_t>(d.bias) & 15))) return DDPO_EINVAL;
     if (reinterpret_cast<uintptr_t>(d.aux_out) & 15) return DDPO_EINVAL;
@@ -1667,7 +1698,7 @@ static int dispatch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const ui
     constexpr int tall_mode = 1;
     // ... and where their last round of 256 is not much emptier than the 128x320 grid's: 256 tall tiles (SD-1.5, 64x64 latents at batch 16)
     // are exactly one round; 576 (SD-2.1, 96x96) are 2.25 rounds = 3 rounds of time, where 1152 wide tiles waste half a round of five
-    const long ntall = (long)((d.M + 255) / 256) * (d.N / 320), nwide = (long)((d.M + 127) / 128) * (d.N / 320);
+    const long ntall = (long)NPH * ((d.M + 255) / 256) * (d.N / 320), nwide = (long)NPH * ((d.M + 127) / 128) * (d.N / 320);
     const double eff_tall = (double)ntall / (double)(((ntall + 255) / 256) * 256), eff_wide = (double)nwide / (double)(((nwide + 255) / 256) * 256);
     // (bf16x3 only.  An f16mx tall loop — the weight operand's ks = 1 fragments streamed per column block beside the 160 accumulators — was
     // built twice in round 3: correct, but ~20 registers short at two waves per SIMD.  The compiler spills 44-58 values around the 8-register
@@ -1676,13 +1707,14 @@ static int dispatch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const ui
     // vmcnt counter, so every k-tile waits for its own prefetch: 0.326 ms against 0.321 (bf16x3 tall) / 0.317 (f16mx 128x320) on conv 320->320
     // @64^2, profiles/r03_probe_mx_tall.log.  The f16mx tall tile wants FOUR waves of 128 x 160 (one per SIMD, accumulators in AGPRs).)
     if (tall_mode && npass == 3 && d.N % 320 == 0 && d.epilogue == 0 && ntall >= 200 && eff_tall * 1.08 >= eff_wide)
-      return launch_bf16_tall<5>(d, w_hi, w_lo, ldw, st);
+      return launch_bf16_tall<5, 3, FOLD>(d, w_hi, w_lo, ldw, st);
     if constexpr (APL == 3) {
       // single-pass bf16, plane-fed (round 6): the tall tile with the four-stage ring (APL = 8) under the same rule
       if (npass == 1 && d.N % 320 == 0 && d.epilogue == 0 && ntall >= 200 && eff_tall * 1.08 >= eff_wide)
-        return launch_bf16_tall<8, 1>(d, w_hi, w_lo, ldw, st);
-      if (npass == 5 && d.N % 320 == 0 && d.epilogue == 0 && ntall >= 200 && eff_tall * 1.08 >= eff_wide)
-        return launch_bf16_tall<8, 5>(d, w_hi, w_lo, ldw, st);
+        return launch_bf16_tall<8, 1, FOLD>(d, w_hi, w_lo, ldw, st);
+      if constexpr (!FOLD)
+        if (npass == 5 && d.N % 320 == 0 && d.epilogue == 0 && ntall >= 200 && eff_tall * 1.08 >= eff_wide)
+          return launch_bf16_tall<8, 5>(d, w_hi, w_lo, ldw, st);
       // f16mx layers on the tall tile (APL = 7) under the bf16x3 tall tile's rule: grids that fill whole rounds of the chip unsplit — the 64x64
       // level at batch 16 and the up-sampled 32x32 -> 64x64 convolution.  Measured round 5 (profiles/r05_probe_mx_tall.log, r05_ab_mx_tall.log):
       // conv 320->320 @64^2 0.259 -> 0.236 ms, 960->320 0.930 -> 0.709 ms, up-conv 640->640 1.084 -> 0.878 ms, bit-identical; sampling +1.4 %.
@@ -1691,21 +1723,22 @@ static int dispatch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const ui
       // the probe's and the tests' bit-identity comparison.
       const char* mx_tall_env = getenv("DDPO_MX_TALL");
       if (npass == 4 && !(mx_tall_env && mx_tall_env[0] == '0') && d.N % 320 == 0 && d.epilogue == 0 && ntall >= 200 && eff_tall * 1.08 >= eff_wide)
-        return launch_mx_tall(d, w_hi, w_lo, st);
+        return launch_mx_tall<FOLD>(d, w_hi, w_lo, st);
     }
   }
-  const int wsplits = wide_splits(d, wsf != nullptr, ws_bytes);
-  if (wide_mode && d.N % 320 == 0 && d.M >= 512 && buf_path_ok(d, ldw) && !(d.K / BF_BK < 16 && d.N > 1280) &&
-      (long)((d.M + 127) / 128) * (d.N / 320) * wsplits >= 200 &&
+  const int wsplits = wide_splits(d, wsf != nullptr, ws_bytes, NPH);
+  if (wide_mode && d.N % 320 == 0 && (long)NPH * d.M >= 512 && buf_path_ok(d, ldw) && !(d.K / BF_BK < 16 && d.N > 1280) &&
+      (long)NPH * ((d.M + 127) / 128) * (d.N / 320) * wsplits >= 200 &&
       !(wsplits > 1 && d.K / BF_BK < 64)) {     // a split short reduction only adds the reduce pass (measured equal to 128x128 unsplit)
     if constexpr (APL == 3) {
-      if (npass == 4) return launch_bf16_wide<4, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-      if (npass == 1) return launch_bf16_wide<1, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-      if (npass == 5) return launch_bf16_wide<5, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+      if (npass == 4) return launch_bf16_wide<4, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+      if (npass == 1) return launch_bf16_wide<1, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+      if constexpr (!FOLD) if (npass == 5) return launch_bf16_wide<5, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
     }
-    return npass == 3 ? launch_bf16_wide<3, APL>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16_wide<1>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+    if constexpr (FOLD) return launch_bf16_wide<3, APL, true>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+    else return npass == 3 ? launch_bf16_wide<3, APL>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16_wide<1>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
   }
-  const long t128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
+  const long t128 = (long)NPH * ((d.M + 127) / 128) * ((d.N + 127) / 128);
   constexpr long big_min = 256;
   // 128x128 tiles need >= 512 of them to fill both workgroup slots of every CU; a short reduction on 256..511 of them (the 16x16
   // level's q / k / v / out projections: M = 4096, N = K = 1280 -> 320 tiles) runs ~15 % faster on 640 tiles of 128x64, three per CU
@@ -1715,15 +1748,20 @@ static int dispatch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const ui
   const bool big = (d.N % 128 == 0) && t128 >= big_min && !mid_short;
   if constexpr (APL == 3) {
     if (npass == 4)
-      return big ? launch_bf16<128, 128, 4, 2, 2, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 4, 2, 2, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+      return big ? launch_bf16<128, 128, 4, 2, 2, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 4, 2, 2, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
     if (npass == 1)
-      return big ? launch_bf16<128, 128, 1, 2, 2, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 1, 2, 2, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-    if (npass == 5)
-      return big ? launch_bf16<128, 128, 5, 2, 2, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 5, 2, 2, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+      return big ? launch_bf16<128, 128, 1, 2, 2, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 1, 2, 2, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+    if constexpr (!FOLD)
+      if (npass == 5)
+        return big ? launch_bf16<128, 128, 5, 2, 2, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 5, 2, 2, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
   }
-  if (npass == 3)
-    return big ? launch_bf16<128, 128, 3, 2, 2, APL>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 3, 2, 2, APL>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-  return big ? launch_bf16<128, 128, 1>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 1>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+  if constexpr (FOLD) {
+    return big ? launch_bf16<128, 128, 3, 2, 2, APL, true>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 3, 2, 2, APL, true>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+  } else {
+    if (npass == 3)
+      return big ? launch_bf16<128, 128, 3, 2, 2, APL>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 3, 2, 2, APL>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+    return big ? launch_bf16<128, 128, 1>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 1>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+  }
 }
 
 extern "C" int ddpo_gemm_conv_fwd_bf16(const ddpo_gemm_desc* dp, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, int npass,
@@ -1810,6 +1848,81 @@ extern "C" int ddpo_gemm_conv_fwd_f16mx_planes(const ddpo_gemm_desc* dp, const u
   { const char* e = getenv("DDPO_DBG_ABL"); if (e) d.splits |= atoi(e) << 4; }
 #endif
   return dispatch_bf16<3>(d, w16, w8, 0, npass, ws, ws_bytes, as_stream(stream));
+}
+
+// ------------------------------------------------------------------------------------------------
+// Folded nearest-2x up-sampler (FlaxUpsample2D: repeat every pixel 2x2, then a 3x3 convolution).  The four output pixels (2y + py, 2x + px) of
+// source pixel (y, x) read a 2x2 neighbourhood of the SOURCE image only, because neighbouring taps of the 3x3 kernel land on the same source
+// pixel: per axis, phase 0 reads offsets {-1, 0} with taps {w[0], w[1] + w[2]}, phase 1 offsets {0, +1} with taps {w[0] + w[1], w[2]} (the zero
+// padding of the virtual image at rows -1 / 2H coincides with source rows -1 / H).  So the layer is four stride-1 2x2 convolutions on the source
+// grid with pre-summed kernels — reduction length 4 Cin instead of 9 Cin — each writing one quarter of the output rows (fold_row).  All four
+// phases run as blockIdx.z of ONE launch of the FOLD instantiation of the plane-fed kernel, chosen by dispatch_bf16<3, true>: the tile and
+// split-K rules of every other layer, applied to a tile grid four times the source grid's.
+// ------------------------------------------------------------------------------------------------
+extern "C" int ddpo_conv_up2x_folded_fwd(const ddpo_gemm_desc* dp, const uint16_t* a_hi, const uint16_t* a_lo, int lda, const uint16_t* w_hi,
+                                         const uint16_t* w_lo, int f16mx, void* ws, size_t ws_bytes, void* stream) {
+  if (!dp || !a_hi || !w_hi || (a_lo == nullptr) != (w_lo == nullptr)) return DDPO_EINVAL;
+  if (f16mx && (!a_lo || !dp->w_scale)) return DDPO_EINVAL;
+  const int npass = f16mx ? 4 : (a_lo ? 3 : 1);
+  ddpo_gemm_desc d = *dp;
+  if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.Cin <= 0 || d.N <= 0 || (d.Cin % BF_BK) || (d.N & 3)) return DDPO_EINVAL;
+  if ((int64_t)d.B * d.H * d.W * 4 > 0x7FFFFFFF || (int64_t)d.Cin * 4 > 0x7FFFFFFF) return DDPO_EINVAL;      // output rows and K are 32-bit
+  if (lda < 0 || (lda & (f16mx ? 31 : 7)) || (lda && lda < d.Cin)) return DDPO_EINVAL;
+  if (!d.out || d.out_hi || d.out_lo || d.rowbias || d.residual || d.epilogue || d.w_dgrad || d.aux_out) return DDPO_EINVAL;
+  if (d.ld_out < d.N || (d.ld_out & 3) || (reinterpret_cast<uintptr_t>(d.out) & 15) || (d.bias && (reinterpret_cast<uintptr_t>(d.bias) & 15))) return DDPO_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(a_hi) | reinterpret_cast<uintptr_t>(a_lo) | reinterpret_cast<uintptr_t>(w_hi) | reinterpret_cast<uintptr_t>(w_lo)) & 15)
+    return DDPO_EINVAL;
+  // the geometry of ONE phase, as the kernel reads it: a 2x2 stride-1 convolution on the source grid
+  d.M = d.B * d.H * d.W; d.K = 4 * d.Cin;             // (both checked above to fit)
+  d.alpha = 1.0f;                                     // the layer has no scale: whatever the caller left in the field is not applied
+  d.OH = d.H; d.OW = d.W;
+  d.ksize = 2; d.stride = 1; d.pad = 1; d.upsample = 3;
+  d.w_layout = 1; d.planes_fmt = 0; d.ld_planes = 0;
+  d.src = reinterpret_cast<const float*>(a_hi);
+  d.w = reinterpret_cast<const float*>(a_lo);
+  d.ld_src = lda;
+  if (!f16mx) d.w_scale = nullptr;
+  if (!buf_path_ok(d, 0) || (int64_t)4 * d.K * d.N * 2 >= 0x7FFFFFFF) return DDPO_EINVAL;
+  d.splits = 1;                                      // (the stagger flag of the plane-fed k-loops, as in ddpo_gemm_conv_fwd_bf16_planes)
+  return dispatch_bf16<3, true>(d, w_hi, w_lo, 0, npass, ws, ws_bytes, as_stream(stream));
+}
+
+// The four phase kernels (2, 2, Cin, Cout) of a 3x3 HWIO kernel w (3, 3, Cin, Cout): wf[(py 2 + px)][ty][tx] = the sum, in fp32, ky then kx
+// ascending, of w[ky][kx] over the taps that land on source offset (ty - 1 + py, tx - 1 + px).  cn = Cin * Cout.
+__global__ void __launch_bounds__(256) fold_up2x_weights_kernel(const float* __restrict__ w, int64_t cn, float* __restrict__ wf) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= cn) return;
+  float v[3][3];
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) v[ky][kx] = w[(ky * 3 + kx) * cn + i];
+#pragma unroll
+  for (int ph = 0; ph < 4; ++ph)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int py = ph >> 1, px = ph & 1, ty = t >> 1, tx = t & 1;
+      const int y0 = py ? (ty ? 2 : 0) : (ty ? 1 : 0), y1 = py ? (ty ? 2 : 1) : (ty ? 2 : 0);
+      const int x0 = px ? (tx ? 2 : 0) : (tx ? 1 : 0), x1 = px ? (tx ? 2 : 1) : (tx ? 2 : 0);
+      float sum = 0.f;
+      bool first = true;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          if (ky < y0 || ky > y1 || kx < x0 || kx > x1) continue;
+          sum = first ? v[ky][kx] : sum + v[ky][kx];
+          first = false;
+        }
+      wf[(ph * 4 + t) * cn + i] = sum;
+    }
+}
+extern "C" int ddpo_fold_up2x_weights(const float* w, int Cin, int Cout, float* wf, void* stream) {
+  if (!w || !wf || Cin <= 0 || Cout <= 0) return DDPO_EINVAL;
+  const int64_t cn = (int64_t)Cin * Cout;
+  hipLaunchKernelGGL(fold_up2x_weights_kernel, dim3((unsigned)((cn + 255) / 256)), dim3(256), 0, as_stream(stream), w, cn, wf);
+  DDPO_LAUNCH_CHECK();
+  return DDPO_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -88,6 +88,9 @@ _SIGS = {
     "ddpo_pack_weights_f16mx": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ddpo_split_planes_f16mx": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "ddpo_gemm_conv_fwd_f16mx_planes": (c_int, [POINTER(GemmDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # folded nearest-2x up-sampler (additive to ABI v14)
+    "ddpo_fold_up2x_weights": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ddpo_conv_up2x_folded_fwd": (c_int, [POINTER(GemmDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "ddpo_attention_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                    c_int, c_int, c_int, c_float, c_void_p]),
     "ddpo_attention_kv_images_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
@@ -746,6 +749,8 @@ def pack_weights(w, bwd=True):
         ent["bwd"] = (mk(K, N), mk(K, N))
     if "geglu" in ent:
         ent["geglu"]["stale"] = True          # re-ordered GEGLU planes (pack_weights_geglu) no longer match w
+    if "fold" in ent:
+        ent["fold"]["stale"] = True           # folded up-sampler planes (pack_weights_up2x_folded) no longer match w
     fh, fl, _ = ent["fwd"]
     bh, bl = ent["bwd"] if ent["bwd"] is not None else (None, None)
     if _mx() and K % 32 == 0 and K >= MX_MIN_K:            # f16mx forward planes next to the bf16 ones (mx_layer(); the backward uses the bf16 ones)
@@ -763,6 +768,163 @@ def pack_weights(w, bwd=True):
     else:
         _check(load().ddpo_pack_weights_bf16(_p(w), K, N, Kp, _p(fh), _p(fl), _p(bh), _p(bl), _stream()), "ddpo_pack_weights_bf16")
     return ent
+
+
+# Nearest-2x up-sampler convolutions (FlaxUpsample2D) as four 2x2 convolutions on the source grid (include/ddpo_hip.h: ddpo_conv_up2x_folded_fwd;
+# the algebra is fold_up2x_kernel_reference below): 4/9 of the matrix work of the up-sampled 3x3 form.  DDPO_UP2X_FOLD=0 keeps the gather form
+# (conv2d(..., upsample=True)), which also stays the fp32 datapath's and the backward's form.
+UP2X_FOLD = os.environ.get("DDPO_UP2X_FOLD", "1") == "1"
+
+
+def fold_up2x_kernel_reference(w):
+    """The four phase kernels of a nearest-2x up-sampler's 3x3 HWIO kernel w (3, 3, Cin, Cout) -> (4, 2, 2, Cin, Cout), phase py * 2 + px,
+    in w's dtype (float64 in: the exact statement; float32 in: the bits of ddpo_fold_up2x_weights — sums taken ky then kx ascending).
+
+    Output pixel (2y + py, 2x + px) of conv3x3(nearest_upsample_2x(x)) reads virtual rows 2y + py - 1 .. 2y + py + 1, i.e. source rows
+    (y - 1, y, y) for py = 0 and (y, y, y + 1) for py = 1: a 2-tap kernel at source offsets {-1, 0} with taps {w[0], w[1] + w[2]} (py = 0) or
+    offsets {0, +1} with taps {w[0] + w[1], w[2]} (py = 1); the same in x.  The zero padding of the virtual image (rows -1 and 2H) coincides
+    with source rows -1 and H, so borders need no special case."""
+    groups = (((0,), (1, 2)), ((0, 1), (2,)))          # [phase][tap] -> 3x3 indices summed into it
+    out = w.new_zeros((4, 2, 2) + tuple(w.shape[2:]))
+    for py in range(2):
+        for px in range(2):
+            for ty in range(2):
+                for tx in range(2):
+                    acc = None
+                    for ky in groups[py][ty]:
+                        for kx in groups[px][tx]:
+                            acc = w[ky, kx].clone() if acc is None else acc + w[ky, kx]
+                    out[py * 2 + px, ty, tx] = acc
+    return out
+
+
+def conv_up2x_folded_reference(x, w):
+    """x (B, H, W, Cin), w (3, 3, Cin, Cout) -> (B, 2H, 2W, Cout): the folded form on the host, in x's dtype (documents the kernel's geometry)."""
+    B, H, W, _ = x.shape
+    wf = fold_up2x_kernel_reference(w)
+    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))          # source rows / columns -1 and H / W are zeros
+    out = x.new_zeros(B, 2 * H, 2 * W, w.shape[3])
+    for py in range(2):
+        for px in range(2):
+            acc = 0
+            for ty in range(2):
+                for tx in range(2):
+                    oy, ox = ty - 1 + py, tx - 1 + px            # source offset of this tap
+                    acc = acc + xp[:, 1 + oy:1 + oy + H, 1 + ox:1 + ox + W] @ wf[py * 2 + px, ty, tx]
+            out[:, py::2, px::2] = acc
+    return out
+
+
+def pack_weights_up2x_folded(w):
+    """Register the folded phase planes of an up-sampler kernel w (3, 3, Cin, Cout) next to its pack_weights() planes (call after it, and
+    after every change of w — pack_weights marks the folded planes stale, and a stale layer runs the gather form): PACKED[w]["fold"] = dict(K = 4 Cin, N, hi, lo (4, K / 32, N, 32) and, on the f16mx datapath for K >= MX_MIN_K,
+    mx = dict(w16, w8, scale)).  Derived data (never saved).  Cin % 32 == 0 and N % 4 == 0 are needed; other layers keep the gather form."""
+    ent = PACKED.get(w.data_ptr())
+    if ent is None:
+        raise DdpoHipError("pack_weights_up2x_folded: pack_weights(w) first")
+    C, N = int(w.shape[2]), int(w.shape[3])
+    if not (UP2X_FOLD and w.dim() == 4 and w.shape[0] == 3 and w.shape[1] == 3 and C % 32 == 0 and N % 4 == 0 and W_KBLOCKED):
+        ent.pop("fold", None)
+        return None
+    K, Kb = 4 * C, 4 * C // 32
+    fo = ent.get("fold")
+    if fo is None or fo["K"] != K or fo["N"] != N:
+        mk = lambda: torch.zeros(4, Kb, N, 32, dtype=torch.int16, device=w.device)
+        fo = ent["fold"] = dict(K=K, N=N, hi=mk(), lo=mk())
+    wf = torch.empty(4, K, N, dtype=torch.float32, device=w.device)       # the folded fp32 kernels: only live until they are packed
+    _check(load().ddpo_fold_up2x_weights(_p(w), C, N, _p(wf), _stream()), "ddpo_fold_up2x_weights")
+    mx = _mx() and K >= MX_MIN_K
+    if mx and "mx" not in fo:
+        fo["mx"] = dict(w16=torch.zeros(4, Kb, N, 32, dtype=torch.int16, device=w.device), w8=torch.zeros(4, Kb, N, 64, dtype=torch.uint8, device=w.device),
+                        scale=torch.zeros(4, N, dtype=torch.uint8, device=w.device))
+    if not mx:
+        fo.pop("mx", None)
+    for ph in range(4):
+        _check(load().ddpo_pack_weights_bf16_kblocked(_p(wf[ph]), K, N, _p(fo["hi"][ph]), _p(fo["lo"][ph]), _stream()), "ddpo_pack_weights_bf16_kblocked")
+        if mx:
+            m = fo["mx"]
+            _check(load().ddpo_pack_weights_f16mx(_p(wf[ph]), K, N, _p(m["w16"][ph]), _p(m["w8"][ph]), _p(m["scale"][ph]), _stream()), "ddpo_pack_weights_f16mx")
+    fo["stale"] = False
+    return fo
+
+
+def up2x_fold_ok(w, cin, rows):
+    """True when the up-sampler convolution with kernel `w` (`rows` SOURCE pixels of `cin` channels) runs folded: a bf16 / f16mx datapath,
+    folded planes registered (pack_weights_up2x_folded), the buffer-addressed kernels' 31-bit offsets.  False under DDPO_MX_CROSS=0 (that
+    experiment's single-pass f16 kernels have no folded form): those layers keep the gather form, like the fp32 datapath."""
+    # (not a function of PLANES / BF16_PLANES: those say how activations TRAVEL, and a layer's arithmetic must not depend on that — with them
+    # off the producers write fp32 and the layer splits it on the way in)
+    if not UP2X_FOLD or current_datapath() == "fp32" or cin % 32 or (_mx() and not MX_CROSS):
+        return False
+    ent = PACKED.get(w.data_ptr())
+    if ent is None or "fold" not in ent:
+        return False
+    fo = ent["fold"]
+    if fo.get("stale", True):                 # pack_weights(w) ran since: the planes are those of the OLD weights
+        return False
+    if _mx() and fo["K"] >= MX_MIN_K and "mx" not in fo:      # packed under another datapath: no f16mx planes for an f16mx layer
+        return False
+    lim = 0x7FFFFFFF
+    return rows * cin * 4 < lim and 4 * fo["N"] * fo["K"] * 2 < lim and rows * 4 < lim
+
+
+def up2x_planes_pay(w, cin, rows):
+    """planes_pay() for an up-sampler convolution: a folded layer is always plane-fed, f16mx (2) when its FOLDED reduction 4 * cin reaches
+    MX_MIN_K, else bf16 hi / lo (1; the single-pass datapath reads the hi plane); the gather form answers as planes_pay."""
+    if not up2x_fold_ok(w, cin, rows):
+        return planes_pay(w, cin, rows)
+    if not (PLANES and _planes_dp()):          # producers write fp32; the folded layer splits it on the way in
+        return 0
+    return 2 if (_mx() and "mx" in PACKED[w.data_ptr()]["fold"]) else 1
+
+
+def conv2d_up2x_folded(x, w, bias, B, H, W, Cin, Cout, out=None, ld_out=None):
+    """Nearest-2x up-sampling + 3x3 convolution in the folded form (check up2x_fold_ok first).  x: fp32 (B*H*W, Cin) rows (tensor or
+    row-strided view; split into the layer's plane format on the way in — the same bits a plane-emitting producer writes) or Planes of the
+    format up2x_planes_pay names.  Returns ((B*2H*2W, Cout), 2H, 2W); `out` / `ld_out` as in gemm_conv."""
+    rows = B * H * W
+    if not up2x_fold_ok(w, Cin, rows):
+        raise DdpoHipError("conv2d_up2x_folded: no folded planes for this layer / datapath (check up2x_fold_ok)")
+    fo = PACKED[w.data_ptr()]["fold"]
+    if fo["K"] != 4 * Cin or fo["N"] != Cout:
+        raise DdpoHipError("conv2d_up2x_folded: geometry does not match the registered kernel")
+    mxl = _mx() and "mx" in fo
+    if isinstance(x, Planes):
+        pl = x
+        if pl.fmt != int(mxl) or pl.rows != rows or pl.C != Cin:
+            raise DdpoHipError("activation planes of the wrong format / shape for this layer (ask up2x_planes_pay)")
+    else:
+        if not (x.dim() == 2 and x.shape[0] == rows and x.shape[1] == Cin and x.stride(1) == 1):
+            raise DdpoHipError("conv2d_up2x_folded needs its fp32 input as a (rows, channels) tensor or row-strided view")
+        pl = split_planes(x, fmt=1 if mxl else 0)
+    M = 4 * rows
+    if out is None:
+        out = torch.empty(M, Cout, dtype=torch.float32, device=pl.device)
+    d = GemmDesc()
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.out = out.data_ptr(); d.ld_out = int(ld_out if ld_out is not None else Cout)
+    d.alpha = 1.0
+    d.N = int(Cout)
+    d.B, d.H, d.W, d.Cin = int(B), int(H), int(W), int(Cin)
+    if PROFILE is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    ws = _scratch(SPLITK_WS_BYTES, pl.device, "splitk")
+    one = not _x3()
+    if mxl:
+        m = fo["mx"]
+        d.w_scale = m["scale"].data_ptr()
+        wh, wl = m["w16"], m["w8"]
+    else:
+        wh, wl = fo["hi"], (None if one else fo["lo"])
+    _check(load().ddpo_conv_up2x_folded_fwd(byref(d), _p(pl.hi), None if (one and not mxl) else _p(pl.lo), pl.ld, _p(wh), None if wl is None else _p(wl),
+                                            int(mxl), _p(ws), SPLITK_WS_BYTES, _stream()), "ddpo_conv_up2x_folded_fwd")
+    if PROFILE is not None:
+        e1.record()
+        K = 4 * Cin                          # the FLOPs actually executed: 2 * M * 4 Cin * N
+        io_bytes = 4.0 * rows * Cin + (4.0 if _x3() else 2.0) * 4 * K * Cout + 4.0 * M * Cout
+        PROFILE.append((e0, e1, 2.0 * M * Cout * K, "f16mx" if mxl else ("bf16x3" if _x3() else current_datapath()), io_bytes))
+    return out, 2 * H, 2 * W
 
 
 def _pack_dgrad_planes(w, ent):

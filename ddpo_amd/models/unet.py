@@ -94,6 +94,8 @@ class ParamStore:
                 if n not in sel or not n.endswith(".kernel"):
                     continue
                 L.pack_weights(v, bwd=bwd)
+                if n.endswith(".upsamplers_0.conv.kernel"):
+                    L.pack_weights_up2x_folded(v)
                 if n.endswith(".ff.net_0.proj.kernel"):
                     L.pack_weights_geglu(v, self.views[n[:-len("kernel")] + "bias"])
                 m = re.search(r"\.attn1\.to_[qkv]\.kernel$", n)
@@ -105,6 +107,8 @@ class ParamStore:
         for n, v in self.views.items():
             if n.endswith(".kernel"):
                 L.pack_weights(v, bwd=bwd)
+                if n.endswith(".upsamplers_0.conv.kernel"):      # nearest-2x up-sampler: the folded phase planes (U-Net and VAE decoder)
+                    L.pack_weights_up2x_folded(v)
                 if n.endswith(".ff.net_0.proj.kernel"):          # GEGLU feed-forward: extra planes for the fused forward
                     L.pack_weights_geglu(v, self.views[n[:-len("kernel")] + "bias"])
                 if QKV_FUSED and n.endswith(".attn1.to_q.kernel"):
@@ -696,7 +700,7 @@ class UNet2DCondition:
                 emit = 0
                 last_of_level = j == cfg.layers_per_block
                 if tape is None and i < nlev - 1 and last_of_level:      # feeds the up-sampler convolution: its planes_pay value
-                    emit = L.planes_pay(P[f"up_blocks_{i}.upsamplers_0.conv.kernel"], boc[lvl], B * h.HW)
+                    emit = L.up2x_planes_pay(P[f"up_blocks_{i}.upsamplers_0.conv.kernel"], boc[lvl], B * h.HW)
                 # where this block's output goes: the next up block's concat buffer — unless an up-sampler convolution (or conv_norm_out) reads it
                 nxt = None if last_of_level else up_dest(kblk)
                 h = resnet_forward(P, f"up_blocks_{i}.resnets_{j}", Act(cat, B, h.H, h.W, h.C + s.C), temb_act, G, 1e-5, tape,
@@ -705,10 +709,13 @@ class UNet2DCondition:
                     h = self._transformer(f"up_blocks_{i}.attentions_{j}", h, ctx, Lc, cfg.num_heads[lvl], tape, emit_planes=emit, dest=nxt)
             if i < nlev - 1:
                 name = f"up_blocks_{i}.upsamplers_0.conv"
-                src = h.pl if (h.pl is not None and L.planes_pay(P[name + ".kernel"], h.C, h.M) == h.pl.fmt + 1) else h.t
+                src = h.pl if (h.pl is not None and L.up2x_planes_pay(P[name + ".kernel"], h.C, h.M) == h.pl.fmt + 1) else h.t
                 dd = up_dest(kblk)
-                t, OH, OW = L.conv2d(src, P[name + ".kernel"], P[name + ".bias"], B, h.H, h.W, h.C, h.C, 3, upsample=True,
-                                     **({} if dd is None else dict(out=dd, ld_out=int(dd.stride(0)))))
+                dkw = {} if dd is None else dict(out=dd, ld_out=int(dd.stride(0)))
+                if L.up2x_fold_ok(P[name + ".kernel"], h.C, h.M):       # four 2x2 convolutions on the source grid (sampler and taped forward alike)
+                    t, OH, OW = L.conv2d_up2x_folded(src, P[name + ".kernel"], P[name + ".bias"], B, h.H, h.W, h.C, h.C, **dkw)
+                else:
+                    t, OH, OW = L.conv2d(src, P[name + ".kernel"], P[name + ".bias"], B, h.H, h.W, h.C, h.C, 3, upsample=True, **dkw)
                 if tape is not None:
                     tape.append(("up", dict(name=name, x=h)))
                 h = Act(t, B, OH, OW, h.C)

@@ -118,8 +118,11 @@ class VAEDecoder:
             for j in range(cfg.layers_per_block + 1):
                 h = resnet_forward(P, f"decoder.up_blocks_{i}.resnets_{j}", h, None, G, 1e-6)
             if i < n - 1:
-                t, OH, OW = L.conv2d(h.t, P[f"decoder.up_blocks_{i}.upsamplers_0.conv.kernel"],
-                                     P[f"decoder.up_blocks_{i}.upsamplers_0.conv.bias"], B, h.H, h.W, h.C, h.C, 3, upsample=True)
+                uk, ub = P[f"decoder.up_blocks_{i}.upsamplers_0.conv.kernel"], P[f"decoder.up_blocks_{i}.upsamplers_0.conv.bias"]
+                if L.up2x_fold_ok(uk, h.C, h.M):
+                    t, OH, OW = L.conv2d_up2x_folded(h.t, uk, ub, B, h.H, h.W, h.C, h.C)
+                else:
+                    t, OH, OW = L.conv2d(h.t, uk, ub, B, h.H, h.W, h.C, h.C, 3, upsample=True)
                 h = Act(t, B, OH, OW, h.C)
         t = L.groupnorm(h.t, B, h.HW, P["decoder.conv_norm_out.scale"], P["decoder.conv_norm_out.bias"], G, 1e-6, True)
         kp, bp, n4 = self._padded_conv_out()

@@ -155,7 +155,8 @@ int ddpo_layernorm_bwd(const float* x, const float* dy, const float* gamma, int 
 /* Implicit-GEMM convolution / dense GEMM on the exact-fp32 MFMA datapath (v_mfma_f32_32x32x2_f32).
  *   out[m][n] = alpha * sum_k A(m,k) * W[k][n] (+ bias[n]) (+ rowbias[m / rows_per_batch][n]) (+ residual[m][n])
  * conv mode: m = (b, oy, ox), k = (ky, kx, ci); src is NHWC with pixel stride ld_src; optional nearest-2x
- * upsampling (upsample=1) of the source folded into the gather (FlaxUpsample2D), stride 1|2, pad 0|1, ksize 1|3.
+ * upsampling (upsample=1) of the source folded into the gather (FlaxUpsample2D), stride 1|2, pad 0|1, ksize 1|3
+ * (upsample = 3 / ksize = 2 are what ddpo_conv_up2x_folded_fwd hands its kernels: not accepted from callers).
  * dense mode (ksize==0): A = src (M,K) with row stride ld_src.
  * W is (K, N) row-major (Flax HWIO / (in,out) layout) unless w_trans, then (N, K). */
 typedef struct {
@@ -261,6 +262,23 @@ int ddpo_gemm_conv_fwd_bf16_planes(const ddpo_gemm_desc* d, const uint16_t* a_hi
  * (DDPO_MX_CROSS=0); exactly one of the two NULL is DDPO_EINVAL. */
 int ddpo_gemm_conv_fwd_f16mx_planes(const ddpo_gemm_desc* d, const uint16_t* a16, const uint16_t* a8, int lda,
                                     const uint16_t* w16, const uint16_t* w8, void* ws, size_t ws_bytes, void* stream);
+/* Folded nearest-2x up-sampler (additive to ABI v14): FlaxUpsample2D — jax.image.resize(nearest, 2x) followed by a 3x3 convolution, inside the
+ * U-Net / VAE-decoder call sites of ddpo/diffusers_patch/pipeline_flax_stable_diffusion.py:219-224,251 and ddpo/training/policy_gradient.py:87-102
+ * — computed as FOUR stride-1 2x2 convolutions on the source grid, one per output phase (py, px): output pixel (2y + py, 2x + px) reads source
+ * offsets {-1, 0} (phase 0) / {0, +1} (phase 1) per axis with the 3x3 taps that land on the same source pixel summed beforehand
+ * (ddpo_fold_up2x_weights).  Reduction length 4 Cin instead of 9 Cin; same function of the input, different rounding (weights are summed first).
+ *   ddpo_fold_up2x_weights: w (3, 3, Cin, Cout) HWIO -> wf (4, 2, 2, Cin, Cout) fp32, phase index py * 2 + px; fp32 sums, ky then kx ascending.
+ *     Each phase (4 Cin, Cout) is then packed like any forward weight (ddpo_pack_weights_bf16_kblocked / ddpo_pack_weights_f16mx).
+ *   ddpo_conv_up2x_folded_fwd: plane-fed only.  d: B, H, W (SOURCE dims), Cin (% 32 == 0), N = Cout (% 4 == 0), bias (optional), out (B * 2H * 2W
+ *     rows of ld_out floats, 16-byte aligned; ld_out may exceed N: the other columns are not touched); row bias / residual / epilogue / plane
+ *     emission / w_dgrad / aux_out must be zero (DDPO_EINVAL otherwise), every other field — alpha included: the layer has no scale — is ignored.  a_hi / a_lo / lda: the source activation planes as in
+ *     ddpo_gemm_conv_fwd_bf16_planes (f16mx != 0: as in ddpo_gemm_conv_fwd_f16mx_planes).  w_hi / w_lo: the four phases' k-blocked planes back to
+ *     back, (4, 4 Cin / 32, N, 32) 16-bit elements each (f16mx: w16 and w8 — (4, 4 Cin / 32, N, 64) bytes — with d->w_scale = (4, N) E8M0 bytes).
+ *     a_lo == NULL and w_lo == NULL: single-pass bf16.  All four phases run in one launch (plus one fixed-order reduce pass when the reduction
+ *     is split: ws / ws_bytes as in ddpo_gemm_conv_fwd_bf16; bit-reproducible). */
+int ddpo_fold_up2x_weights(const float* w, int Cin, int Cout, float* wf, void* stream);
+int ddpo_conv_up2x_folded_fwd(const ddpo_gemm_desc* d, const uint16_t* a_hi, const uint16_t* a_lo, int lda, const uint16_t* w_hi,
+                              const uint16_t* w_lo, int f16mx, void* ws, size_t ws_bytes, void* stream);
 /* fp32 W (K, N) -> f16mx weight planes, k-blocked: w16 (ceil(K/32), N, 32) f16 = f16(w); w8 (ceil(K/32), N, 64) bytes =
  * [e4m3(l * 2^11 / s_n) x 32 | e4m3(h / s_n) x 32] with h = f16(w), l = w - h and s_n = 2^(scale[n] - 127) the power of two that
  * puts the column's largest |w| in [128, 256); scale (N) bytes.  Zero padded in k. */
