@@ -19,7 +19,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <int D, int DPV, int KT>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k, int ldk,
                                                        const float* __restrict__ v, int ldv, float* __restrict__ o, int ldo,
-                                                       float* __restrict__ lse, int heads, int Nq, int Nk, float scale_log2e) {
+                                                       float* __restrict__ lse, int heads, int Nq, int Nk, float scale_log2e, int qbat) {
   constexpr int LDK = D + 2;
   constexpr int LDV = DPV + 4;
   constexpr int NS = D / 4;         // k-steps of the S^T product
@@ -36,7 +36,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
 
   float qr[NS];
   {
-    const float* qp = q + ((int64_t)b * Nq + qrow) * ldq + h * D + g;
+    const float* qp = q + ((int64_t)(b % qbat) * Nq + qrow) * ldq + h * D + g;      // qbat: query batch period (= B unless the queries are shared)
 #pragma unroll
     for (int s = 0; s < NS; ++s) qr[s] = qp[4 * s] * scale_log2e;
   }
@@ -141,31 +141,38 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const float* __restrict__
 }
 
 template <int D, int DPV, int KT>
-static int launch_attn(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo, float* lse,
+static int launch_attn(const float* q, int ldq, int qbat, const float* k, int ldk, const float* v, int ldv, float* o, int ldo, float* lse,
                        int B, int heads, int Nq, int Nk, float scale, hipStream_t st) {
   dim3 grid((Nq + 63) / 64, B * heads);
   hipLaunchKernelGGL((attn_fwd_kernel<D, DPV, KT>), grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, o, ldo, lse, heads, Nq, Nk,
-                     scale * 1.4426950408889634f);
+                     scale * 1.4426950408889634f, qbat);
   DDPO_LAUNCH_CHECK();
   return DDPO_OK;
 }
 
-extern "C" int ddpo_attention_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
-                                  float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
+/* batch b reads the queries of batch b % q_batches (q_batches == B: the plain function) */
+extern "C" int ddpo_attention_fwd_shared_q(const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
+                                           float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
   if (!q || !k || !v || !o || B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0) return DDPO_EINVAL;
   if ((ldq & 3) || (ldk & 3) || (ldv & 3) || (ldo & 3)) return DDPO_EINVAL;
   if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
        reinterpret_cast<uintptr_t>(o)) & 15) return DDPO_EINVAL;
   if ((long)B * heads > 65535) return DDPO_EINVAL;
+  if (q_batches < 1 || q_batches > B || B % q_batches) return DDPO_EINVAL;
   hipStream_t st = as_stream(stream);
   switch (d) {
-    case 4:   return launch_attn<4, 16, 64>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
-    case 8:   return launch_attn<8, 16, 64>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
-    case 16:  return launch_attn<16, 16, 64>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
-    case 40:  return launch_attn<40, 48, 64>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
-    case 64:  return launch_attn<64, 64, 64>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
-    case 80:  return launch_attn<80, 80, 64>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
-    case 160: return launch_attn<160, 160, 32>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
+    case 4:   return launch_attn<4, 16, 64>(q, ldq, q_batches, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
+    case 8:   return launch_attn<8, 16, 64>(q, ldq, q_batches, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
+    case 16:  return launch_attn<16, 16, 64>(q, ldq, q_batches, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
+    case 40:  return launch_attn<40, 48, 64>(q, ldq, q_batches, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
+    case 64:  return launch_attn<64, 64, 64>(q, ldq, q_batches, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
+    case 80:  return launch_attn<80, 80, 64>(q, ldq, q_batches, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
+    case 160: return launch_attn<160, 160, 32>(q, ldq, q_batches, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
     default:  return DDPO_EINVAL;
   }
+}
+
+extern "C" int ddpo_attention_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
+                                  float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
+  return ddpo_attention_fwd_shared_q(q, ldq, B, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, d, scale, stream);
 }

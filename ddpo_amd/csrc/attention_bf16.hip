@@ -264,7 +264,7 @@ __device__ __forceinline__ void attn_store_o(const AttnOut out, int64_t row, int
 template <int D, int DKP, int DVP, bool F16P>     // head dim, padded to 16 (QK^T reduction) and to 32 (rows of O^T)
 __global__ void __launch_bounds__(256) attn_fwd_bf16_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k, int ldk,
                                                             const float* __restrict__ v, int ldv, const AttnOut out,
-                                                            float* __restrict__ lse, int heads, int Nq, int Nk, float scale_log2e) {
+                                                            float* __restrict__ lse, int heads, int Nq, int Nk, float scale_log2e, int qbat) {
   constexpr int KT = 64;                  // keys per tile
   constexpr int LDK = DKP + 8;            // bf16 per K row: (DKP+8)*2 bytes = odd multiple of 16 B -> conflict-free b128 rows
   constexpr int LDVT = KT + 4;            // f16 per V^T row: 136 B -> 32 rows hit distinct even banks for ds_read_b64
@@ -285,7 +285,7 @@ __global__ void __launch_bounds__(256) attn_fwd_bf16_kernel(const float* __restr
   // Q^T fragments (B operand): lane holds Q[q = li][dk = 16s + 8h .. +8], scaled, split
   bf16x8 qh[NKS], ql[NKS];
   {
-    const float* qp = q + ((int64_t)b * Nq + qrow) * ldq + hd * D;
+    const float* qp = q + ((int64_t)(b % qbat) * Nq + qrow) * ldq + hd * D;      // qbat: query batch period (= B unless the queries are shared)
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
       uint32_t hi[4], lo[4];
@@ -437,7 +437,7 @@ __global__ void __launch_bounds__(256) attn_pack_kv_kernel(const float* __restri
 template <int D, int DKP, int DVP, bool F16P>
 __global__ void __launch_bounds__(256, (DVP <= 32 ? 4 : (DKP <= 48 ? 3 : 2))) attn_fwd_bf16_pk_kernel(const float* __restrict__ q, int ldq, const uint4* __restrict__ img,
                                                                const AttnOut out, float* __restrict__ lse, int heads,
-                                                               int Nq, int Nk, int ntiles, float scale_log2e) {
+                                                               int Nq, int Nk, int ntiles, float scale_log2e, int qbat) {
   using I = AttnImg<D, DKP, DVP>;
   constexpr int KT = I::KT, LDK = I::LDK, LDVT = I::LDVT;
   constexpr int NKS = DKP / 16, NDT = DVP / 32;
@@ -455,7 +455,7 @@ __global__ void __launch_bounds__(256, (DVP <= 32 ? 4 : (DKP <= 48 ? 3 : 2))) at
 
   bf16x8 qh[NKS], ql[NKS];
   {
-    const float* qp = q + ((int64_t)b * Nq + qrow) * ldq + hd * D;
+    const float* qp = q + ((int64_t)(b % qbat) * Nq + qrow) * ldq + hd * D;      // qbat: query batch period (= B unless the queries are shared)
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
       uint32_t hi[4], lo[4];
@@ -559,7 +559,7 @@ typedef unsigned int u32x4_a __attribute__((ext_vector_type(4)));
 template <int D, int DKP, int DVP, int QB, bool F16P>
 __global__ void __launch_bounds__(256, (QB == 2 ? 2 : (DVP <= 32 ? 4 : (DKP <= 48 ? 3 : 2)))) attn_fwd_bf16_dma_kernel(const float* __restrict__ q, int ldq, const uint4* __restrict__ img,
                                                                const AttnOut out, float* __restrict__ lse, int heads,
-                                                               int Nq, int Nk, int ntiles, float scale_log2e) {
+                                                               int Nq, int Nk, int ntiles, float scale_log2e, int qbat) {
   using I = AttnImg<D, DKP, DVP>;
   constexpr int KT = I::KT, LDK = I::LDK, LDVT = I::LDVT;
   constexpr int NKS = DKP / 16, NDT = DVP / 32;
@@ -579,7 +579,7 @@ __global__ void __launch_bounds__(256, (QB == 2 ? 2 : (DVP <= 32 ? 4 : (DKP <= 4
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
     const int qrow = min(q0 + 32 * qb + li, Nq - 1);
-    const float* qp = q + ((int64_t)b * Nq + qrow) * ldq + hd * D;
+    const float* qp = q + ((int64_t)(b % qbat) * Nq + qrow) * ldq + hd * D;      // qbat: query batch period (= B unless the queries are shared)
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
       uint32_t hi[4], lo[4];
@@ -699,7 +699,7 @@ static int launch_pack_kv(const float* k, int ldk, const float* v, int ldv, uint
 
 // attention from pre-packed K / V^T images (one image per 64-key tile and (batch, head))
 template <int D, int DKP, int DVP, bool F16P>
-static int launch_attn_images(const float* q, int ldq, const uint4* img, const AttnOut& out, float* lse, int B, int heads, int Nq, int Nk,
+static int launch_attn_images(const float* q, int ldq, int qbat, const uint4* img, const AttnOut& out, float* lse, int B, int heads, int Nq, int Nk,
                               float scale, hipStream_t st) {
   using I = AttnImg<D, DKP, DVP>;
   dim3 grid((Nq + 127) / 128, B * heads);
@@ -712,19 +712,19 @@ static int launch_attn_images(const float* q, int ldq, const uint4* img, const A
       // (measured and not kept, round 4: two query blocks per wave, s_setprio around the MFMA phases, and a software-pipelined one-barrier loop
       // with K and V^T double-buffered — 1.23 / 1.23 / 1.31 ms against 1.22: profiles/r04_probe_attn_qb2_prio.log)
       hipLaunchKernelGGL((attn_fwd_bf16_dma_kernel<D, DKP, DVP, 1, F16P>), grid, dim3(256), 0, st, q, ldq, img, out, lse, heads, Nq, Nk, ntiles,
-                         scale * 1.4426950408889634f);
+                         scale * 1.4426950408889634f, qbat);
       DDPO_LAUNCH_CHECK();
       return DDPO_OK;
     }
   }
   hipLaunchKernelGGL((attn_fwd_bf16_pk_kernel<D, DKP, DVP, F16P>), grid, dim3(256), 0, st, q, ldq, img, out, lse, heads, Nq, Nk, ntiles,
-                     scale * 1.4426950408889634f);
+                     scale * 1.4426950408889634f, qbat);
   DDPO_LAUNCH_CHECK();
   return DDPO_OK;
 }
 
 template <int D, int DKP, int DVP, bool F16P>
-static int launch_attn_bf16(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const AttnOut& out, float* lse,
+static int launch_attn_bf16(const float* q, int ldq, int qbat, const float* k, int ldk, const float* v, int ldv, const AttnOut& out, float* lse,
                             int B, int heads, int Nq, int Nk, float scale, void* ws, size_t ws_bytes, hipStream_t st) {
   using I = AttnImg<D, DKP, DVP>;
   dim3 grid((Nq + 127) / 128, B * heads);
@@ -734,10 +734,10 @@ static int launch_attn_bf16(const float* q, int ldq, const float* k, int ldk, co
     uint4* img = reinterpret_cast<uint4*>(ws);
     const int rc = launch_pack_kv<D, DKP, DVP, F16P>(k, ldk, v, ldv, img, B, heads, Nk, st);
     if (rc != DDPO_OK) return rc;
-    return launch_attn_images<D, DKP, DVP, F16P>(q, ldq, img, out, lse, B, heads, Nq, Nk, scale, st);
+    return launch_attn_images<D, DKP, DVP, F16P>(q, ldq, qbat, img, out, lse, B, heads, Nq, Nk, scale, st);
   }
   hipLaunchKernelGGL((attn_fwd_bf16_kernel<D, DKP, DVP, F16P>), grid, dim3(256), 0, st, q, ldq, k, ldk, v, ldv, out, lse, heads, Nq, Nk,
-                     scale * 1.4426950408889634f);
+                     scale * 1.4426950408889634f, qbat);
   DDPO_LAUNCH_CHECK();
   return DDPO_OK;
 }
@@ -786,26 +786,27 @@ static bool attn_out_ok(const AttnOut& out, int heads, int d) {
 }
 
 template <bool F16P>
-static int attention_fwd_impl(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const AttnOut& out,
+static int attention_fwd_impl(const float* q, int ldq, int qbat, const float* k, int ldk, const float* v, int ldv, const AttnOut& out,
                               float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* ws, size_t ws_bytes, void* stream) {
   if (!q || !k || !v || B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0 || d <= 0 || !attn_out_ok(out, heads, d)) return DDPO_EINVAL;
   if ((ldq & 3) || (ldk & 3) || (ldv & 3) || (long)B * heads > 65535) return DDPO_EINVAL;
   if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) & 15) return DDPO_EINVAL;
+  if (qbat < 1 || qbat > B || B % qbat) return DDPO_EINVAL;      // query batch period: a divisor of B
   hipStream_t st = as_stream(stream);
-#define CALL(DD, DK, DV) launch_attn_bf16<DD, DK, DV, F16P>(q, ldq, k, ldk, v, ldv, out, lse, B, heads, Nq, Nk, scale, ws, ws_bytes, st)
+#define CALL(DD, DK, DV) launch_attn_bf16<DD, DK, DV, F16P>(q, ldq, qbat, k, ldk, v, ldv, out, lse, B, heads, Nq, Nk, scale, ws, ws_bytes, st)
   ATTN_BY_D(CALL)
 #undef CALL
 }
 extern "C" int ddpo_attention_fwd_bf16x3(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
                                          float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* ws, size_t ws_bytes,
                                          void* stream) {
-  return attention_fwd_impl<false>(q, ldq, k, ldk, v, ldv, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale, ws,
+  return attention_fwd_impl<false>(q, ldq, B, k, ldk, v, ldv, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale, ws,
                                    ws_bytes, stream);
 }
 extern "C" int ddpo_attention_fwd_f16p(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
                                        float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* ws, size_t ws_bytes,
                                        void* stream) {
-  return attention_fwd_impl<true>(q, ldq, k, ldk, v, ldv, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale, ws,
+  return attention_fwd_impl<true>(q, ldq, B, k, ldk, v, ldv, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale, ws,
                                   ws_bytes, stream);
 }
 /* Plane-emitting forms (ABI v12): the output leaves as bf16 hi / lo planes (o_hi / o_lo, row stride ld_planes elements; 0 = k-blocked
@@ -814,14 +815,14 @@ extern "C" int ddpo_attention_fwd_bf16x3_po(const float* q, int ldq, const float
                                             uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale,
                                             void* ws, size_t ws_bytes, void* stream) {
   if (!o_hi) return DDPO_EINVAL;
-  return attention_fwd_impl<false>(q, ldq, k, ldk, v, ldv, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale,
+  return attention_fwd_impl<false>(q, ldq, B, k, ldk, v, ldv, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale,
                                    ws, ws_bytes, stream);
 }
 extern "C" int ddpo_attention_fwd_f16p_po(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, uint16_t* o_hi,
                                           uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale,
                                           void* ws, size_t ws_bytes, void* stream) {
   if (!o_hi) return DDPO_EINVAL;
-  return attention_fwd_impl<true>(q, ldq, k, ldk, v, ldv, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale,
+  return attention_fwd_impl<true>(q, ldq, B, k, ldk, v, ldv, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale,
                                   ws, ws_bytes, stream);
 }
 
@@ -864,38 +865,66 @@ extern "C" int ddpo_attention_pack_kv_f16p(const float* k, int ldk, const float*
 }
 
 template <bool F16P>
-static int attention_images_impl(const float* q, int ldq, const void* images, size_t images_bytes, const AttnOut& out, float* lse,
+static int attention_images_impl(const float* q, int ldq, int qbat, const void* images, size_t images_bytes, const AttnOut& out, float* lse,
                                  int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
   if (!q || !images || B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0 || d <= 0 || !attn_out_ok(out, heads, d)) return DDPO_EINVAL;
   if ((ldq & 3) || (long)B * heads > 65535) return DDPO_EINVAL;
+  if (qbat < 1 || qbat > B || B % qbat) return DDPO_EINVAL;      // query batch period: a divisor of B
   if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(images)) & 15) return DDPO_EINVAL;
   const size_t need = ddpo_attention_kv_images_bytes(B, heads, Nk, d);
   if (need == 0 || images_bytes < need) return DDPO_EINVAL;
   hipStream_t st = as_stream(stream);
   const uint4* img = reinterpret_cast<const uint4*>(images);
-#define CALL(DD, DK, DV) launch_attn_images<DD, DK, DV, F16P>(q, ldq, img, out, lse, B, heads, Nq, Nk, scale, st)
+#define CALL(DD, DK, DV) launch_attn_images<DD, DK, DV, F16P>(q, ldq, qbat, img, out, lse, B, heads, Nq, Nk, scale, st)
   ATTN_BY_D(CALL)
 #undef CALL
 }
 extern "C" int ddpo_attention_fwd_bf16x3_images(const float* q, int ldq, const void* images, size_t images_bytes, float* o, int ldo, float* lse,
                                                 int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
-  return attention_images_impl<false>(q, ldq, images, images_bytes, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d,
+  return attention_images_impl<false>(q, ldq, B, images, images_bytes, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d,
                                       scale, stream);
 }
 extern "C" int ddpo_attention_fwd_f16p_images(const float* q, int ldq, const void* images, size_t images_bytes, float* o, int ldo, float* lse,
                                               int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
-  return attention_images_impl<true>(q, ldq, images, images_bytes, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d,
+  return attention_images_impl<true>(q, ldq, B, images, images_bytes, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d,
                                      scale, stream);
 }
 extern "C" int ddpo_attention_fwd_bf16x3_images_po(const float* q, int ldq, const void* images, size_t images_bytes, uint16_t* o_hi, uint16_t* o_lo,
                                                    int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
   if (!o_hi) return DDPO_EINVAL;
-  return attention_images_impl<false>(q, ldq, images, images_bytes, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk,
+  return attention_images_impl<false>(q, ldq, B, images, images_bytes, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk,
                                       d, scale, stream);
 }
 extern "C" int ddpo_attention_fwd_f16p_images_po(const float* q, int ldq, const void* images, size_t images_bytes, uint16_t* o_hi, uint16_t* o_lo,
                                                  int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
   if (!o_hi) return DDPO_EINVAL;
-  return attention_images_impl<true>(q, ldq, images, images_bytes, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk,
+  return attention_images_impl<true>(q, ldq, B, images, images_bytes, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk,
                                      d, scale, stream);
+}
+
+/* Shared-query forms (include/ddpo_hip.h): batch b reads the queries of batch b % q_batches; everything else as the functions above. */
+static bool shared_q_out(float* o, int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, int64_t rows, AttnOut& out) {
+  if (o_hi) {
+    if (o) return false;
+    out = AttnOut{nullptr, o_hi, o_lo, ld_planes, rows};
+  } else {
+    out = AttnOut{o, nullptr, nullptr, ldo, rows};
+  }
+  return true;
+}
+extern "C" int ddpo_attention_fwd_x16_shared_q(int f16p, const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv,
+                                               float* o, int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads,
+                                               int Nq, int Nk, int d, float scale, void* ws, size_t ws_bytes, void* stream) {
+  AttnOut out;
+  if (!shared_q_out(o, ldo, o_hi, o_lo, ld_planes, (int64_t)B * Nq, out)) return DDPO_EINVAL;
+  return f16p ? attention_fwd_impl<true>(q, ldq, q_batches, k, ldk, v, ldv, out, lse, B, heads, Nq, Nk, d, scale, ws, ws_bytes, stream)
+              : attention_fwd_impl<false>(q, ldq, q_batches, k, ldk, v, ldv, out, lse, B, heads, Nq, Nk, d, scale, ws, ws_bytes, stream);
+}
+extern "C" int ddpo_attention_fwd_images_shared_q(int f16p, const float* q, int ldq, int q_batches, const void* images, size_t images_bytes,
+                                                  float* o, int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads,
+                                                  int Nq, int Nk, int d, float scale, void* stream) {
+  AttnOut out;
+  if (!shared_q_out(o, ldo, o_hi, o_lo, ld_planes, (int64_t)B * Nq, out)) return DDPO_EINVAL;
+  return f16p ? attention_images_impl<true>(q, ldq, q_batches, images, images_bytes, out, lse, B, heads, Nq, Nk, d, scale, stream)
+              : attention_images_impl<false>(q, ldq, q_batches, images, images_bytes, out, lse, B, heads, Nq, Nk, d, scale, stream);
 }

@@ -196,7 +196,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) gemm_conv_kernel(const ddpo_gemm
         if (row >= d.M) continue;
         float v = d.alpha * acc[i][j][r] + bv;
         if (d.rowbias) v += d.rowbias[(int64_t)(row / d.rows_per_batch) * d.ld_rowbias + col];
-        if (d.residual) v += d.residual[(int64_t)row * d.ld_res + col];
+        if (d.residual) v += d.residual[(int64_t)(d.res_rows ? row % d.res_rows : row) * d.ld_res + col];      // res_rows: row period of the residual
         d.out[(int64_t)row * d.ld_out + col] = v;
       }
     }
@@ -364,7 +364,7 @@ static int launch_wgrad(const ddpo_gemm_desc& d0, hipStream_t st) {
 extern "C" int ddpo_gemm_conv_wgrad(const ddpo_gemm_desc* dp, void* stream) {
   if (!dp) return DDPO_EINVAL;
   const ddpo_gemm_desc& d = *dp;
-  if (!d.src || !d.w || !d.out || d.M <= 0 || d.N <= 0 || d.K <= 0) return DDPO_EINVAL;
+  if (!d.src || !d.w || !d.out || d.M <= 0 || d.N <= 0 || d.K <= 0 || d.res_rows) return DDPO_EINVAL;
   if ((d.ld_src & 3) || (d.ld_w & 3) || (d.N & 3) || (d.K & 3)) return DDPO_EINVAL;
   if ((reinterpret_cast<uintptr_t>(d.src) | reinterpret_cast<uintptr_t>(d.w)) & 15) return DDPO_EINVAL;
   if (d.ksize > 0) {
@@ -408,6 +408,7 @@ extern "C" int ddpo_gemm_conv_fwd(const ddpo_gemm_desc* dp, void* stream) {
   if (d.w_dgrad && (!d.w_trans || d.ksize <= 0)) return DDPO_EINVAL;
   if (d.upsample < 0 || d.upsample > 2) return DDPO_EINVAL;
   if (d.rowbias && d.rows_per_batch <= 0) return DDPO_EINVAL;
+  if (d.res_rows != 0 && (d.res_rows < 0 || !d.residual || d.M % d.res_rows)) return DDPO_EINVAL;      // residual row period: a divisor of M
   hipStream_t st = as_stream(stream);
   // tile choice: big tiles when they still fill the chip (256 CUs), smaller ones for small problems
   const long t128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);

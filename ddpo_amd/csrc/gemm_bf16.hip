@@ -87,6 +87,9 @@ __device__ __forceinline__ void st_out4(float* p, const float4 v) {
   *reinterpret_cast<float4*>(p) = v;
 }
 
+// residual row of output row `row`: d.res_rows != 0 is a row period (the residual of a batch whose halves share it is held once)
+__device__ __forceinline__ int res_row(const ddpo_gemm_desc& d, int row) { return d.res_rows ? row % d.res_rows : row; }
+
 // plane-emitting output stage: 4 consecutive output values -> 4 bf16 hi + 4 bf16 lo (the split the fp32-fed loader would apply)
 __device__ __forceinline__ void store_planes4(const ddpo_gemm_desc& d, int64_t row, int col, const float4 v) {
   if (d.planes_fmt == 1) {                                            // f16mx planes (common.h)
@@ -145,6 +148,7 @@ struct EpiRows {
   // them and to every pass of the tall tile, computed for all NIT iterations up front and spilled — 1.4 KB of scratch per lane)
   __device__ __forceinline__ void fetch(const ddpo_gemm_desc& d, int b0, int row_base, int col_base, int lane) {
     if (!d.residual && !d.rowbias) return;
+    if (d.res_rows) { fetch_periodic(d, b0, row_base, col_base, lane); return; }
     asm volatile("" : "+v"(lane));
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
@@ -152,6 +156,17 @@ struct EpiRows {
       const int rowc = min(row_base + rr, d.M - 1), colc = min(col_base + (e - rr * LPR) * 4, d.N - 4);
       ex[i] = d.residual ? *reinterpret_cast<const float4*>(d.residual + (int64_t)rowc * d.ld_res + colc)
                          : *reinterpret_cast<const float4*>(d.rowbias + (int64_t)(rowc / d.rows_per_batch) * d.ld_rowbias + colc);
+    }
+  }
+  // the same with a residual row period (d.res_rows != 0, wave-uniform): output row m adds residual row m % res_rows.  A loop of its own, so
+  // the instruction sequence of every launch without a period stays what it was.
+  __device__ __forceinline__ void fetch_periodic(const ddpo_gemm_desc& d, int b0, int row_base, int col_base, int lane) {
+    asm volatile("" : "+v"(lane));
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int e = (b0 + i) * 64 + lane, rr = e / LPR;
+      const int rowc = min(row_base + rr, d.M - 1) % d.res_rows, colc = min(col_base + (e - rr * LPR) * 4, d.N - 4);
+      ex[i] = *reinterpret_cast<const float4*>(d.residual + (int64_t)rowc * d.ld_res + colc);
     }
   }
   // alpha * acc + bias (+ row bias) (+ residual), iterations b0 .. b0 + NB - 1, back into the LDS slot
@@ -487,7 +502,7 @@ __global__ void __launch_bounds__(BF_THREADS) gemm_conv_bf16_kernel(const ddpo_g
         if (row >= d.M) continue;
         float v = d.alpha * acc[i][j][r] + bv;
         if (d.rowbias) v += d.rowbias[(int64_t)(row / d.rows_per_batch) * d.ld_rowbias + col];
-        if (d.residual) v += d.residual[(int64_t)row * d.ld_res + col];
+        if (d.residual) v += d.residual[(int64_t)res_row(d, row) * d.ld_res + col];
         d.out[(int64_t)row * d.ld_out + col] = v;
       }
     }
@@ -1415,7 +1430,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         if ((ABL & 16) && (r | i | j)) { if (acc[i][j][r] == 123.456f) d.out[0] = 1.f; continue; }
         float v = d.alpha * acc[i][j][r] + bv;
         if (d.rowbias) v += d.rowbias[(int64_t)(row / d.rows_per_batch) * d.ld_rowbias + col];
-        if (d.residual) v += d.residual[(int64_t)row * d.ld_res + col];
+        if (d.residual) v += d.residual[(int64_t)res_row(d, row) * d.ld_res + col];
         d.out[(FOLD ? fold_row(d, row, ph) : (int64_t)row) * d.ld_out + col] = v;
       }
     }
@@ -1439,11 +1454,12 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ddpo_gemm_desc
       a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
     }
     float v[4] = {a.x, a.y, a.z, a.w};
+    const int rrow = res_row(d, row);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float x = d.alpha * v[e] + (d.bias ? d.bias[col + e] : 0.f);
       if (d.rowbias) x += d.rowbias[(int64_t)(row / d.rows_per_batch) * d.ld_rowbias + col + e];
-      if (d.residual) x += d.residual[(int64_t)row * d.ld_res + col + e];
+      if (d.residual) x += d.residual[(int64_t)rrow * d.ld_res + col + e];
       v[e] = x;
       if (d.out) d.out[(fold ? fold_row(d, row, ph) : (int64_t)row) * d.ld_out + col + e] = x;
     }
@@ -1452,6 +1468,18 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ddpo_gemm_desc
 }
 
 // plane-emitting output stage: only the vector output stage of the buffer-addressed kernels (and the split-K reduce) writes planes
+// Shortest reduction, in 32-wide k-tiles, for which a forward launcher considers a split-K (launch_bf16 / wide_splits below).  The split follows
+// the launch's tile count, i.e. its ROW count; callers that run one layer on a part of a batch and need the bits of the whole-batch launch
+// (UNet2DCondition.forward, cfg_dup) ask ddpo_gemm_splitk_min_ktiles() and do so only for reductions below the smaller of the two.
+constexpr int SPLITK_MIN_KTILES_128 = 32;       // 128 x 128 / 128 x 64 tiles
+constexpr int SPLITK_MIN_KTILES_WIDE = 16;      // 128 x 320 tiles
+extern "C" int ddpo_gemm_splitk_min_ktiles(void) { return SPLITK_MIN_KTILES_WIDE < SPLITK_MIN_KTILES_128 ? SPLITK_MIN_KTILES_WIDE : SPLITK_MIN_KTILES_128; }
+
+// residual row period (ddpo_gemm_desc.res_rows): 0, or a divisor of M with a residual to apply it to
+static bool res_rows_ok(const ddpo_gemm_desc& d) {
+  return d.res_rows == 0 || (d.res_rows > 0 && d.residual && d.M > 0 && d.M % d.res_rows == 0);
+}
+
 static bool planes_out_ok(const ddpo_gemm_desc& d) {
   if (!d.out_hi) return d.out != nullptr && !d.out_lo;
   if (!d.out_lo || d.ld_planes < 0 || (d.ld_planes & 3)) return false;
@@ -1511,7 +1539,7 @@ static int launch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint
   // split-K when the tile grid under-fills the 256 CUs and the reduction is long (8x8 / 16x16 latent levels)
   const int nk_total = (d.K + BF_BK - 1) / BF_BK;
   int splits = 1;
-  if (ws && ngrid < 192 && nk_total >= 32 && (d.N & 3) == 0 && d.epilogue == 0) {
+  if (ws && ngrid < 192 && nk_total >= SPLITK_MIN_KTILES_128 && (d.N & 3) == 0 && d.epilogue == 0) {
     splits = (384 + ngrid - 1) / ngrid;
     if (splits > 8) splits = 8;
     if (splits > nk_total / 8) splits = nk_total / 8;
@@ -1572,7 +1600,7 @@ static int wide_splits(const ddpo_gemm_desc& d, bool have_ws, size_t ws_bytes, i
   const int nblk = nph * ((d.M + 127) / 128) * ((d.N + 319) / 320);
   const int nk_total = d.K / BF_BK;
   int splits = 1;
-  if (have_ws && nblk <= 192 && nk_total >= 16) {
+  if (have_ws && nblk <= 192 && nk_total >= SPLITK_MIN_KTILES_WIDE) {
     splits = (256 + nblk / 2) / nblk;
     if (splits > 8) splits = 8;
     if (splits > nk_total / 8) splits = nk_total / 8;
@@ -1772,7 +1800,7 @@ extern "C" int ddpo_gemm_conv_fwd_bf16(const ddpo_gemm_desc* dp, const uint16_t*
   if (npass == 3 && !w_lo) return DDPO_EINVAL;
   if (!d.src || d.M <= 0 || d.N <= 0 || d.K <= 0 || d.ld_src <= 0 || (d.ld_src & 3) || (reinterpret_cast<uintptr_t>(d.src) & 15)) return DDPO_EINVAL;
   if ((reinterpret_cast<uintptr_t>(w_hi) & 15) || (w_lo && (reinterpret_cast<uintptr_t>(w_lo) & 15))) return DDPO_EINVAL;
-  if (!planes_out_ok(d) || (d.out_hi && !buf_path_ok(d, ldw))) return DDPO_EINVAL;
+  if (!planes_out_ok(d) || !res_rows_ok(d) || (d.out_hi && !buf_path_ok(d, ldw))) return DDPO_EINVAL;
   if (d.ksize > 0) {
     if (d.ksize != 1 && d.ksize != 3) return DDPO_EINVAL;
     if ((d.Cin & 7) || d.K != d.ksize * d.ksize * d.Cin || d.M != d.B * d.OH * d.OW) return DDPO_EINVAL;
@@ -1796,7 +1824,7 @@ extern "C" int ddpo_gemm_conv_fwd_bf16_planes(const ddpo_gemm_desc* dp, const ui
   if (!dp || !a_hi || !w_hi || (a_lo == nullptr) != (w_lo == nullptr)) return DDPO_EINVAL;
   const int npass = a_lo ? 3 : 1;          // ABI v14: BOTH lo planes NULL = single-pass bf16 (a_hi * w_hi only: XLA's TPU default precision)
   ddpo_gemm_desc d = *dp;
-  if (d.M <= 0 || d.N <= 0 || d.K <= 0 || lda < 0 || (lda & 7) || d.w_dgrad || !planes_out_ok(d)) return DDPO_EINVAL;      // lda == 0: k-blocked planes
+  if (d.M <= 0 || d.N <= 0 || d.K <= 0 || lda < 0 || (lda & 7) || d.w_dgrad || !planes_out_ok(d) || !res_rows_ok(d)) return DDPO_EINVAL;      // lda == 0: k-blocked planes
   if (npass == 1 && d.epilogue == 2) return DDPO_EINVAL;      // the tall GEGLU tile exists on the three-pass datapath only
   if ((reinterpret_cast<uintptr_t>(a_hi) | reinterpret_cast<uintptr_t>(a_lo) | reinterpret_cast<uintptr_t>(w_hi) |
        reinterpret_cast<uintptr_t>(w_lo)) & 15) return DDPO_EINVAL;
@@ -1830,7 +1858,7 @@ extern "C" int ddpo_gemm_conv_fwd_f16mx_planes(const ddpo_gemm_desc* dp, const u
   const int npass = a8 ? 4 : 5;            // ABI v14: BOTH 8-bit planes NULL = single-pass f16 (a_h * w_h only: the operator without its cross terms; opt-in)
   ddpo_gemm_desc d = *dp;
   if (npass == 5 && d.epilogue == 2) return DDPO_EINVAL;
-  if (d.M <= 0 || d.N <= 0 || d.K <= 0 || lda < 0 || (lda & 31) || d.w_dgrad || d.w_layout != 1 || !planes_out_ok(d)) return DDPO_EINVAL;
+  if (d.M <= 0 || d.N <= 0 || d.K <= 0 || lda < 0 || (lda & 31) || d.w_dgrad || d.w_layout != 1 || !planes_out_ok(d) || !res_rows_ok(d)) return DDPO_EINVAL;
   if ((reinterpret_cast<uintptr_t>(a16) | reinterpret_cast<uintptr_t>(a8) | reinterpret_cast<uintptr_t>(w16) | reinterpret_cast<uintptr_t>(w8)) & 15)
     return DDPO_EINVAL;
   if (d.ksize > 0) {
@@ -1868,7 +1896,7 @@ extern "C" int ddpo_conv_up2x_folded_fwd(const ddpo_gemm_desc* dp, const uint16_
   if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.Cin <= 0 || d.N <= 0 || (d.Cin % BF_BK) || (d.N & 3)) return DDPO_EINVAL;
   if ((int64_t)d.B * d.H * d.W * 4 > 0x7FFFFFFF || (int64_t)d.Cin * 4 > 0x7FFFFFFF) return DDPO_EINVAL;      // output rows and K are 32-bit
   if (lda < 0 || (lda & (f16mx ? 31 : 7)) || (lda && lda < d.Cin)) return DDPO_EINVAL;
-  if (!d.out || d.out_hi || d.out_lo || d.rowbias || d.residual || d.epilogue || d.w_dgrad || d.aux_out) return DDPO_EINVAL;
+  if (!d.out || d.out_hi || d.out_lo || d.rowbias || d.residual || d.res_rows || d.epilogue || d.w_dgrad || d.aux_out) return DDPO_EINVAL;
   if (d.ld_out < d.N || (d.ld_out & 3) || (reinterpret_cast<uintptr_t>(d.out) & 15) || (d.bias && (reinterpret_cast<uintptr_t>(d.bias) & 15))) return DDPO_EINVAL;
   if ((reinterpret_cast<uintptr_t>(a_hi) | reinterpret_cast<uintptr_t>(a_lo) | reinterpret_cast<uintptr_t>(w_hi) | reinterpret_cast<uintptr_t>(w_lo)) & 15)
     return DDPO_EINVAL;
@@ -2697,7 +2725,7 @@ static int wgrad_bf16x3(const ddpo_gemm_desc* dp, const uint16_t* a_hi, const ui
                        void* stream) {
   if (!dp) return DDPO_EINVAL;
   ddpo_gemm_desc d = *dp;
-  if ((!d.src && !a_hi) || (!d.w && !b_hi) || !d.out || d.M <= 0 || d.N <= 0 || d.K <= 0) return DDPO_EINVAL;
+  if ((!d.src && !a_hi) || (!d.w && !b_hi) || !d.out || d.M <= 0 || d.N <= 0 || d.K <= 0 || d.res_rows) return DDPO_EINVAL;
   if ((a_hi && !a_lo) || (b_hi && !b_lo)) return DDPO_EINVAL;
   if (d.colsum && b_hi) return DDPO_EINVAL;          // the fused bias gradient sums the fp32 dY registers
   if ((d.ld_src & 3) || (d.ld_w & 3) || (d.N & 3) || (d.K & 3)) return DDPO_EINVAL;

@@ -40,7 +40,7 @@ class GemmDesc(ctypes.Structure):
                 ("OH", c_int), ("OW", c_int),
                 ("w_dgrad", c_int), ("ld_w", c_int), ("splits", c_int), ("accumulate", c_int), ("epilogue", c_int),
                 ("out_hi", c_void_p), ("out_lo", c_void_p), ("ld_planes", c_int), ("w_layout", c_int),
-                ("w_scale", c_void_p), ("planes_fmt", c_int), ("colsum", c_void_p), ("aux_out", c_void_p)]
+                ("w_scale", c_void_p), ("planes_fmt", c_int), ("colsum", c_void_p), ("aux_out", c_void_p), ("res_rows", c_int)]
 
 
 ABI_VERSION = 14         # must equal ddpo_abi_version() of the loaded library (include/ddpo_hip.h)
@@ -50,6 +50,7 @@ _SIGS = {
     "ddpo_sizeof_gemm_desc": (c_size_t, []),
     "ddpo_sizeof_ddim_consts": (c_size_t, []),
     "ddpo_gemm_tile_launch_counts": (c_int, [c_void_p, c_int]),
+    "ddpo_gemm_splitk_min_ktiles": (c_int, []),
     "ddpo_threefry_bits_host": (c_int, [c_uint32, c_uint32, c_int64, c_void_p]),
     "ddpo_threefry_normal": (c_int, [c_uint32, c_uint32, c_void_p, c_void_p, c_int64, c_void_p]),
     "ddpo_ddim_step_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, POINTER(DdimConsts),
@@ -110,6 +111,13 @@ _SIGS = {
                                               c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]) for v in ("bf16x3", "f16p")},
     **{f"ddpo_attention_fwd_{v}_images_po": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                                      c_int, c_int, c_float, c_void_p]) for v in ("bf16x3", "f16p")},
+    # shared-query attention forwards (additive to ABI v14): q_batches after ldq; the 16-bit forms take f16p first and both output forms
+    "ddpo_attention_fwd_shared_q": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                            c_int, c_int, c_int, c_float, c_void_p]),
+    "ddpo_attention_fwd_x16_shared_q": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                                c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
+    "ddpo_attention_fwd_images_shared_q": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                                   c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ddpo_attention_bwd_f16p": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ddpo_attention_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -248,6 +256,12 @@ def mx_layer(w):
         return False
     ent = PACKED.get(w.data_ptr())
     return ent is not None and "mx" in ent
+
+
+def splitk_min_ktiles():
+    """The shortest reduction, in 32-wide k-tiles, for which the forward GEMM dispatcher considers a split-K at all — read from the library
+    (ddpo_gemm_splitk_min_ktiles: the dispatcher's own constants).  Below it the k partition of a layer cannot depend on the launch's row count."""
+    return int(load().ddpo_gemm_splitk_min_ktiles())
 
 
 def norm_planes(w, cin, rows, training=False):
@@ -1149,8 +1163,10 @@ def _bf16_route(w, K, N, conv, dgrad):
 
 
 def gemm_conv(src, w, *, M, N, K, bias=None, rowbias=None, rows_per_batch=0, residual=None, out=None, alpha=1.0,
-              w_trans=False, ld_src=None, ld_out=None, ld_res=None, conv=None, planes_out=None, planes_fmt=0):
+              w_trans=False, ld_src=None, ld_out=None, ld_res=None, conv=None, planes_out=None, planes_fmt=0, res_rows=0):
     """Generic entry: conv = dict(ksize, stride, pad, upsample, B, H, W, Cin, OH, OW) or None for a dense GEMM.
+    res_rows: row period of `residual` (ddpo_gemm_desc.res_rows) — output row m adds residual row m % res_rows, so the residual of a batch
+    whose halves share it is held once; 0: one residual row per output row.
     planes_out: None -> returns the fp32 result; "both" -> (fp32, Planes) from ONE launch (the output stage also writes the
     bf16 hi / lo planes a plane-fed consumer reads); "only" -> Planes (no fp32 tensor is written).  Check
     planes_out_ok() first: only the buffer-addressed bf16x3 kernels have the plane-emitting output stage.  planes_fmt: the format the CONSUMER
@@ -1190,6 +1206,7 @@ def gemm_conv(src, w, *, M, N, K, bias=None, rowbias=None, rows_per_batch=0, res
         out = torch.empty(M, N, dtype=torch.float32, device=src.device)
     if residual is not None:
         d.residual = residual.data_ptr(); d.ld_res = int(ld_res if ld_res is not None else N)
+    d.res_rows = int(res_rows)
     if out is not None:
         d.out = out.data_ptr(); d.ld_out = int(ld_out if ld_out is not None else N)
     d.alpha = float(alpha)
@@ -1231,7 +1248,7 @@ def gemm_conv(src, w, *, M, N, K, bias=None, rowbias=None, rows_per_batch=0, res
         e1.record()
         a_bytes = 4.0 * (conv["B"] * conv["H"] * conv["W"] * conv["Cin"] if conv else M * K)       # unique operand bytes
         w_bytes = (4.0 if route is None else (4.0 if _x3() else 2.0)) * K * N
-        io_bytes = a_bytes + w_bytes + 4.0 * M * N * (2 if residual is not None else 1)
+        io_bytes = a_bytes + w_bytes + 4.0 * N * (M + (0 if residual is None else (res_rows or M)))      # a periodic residual is read once per period
         # family tag: "fp32" (exact-fp32 kernel), "f16mx" (this launch ran the f16 + MX-fp8 kernel), else the bf16 datapath's name
         fam = "fp32" if route is None else ("f16mx" if (pl is not None and pl.fmt == 1) else ("bf16x3" if _x3() else current_datapath()))
         PROFILE.append((e0, e1, 2.0 * M * N * K, fam, io_bytes))
@@ -1265,36 +1282,43 @@ def attention_planes_ok(d):
     return current_datapath() != "fp32" and _x3() and d in (8, 16, 40, 64, 80)
 
 
-def attention(q, k, v, B, heads, Nq, Nk, d, scale=None, out=None, ldq=None, ldk=None, ldv=None, ldo=None, return_lse=False, planes_out=False):
-    """planes_out (check attention_planes_ok first): the result comes back as bf16 hi / lo `Planes` of exactly the fp32 values (ABI v12,
-    ddpo_attention_fwd_*_po) — the operand of a plane-fed to_out projection; no fp32 tensor is written."""
-    C = heads * d
+def attention(q, k, v, B, heads, Nq, Nk, d, scale=None, out=None, ldq=None, ldk=None, ldv=None, ldo=None, return_lse=False, planes_out=False,
+              q_batches=None):
+    """planes_out (check attention_planes_ok first): the result comes back as bf16 hi / lo `Planes` of exactly the fp32 values — the operand of
+    a plane-fed to_out projection; no fp32 tensor is written.
+    q_batches (a divisor of B): q holds q_batches batches of Nq rows and batch b attends with the queries of batch b % q_batches (same kernels,
+    same per-query arithmetic); None: one query batch per batch (q_batches = B)."""
     sc = float(scale if scale is not None else d ** -0.5)
-    if planes_out:
-        if not attention_planes_ok(d) or out is not None or return_lse:
-            raise DdpoHipError("plane-emitting attention needs the bf16x3 / f16mx datapath and a supported head dim (attention_planes_ok)")
-        opl = Planes(B * Nq, C, q.device)
-        nb = int(load().ddpo_attention_fwd_bf16x3_ws_bytes(B, heads, Nk, d))
-        ws = _scratch(nb, q.device, "attn_kv") if nb else None
-        fn, name = (load().ddpo_attention_fwd_f16p_po, "ddpo_attention_fwd_f16p_po") if _mx() else \
-            (load().ddpo_attention_fwd_bf16x3_po, "ddpo_attention_fwd_bf16x3_po")
-        _check(fn(_pr(q, ldq), int(ldq or C), _pr(k, ldk), int(ldk or C), _pr(v, ldv), int(ldv or C), _p(opl.hi), _p(opl.lo), opl.ld,
-                  None, B, heads, Nq, Nk, d, sc, _p(ws), nb, _stream()), name)
-        return opl
-    if out is None:
+    return _attention_shared_q(q, B if q_batches is None else q_batches, k, v, None, B, heads, Nq, Nk, d, sc, out, ldq, ldk, ldv, ldo, return_lse,
+                               planes_out)
+
+
+def _attention_shared_q(q, q_batches, k, v, images, B, heads, Nq, Nk, d, sc, out, ldq, ldk, ldv, ldo, return_lse, planes_out):
+    """The one routing of attention() / attention_from_images() (images: K / V come packed) to the kernels, through the shared-query entry points
+    (q_batches = B is the plain function: the C side forwards its plain entry points to the same code)."""
+    C = heads * d
+    x16 = current_datapath() != "fp32" and d in (8, 16, 40, 64, 80)
+    if planes_out and (not attention_planes_ok(d) or out is not None or return_lse):
+        raise DdpoHipError("plane-emitting attention needs the bf16x3 / f16mx datapath and a supported head dim, and writes planes only")
+    opl = Planes(B * Nq, C, q.device) if planes_out else None
+    if opl is None and out is None:
         out = torch.empty(B * Nq, C, dtype=torch.float32, device=q.device)
     lse = torch.empty(B * heads * Nq, dtype=torch.float32, device=q.device) if return_lse else None
-    if current_datapath() != "fp32" and d in (8, 16, 40, 64, 80):
+    o_args = (None, 0, _p(opl.hi), _p(opl.lo), opl.ld) if opl is not None else (_p(out), int(ldo or C), None, None, 0)
+    if images is not None:
+        _check(load().ddpo_attention_fwd_images_shared_q(int(_mx()), _pr(q, ldq), int(ldq or C), int(q_batches), _p(images), images.numel(), *o_args,
+                                                         _p(lse), B, heads, Nq, Nk, d, sc, _stream()), "ddpo_attention_fwd_images_shared_q")
+    elif x16:
         nb = int(load().ddpo_attention_fwd_bf16x3_ws_bytes(B, heads, Nk, d))      # 0 for short key sequences
         ws = _scratch(nb, q.device, "attn_kv") if nb else None
-        # the f16mx datapath's attention is the f16p operator (probabilities as one f16 term, two second-product passes); bf16x3 keeps three
-        fn, name = (load().ddpo_attention_fwd_f16p, "ddpo_attention_fwd_f16p") if _mx() else (load().ddpo_attention_fwd_bf16x3, "ddpo_attention_fwd_bf16x3")
-        _check(fn(_pr(q, ldq), int(ldq or C), _pr(k, ldk), int(ldk or C), _pr(v, ldv), int(ldv or C), _p(out), int(ldo or C),
-                  _p(lse), B, heads, Nq, Nk, d, sc, _p(ws), nb, _stream()), name)
+        _check(load().ddpo_attention_fwd_x16_shared_q(int(_mx()), _pr(q, ldq), int(ldq or C), int(q_batches), _pr(k, ldk), int(ldk or C), _pr(v, ldv),
+                                                      int(ldv or C), *o_args, _p(lse), B, heads, Nq, Nk, d, sc, _p(ws), nb, _stream()),
+               "ddpo_attention_fwd_x16_shared_q")
     else:
-        _check(load().ddpo_attention_fwd(_pr(q, ldq), int(ldq or C), _pr(k, ldk), int(ldk or C), _pr(v, ldv), int(ldv or C), _p(out), int(ldo or C),
-                                         _p(lse), B, heads, Nq, Nk, d, sc, _stream()), "ddpo_attention_fwd")
-    return (out, lse) if return_lse else out
+        _check(load().ddpo_attention_fwd_shared_q(_pr(q, ldq), int(ldq or C), int(q_batches), _pr(k, ldk), int(ldk or C), _pr(v, ldv), int(ldv or C),
+                                                  _p(out), int(ldo or C), _p(lse), B, heads, Nq, Nk, d, sc, _stream()), "ddpo_attention_fwd_shared_q")
+    res = opl if opl is not None else out
+    return (res, lse) if return_lse else res
 
 
 CAUSAL_MAX_N = 80       # ddpo_attention_causal_fwd holds all keys of a (batch, head) in LDS
@@ -1344,30 +1368,16 @@ def kv_images_valid(images):
     return images is not None and fmt is not None and getattr(images, "_ddpo_kv_fmt", None) == fmt
 
 
-def attention_from_images(q, images, B, heads, Nq, Nk, d, scale=None, out=None, ldq=None, ldo=None, return_lse=False, planes_out=False):
+def attention_from_images(q, images, B, heads, Nq, Nk, d, scale=None, out=None, ldq=None, ldo=None, return_lse=False, planes_out=False,
+                          q_batches=None):
     """softmax(q k^T * scale) v with k, v given as attention_kv_images() — packed under the SAME datapath (the f16mx datapath's images hold V as
-    f16 hi / lo with a row of ones, the bf16x3 datapath's as bf16 hi / lo).  planes_out: as in attention()."""
+    f16 hi / lo with a row of ones, the bf16x3 datapath's as bf16 hi / lo).  planes_out, q_batches: as in attention()."""
     C = heads * d
     if not kv_images_valid(images):
         raise DdpoHipError(f"attention_from_images: images packed as {getattr(images, '_ddpo_kv_fmt', None)!r}, the current datapath "
                            f"({current_datapath()}) reads {kv_images_fmt()!r} — repack with attention_kv_images()")
-    if planes_out:
-        if out is not None or return_lse:
-            raise DdpoHipError("plane-emitting attention writes planes only")
-        opl = Planes(B * Nq, C, q.device)
-        fn, name = (load().ddpo_attention_fwd_f16p_images_po, "ddpo_attention_fwd_f16p_images_po") if _mx() else \
-            (load().ddpo_attention_fwd_bf16x3_images_po, "ddpo_attention_fwd_bf16x3_images_po")
-        _check(fn(_p(q), int(ldq or C), _p(images), images.numel(), _p(opl.hi), _p(opl.lo), opl.ld, None, B, heads, Nq, Nk, d,
-                  float(scale if scale is not None else d ** -0.5), _stream()), name)
-        return opl
-    if out is None:
-        out = torch.empty(B * Nq, C, dtype=torch.float32, device=q.device)
-    lse = torch.empty(B * heads * Nq, dtype=torch.float32, device=q.device) if return_lse else None
-    sc = float(scale if scale is not None else d ** -0.5)
-    fn, name = (load().ddpo_attention_fwd_f16p_images, "ddpo_attention_fwd_f16p_images") if _mx() else \
-        (load().ddpo_attention_fwd_bf16x3_images, "ddpo_attention_fwd_bf16x3_images")
-    _check(fn(_p(q), int(ldq or C), _p(images), images.numel(), _p(out), int(ldo or C), _p(lse), B, heads, Nq, Nk, d, sc, _stream()), name)
-    return (out, lse) if return_lse else out
+    return _attention_shared_q(q, B if q_batches is None else q_batches, None, None, images, B, heads, Nq, Nk, d,
+                               float(scale if scale is not None else d ** -0.5), out, ldq, None, None, ldo, return_lse, planes_out)
 
 
 def attention_bwd(q, k, v, o, d_o, lse, B, heads, Nq, Nk, d, scale=None):

@@ -231,6 +231,9 @@ SKIP_INPLACE = os.environ.get("DDPO_SKIP_INPLACE", "1") == "1"
 H3_PLANES = os.environ.get("DDPO_H3_PLANES", "1") == "1"
 # sampling: the attention kernels hand their result to to_out as planes (see _attention); 0 restores the fp32 hand-over (A/B switch)
 ATTN_PLANES = os.environ.get("DDPO_ATTN_PLANES", "1") == "1"
+# sampling under classifier-free guidance (forward(cfg_dup=True)): the shared half batch is carried THROUGH the first transformer block up to the
+# first cross-attention (see _transformer, `full_B`); 0 restores the duplication behind the first ResBlock (A/B switch)
+CFG_SHARED_FRONT = os.environ.get("DDPO_CFG_SHARED_FRONT", "1") == "1"
 QKV_FUSED = os.environ.get("DDPO_QKV_FUSED", "1") == "1"       # sampling self-attention: q / k / v as one (K, 3C) projection (ParamStore.pack_bf16)
 
 
@@ -385,13 +388,17 @@ class UNet2DCondition:
         return self.grads
 
     # -------------------------------------------------------------------------------- attention
-    def _attention(self, name, x, B, N, C, heads, ctx, ctx_len, rec=None):
-        """Returns the attention output in front of to_out: fp32 (rows, C), or — sampling, where to_out is faster plane-fed (the 64x64 level:
+    def _attention(self, name, x, B, N, C, heads, ctx, ctx_len, rec=None, q_batches=None, plan_B=None):
+        """q_batches (sampling, cross-attention of a CFG batch whose halves share the queries): x holds q_batches * N rows, the query projection
+        runs on them once and batch b attends with the queries of batch b % q_batches (lib.attention `q_batches`).  plan_B: the batch the
+        routing decisions are taken on when this call sees only the shared half of it (default B).
+        Returns the attention output in front of to_out: fp32 (rows, C), or — sampling, where to_out is faster plane-fed (the 64x64 level:
         103 -> 62 us per launch in the model, profiles/r04_timeline_sampling_step.txt) — the bf16 hi / lo planes the attention kernel's output
         stage writes instead (the same values, so the block's result does not change by a bit)."""
         P = self.params
         po = bool(rec is None and ATTN_PLANES and L.PLANES_OUT and L.attention_planes_ok(C // heads) and
-                  L.planes_pay(P[name + ".to_out_0.kernel"], C, B * N) == 1)
+                  L.planes_pay(P[name + ".to_out_0.kernel"], C, (plan_B or B) * N) == 1)
+        qkw = {} if q_batches is None else dict(q_batches=q_batches)
         fq = P.fused_qkv.get(name + ".") if (QKV_FUSED and ctx is None and rec is None and L.current_datapath() != "fp32") else None
         if fq is not None and L.PACKED.get(fq.data_ptr()) is not None:      # sampling self-attention: one projection launch for q, k, v
             qkv = L.linear(x, fq)
@@ -401,14 +408,14 @@ class UNet2DCondition:
         if cached is not None:                     # text-context K / V were projected once for this sampling call
             k, v = cached[0], cached[1]
             if len(cached) > 2 and L.kv_images_valid(cached[2]):      # ... and packed once into the attention kernels' K / V^T images (under THIS datapath)
-                return L.attention_from_images(q, cached[2], B, heads, N, ctx_len, C // heads, planes_out=po)
+                return L.attention_from_images(q, cached[2], B, heads, N, ctx_len, C // heads, planes_out=po, **qkw)
         else:
             kv_src = x if ctx is None else ctx
             k = L.linear(kv_src, P[name + ".to_k.kernel"])
             v = L.linear(kv_src, P[name + ".to_v.kernel"])
         Nk = N if ctx is None else ctx_len
         if rec is None:
-            return L.attention(q, k, v, B, heads, N, Nk, C // heads, planes_out=po)
+            return L.attention(q, k, v, B, heads, N, Nk, C // heads, planes_out=po, **qkw)
         o, lse = L.attention(q, k, v, B, heads, N, Nk, C // heads, return_lse=True)
         rec.update(q=q, k=k, v=v, o=o, lse=lse, Nk=Nk)
         return o
@@ -438,10 +445,21 @@ class UNet2DCondition:
             x = x.float()
         L.lora_wgrad(x, dy, A, B_, dA, dB, self.lora.scale)
 
-    def _transformer(self, name, x: Act, ctx, ctx_len, heads, tape=None, emit_planes=0, dest=None):
-        """dest / strided x.t: as in resnet_forward (sampling: the block output lands in its consumer's concat buffer)."""
+    def _transformer(self, name, x: Act, ctx, ctx_len, heads, tape=None, emit_planes=0, dest=None, full_B=None):
+        """dest / strided x.t: as in resnet_forward (sampling: the block output lands in its consumer's concat buffer).
+        full_B (sampling under classifier-free guidance, the first block of the down path): x is the SHARED half of a batch of full_B = 2 x.B
+        samples whose halves differ in the text context only.  Everything in front of the cross-attention scores — norm, proj_in, norm1,
+        q / k / v, self-attention, attn1.to_out_0, norm2, attn2.to_q — runs on the x.B samples; attn2 reads the half-batch queries with a
+        query batch period against the full_B contexts, and the two residuals that meet the per-half data (h1 in attn2.to_out_0, x in
+        proj_out) are read with a residual row period, so neither is ever duplicated.  Every routing decision is taken on full_B * N rows:
+        what a launch computes per row is what the full-batch launch computes (bit-identical, tests/test_gpu_model.py)."""
         P, cfg = self.params, self.cfg
-        C, B, N = x.C, x.B, x.HW
+        C, Bx, N = x.C, x.B, x.HW                  # Bx: samples in front of the cross-attention; B: behind it (and for every routing decision)
+        B = Bx if full_B is None else full_B
+        if full_B is not None and (tape is not None or ctx is None or full_B % Bx):
+            raise ValueError("full_B: sampling forward only, a multiple of x.B")
+        qb = dict(q_batches=Bx) if B != Bx else {}
+        rr = dict(res_rows=Bx * N) if B != Bx else {}
         rec = None if tape is None else dict(name=name, x=x, heads=heads, ctx=ctx, ctx_len=ctx_len)
         tb = name + ".transformer_blocks_0"
         inf = tape is None                         # plane-fed GEMMs behind the norms (see resnet_forward)
@@ -462,21 +480,21 @@ class UNet2DCondition:
         pl_h3 = L.planes_pay(P[name + ".proj_out.kernel"], C, B * N) if inf and L.PLANES_OUT and H3_PLANES else 0
         if pl_h3 and not L.planes_out_ok(P[tb + ".ff.net_2.kernel"], F, B * N, C):
             pl_h3 = 0
-        hn, st = L.groupnorm(x.t, B, N, P[name + ".norm.scale"], P[name + ".norm.bias"], cfg.norm_groups, 1e-5, False, return_stats=True,
+        hn, st = L.groupnorm(x.t, Bx, N, P[name + ".norm.scale"], P[name + ".norm.bias"], cfg.norm_groups, 1e-5, False, return_stats=True,
                              planes=pl_in)
         if cfg.use_linear_projection:
             h0 = L.linear(hn, P[name + ".proj_in.kernel"], P[name + ".proj_in.bias"])
         else:
-            h0, _, _ = L.conv2d(hn, P[name + ".proj_in.kernel"], P[name + ".proj_in.bias"], B, x.H, x.W, C, C, 1)
+            h0, _, _ = L.conv2d(hn, P[name + ".proj_in.kernel"], P[name + ".proj_in.bias"], Bx, x.H, x.W, C, C, 1)
         ln = lambda n, t, pl=False: L.layernorm(t, P[f"{tb}.{n}.scale"], P[f"{tb}.{n}.bias"], 1e-5, planes=pl)
         a1r = None if rec is None else {}
         a2r = None if rec is None else {}
         l1 = ln("norm1", h0, pl_1)
-        a1 = self._attention(tb + ".attn1", l1, B, N, C, heads, None, 0, a1r)
+        a1 = self._attention(tb + ".attn1", l1, Bx, N, C, heads, None, 0, a1r, plan_B=B)
         h1 = L.linear(a1, P[tb + ".attn1.to_out_0.kernel"], P[tb + ".attn1.to_out_0.bias"], residual=h0)
         l2 = ln("norm2", h1, pl_2)
-        a2 = self._attention(tb + ".attn2", l2, B, N, C, heads, ctx, ctx_len, a2r)
-        h2 = L.linear(a2, P[tb + ".attn2.to_out_0.kernel"], P[tb + ".attn2.to_out_0.bias"], residual=h1)
+        a2 = self._attention(tb + ".attn2", l2, B, N, C, heads, ctx, ctx_len, a2r, **qb)
+        h2 = L.linear(a2, P[tb + ".attn2.to_out_0.kernel"], P[tb + ".attn2.to_out_0.bias"], residual=h1, **rr)
         l3 = ln("norm3", h2, pl_3)
         f = None
         # sampling: GEGLU fused into the GEMM epilogue, written as planes when FF2 can take them
@@ -495,6 +513,7 @@ class UNet2DCondition:
             po.update(out=dest, ld_out=int(dest.stride(0)))
         if x.ld is not None:
             po["ld_res"] = x.ld
+        po.update(rr)                              # the block input is the shared half: residual row m % (x.B * N)
         if cfg.use_linear_projection:
             out = L.linear(h3, P[name + ".proj_out.kernel"], P[name + ".proj_out.bias"], residual=x.t, **po)
         else:
@@ -563,8 +582,10 @@ class UNet2DCondition:
         """sample (B,C,H,W) fp32 NCHW; timesteps (B,) int32; context (B,L,D) fp32 -> (B,C_out,H,W).
         With `tape` (a list) every layer records what `backward` needs.
         `cfg_dup`: the caller guarantees that the second half of `sample` / `timesteps` repeats the first (classifier-free
-        guidance feeds [x; x]): everything in front of the first cross-attention (conv_in, the first ResBlock) is then
-        computed on one half and its rows duplicated — bit-identical, because no kernel depends on batch composition."""
+        guidance feeds [x; x]): everything in front of the first cross-attention — conv_in, the first ResBlock and the first
+        transformer block up to attn2's query projection (_transformer, `full_B`) — is then computed on one half; the two halves
+        meet the per-half text context in attn2, which reads the shared queries with a batch period, and the block's residuals
+        are read with a row period, so nothing is duplicated — bit-identical, because no kernel depends on batch composition."""
         P, cfg = self.params, self.cfg
         B, Cin, H, W = sample.shape
         boc = cfg.block_out_channels
@@ -594,6 +615,9 @@ class UNet2DCondition:
 
         dup = bool(cfg_dup) and tape is None and B % 2 == 0 and cfg.cross_attn_down[0]
         Bh = B // 2 if dup else B
+        # the half batch goes on through the first transformer block unless one of its K = boc[0] reductions is long enough for the GEMM
+        # dispatcher to consider a split-K (which follows the launch's row count: half the rows could then sum in another order)
+        front = dup and CFG_SHARED_FRONT and boc[0] // 32 < L.splitk_min_ktiles()
         def twice(a):
             """[a; a] along the rows (the CFG halves of a tensor computed once), by the engine's own copy kernel: no torch op inside the
             captured step."""
@@ -648,7 +672,7 @@ class UNet2DCondition:
             for j in range(cfg.layers_per_block):
                 if dup and i == 0 and j == 0:      # still in front of the first cross-attention: half the batch, then duplicate
                     r = resnet_forward(P, "down_blocks_0.resnets_0", h_half, temb_act if shared_t else temb_act[:Bh], G, 1e-5, None)
-                    h = Act(twice(r.t), B, r.H, r.W, r.C)
+                    h = r if front else Act(twice(r.t), B, r.H, r.W, r.C)      # front: the transformer block below takes the shared half as it is
                 else:
                     # the level's last block feeds the down-sampler convolution: its output stage also emits planes (sampling)
                     emit = 0
@@ -660,9 +684,9 @@ class UNet2DCondition:
                 if cfg.cross_attn_down[i]:
                     emit_t = 0
                     if tape is None and i < nlev - 1 and j == cfg.layers_per_block - 1:
-                        emit_t = L.planes_pay(P[f"down_blocks_{i}.downsamplers_0.conv.kernel"], boc[i], h.M)
+                        emit_t = L.planes_pay(P[f"down_blocks_{i}.downsamplers_0.conv.kernel"], boc[i], B * h.HW)
                     h = self._transformer(f"down_blocks_{i}.attentions_{j}", h, ctx, Lc, cfg.num_heads[i], tape, emit_planes=emit_t,
-                                          dest=skip_dest(h.M))
+                                          dest=skip_dest(B * h.HW), full_B=B if h.B != B else None)
                 skips.append(h)
                 if tape is not None:
                     tape.append(("skip_push", None))

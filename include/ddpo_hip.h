@@ -33,6 +33,10 @@ size_t ddpo_sizeof_ddim_consts(void);
  * Introspection only (which instantiation a layer geometry is routed to is otherwise invisible to the caller); kernels replayed from a
  * captured HIP graph are counted once, at capture. */
 int ddpo_gemm_tile_launch_counts(unsigned long long* out_host, int n);
+/* Additive to ABI v14.  The shortest reduction, in 32-wide k-tiles, for which the forward GEMM / conv dispatcher considers a split-K at all.  The
+ * split factor follows the launch's row count, so a caller that runs a layer on PART of a batch and needs the bits of the whole-batch launch
+ * (the CFG-shared front of the sampling U-Net) may do so only for layers with K / 32 below this value. */
+int ddpo_gemm_splitk_min_ktiles(void);
 
 /* ---- PRNG: jax.random (Threefry-2x32) -------------------------------------------------------------
  * jax.random.split / PRNGKey bookkeeping, pipeline/policy_gradient.py:51,201,244-245 and
@@ -214,6 +218,14 @@ typedef struct {
    * column order [a (N/2) | gate (N/2)] (the interleaving of the packed weights undone) — what the GEGLU backward needs, so the training forward
    * can use the fused launch too. */
   float* aux_out;
+  /* residual row period.  A TRAILING FIELD ADDED UNDER ABI v14 (the number is unchanged): the struct grew by one int, and the library reads the
+   * field on every forward call — a binding or C caller built against the shorter ABI-14 struct MUST be rebuilt against this header (zero the
+   * descriptor before filling it: 0 = the earlier behaviour) and must compare its struct size with ddpo_sizeof_gemm_desc() at load, as the
+   * ctypes mirror does; ddpo_abi_version() alone does not tell the two layouts apart.  res_rows > 0: `residual` holds res_rows rows and output row m adds residual row m % res_rows — the residual of a
+   * batch whose halves share it (classifier-free guidance: [x; x]) is held once.  Forward entry points only (ddpo_gemm_conv_fwd, _fwd_bf16,
+   * _fwd_bf16_planes, _fwd_f16mx_planes: every tile class, split-K reduce and plane-emitting output stage); needs `residual` and
+   * M % res_rows == 0, DDPO_EINVAL otherwise and wherever else it is non-zero (weight gradients, folded up-sampler). */
+  int res_rows;
 } ddpo_gemm_desc;
 int ddpo_gemm_conv_fwd(const ddpo_gemm_desc* d, void* stream);
 /* Data gradients reuse ddpo_gemm_conv_fwd: src = dY, w = forward kernel with w_trans=1, w_dgrad=1, and for the
@@ -390,6 +402,24 @@ int ddpo_attention_fwd_bf16x3_images_po(const float* q, int ldq, const void* ima
 int ddpo_attention_fwd_f16p_images_po(const float* q, int ldq, const void* images, size_t images_bytes, uint16_t* o_hi, uint16_t* o_lo,
                                       int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
 
+/* ---- Shared-query attention forwards (additive to ABI v14).  The same kernels and per-query arithmetic as the functions above, with a query
+ * batch period: q holds q_batches batches of Nq rows (1 <= q_batches <= B, B % q_batches == 0, DDPO_EINVAL otherwise) and the workgroups of
+ * batch b read their queries from batch b % q_batches; K / V (or their images), the output rows and lse stay per b.  q_batches == B is the plain
+ * function.  For the cross-attention of a classifier-free-guidance batch [x; x], whose two halves share the queries and differ in the text
+ * context only (pipeline_flax_stable_diffusion.py:219-224): the query projection runs, and is stored, once.
+ *   ddpo_attention_fwd_shared_q          the exact-fp32 kernel (ddpo_attention_fwd);
+ *   ddpo_attention_fwd_x16_shared_q      the 16-bit MFMA kernels: f16p == 0 ddpo_attention_fwd_bf16x3, else ddpo_attention_fwd_f16p;
+ *   ddpo_attention_fwd_images_shared_q   the same from K / V images of the matching pack function (ddpo_attention_fwd_{bf16x3,f16p}_images).
+ * Output of the last two: o_hi == NULL: fp32 rows (o, ldo); o_hi != NULL: o must be NULL and the output leaves as planes exactly as in the
+ * `_po` functions (o_hi, o_lo, ld_planes). */
+int ddpo_attention_fwd_shared_q(const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
+                                float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
+int ddpo_attention_fwd_x16_shared_q(int f16p, const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv, float* o,
+                                    int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d,
+                                    float scale, void* ws, size_t ws_bytes, void* stream);
+int ddpo_attention_fwd_images_shared_q(int f16p, const float* q, int ldq, int q_batches, const void* images, size_t images_bytes, float* o,
+                                       int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk,
+                                       int d, float scale, void* stream);
 
 /* Small element-wise pieces. */
 int ddpo_geglu_fwd(const float* x, float* y, int64_t rows, int F, void* stream);      /* y = x[:, :F] * gelu_tanh(x[:, F:]) */
