@@ -1,7 +1,7 @@
 // Implicit-GEMM convolution / dense GEMM on the bf16 MFMA datapath of gfx950 (v_mfma_f32_32x32x16_bf16, ~2.5 PFLOP/s
 // dense) with fp32 operands emulated by a bf16 split:   x = hi + lo,  hi = bf16(x),  lo = bf16(x - hi)
-//   NPASS = 3:  a*b ~= a_lo*b_hi + a_hi*b_lo + a_hi*b_hi   (XLA's "bf16_3x" / HIGH precision, ~2^-16 relative per product)
-//   NPASS = 1:  a*b ~= a_hi*b_hi                            (XLA's TPU DEFAULT precision, what the reference ran with)
+//   bf16x3:  a*b ~= a_lo*b_hi + a_hi*b_lo + a_hi*b_hi   (XLA's "bf16_3x" / HIGH precision, ~2^-16 relative per product)
+//   bf16x1:  a*b ~= a_hi*b_hi                            (XLA's TPU DEFAULT precision, what the reference ran with)
 // accumulated in fp32.  Same contract as gemm_conv_kernel (gemm.hip):
 //   out[m][n] = alpha * sum_k A(m,k) W(k,n) + bias[n] + rowbias[m / rows_per_batch][n] + residual[m][n]
 // Activations stay fp32 in HBM and are split while they are staged into LDS (v_cvt_pk_bf16_f32); weights are
@@ -9,7 +9,9 @@
 // pass, the original [K][N] order for data gradients), so a B fragment is one 16-byte load.
 // LDS tiles are [row][32 k] bf16 (64 B per row) with the 16-byte chunk index XOR-swizzled by (row>>2)&3: every
 // ds_read_b128 / ds_write of a 16-lane group touches 16 distinct 16-byte slots (conflict-free).
-#include "common.h"
+// This file is the forward path: output stage, both forward kernels, split-K reduce, dispatch and entry points.  The weight / activation
+// packers live in gemm_bf16_pack.hip, the weight gradient in gemm_bf16_wgrad.hip.
+#include "gemm_bf16_common.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -45,7 +47,13 @@ extern "C" int ddpo_debug_kloop_times(unsigned long long* host, int n_wg) {
   (void)n_wg;
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(ddpo_dbg_t), (size_t)2 * 16384 * 8 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
 }
+// the probe's ablation bits (DBG_ABL) ride in the unused upper bits of d.splits of a plane-fed launch
+static void dbg_abl_from_env(ddpo_gemm_desc& d) {
+  const char* e = getenv("DDPO_DBG_ABL");
+  if (e) d.splits |= atoi(e) << 4;
+}
 #else
+static void dbg_abl_from_env(ddpo_gemm_desc&) {}
 #define DBG_T(i) do { } while (0)
 #define DBG_ABL(bit) 0
 #define DBG_WDECL do { } while (0)
@@ -55,20 +63,22 @@ extern "C" int ddpo_debug_kloop_times(unsigned long long* host, int n_wg) {
 #define DBG_WSTORE() do { } while (0)
 #endif
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-#define BF_BK 32
-#define BF_THREADS 256
-
-// two floats -> packed bf16 hi pair and packed bf16 lo pair
-__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = cvt_pk_bf16(a, b);
-  lo = cvt_pk_bf16(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xFFFF0000u));
-}
+// The two template axes of the forward kernels.  The numeric values are the `npass` of the C ABI (datapath) and the historical k-loop numbers
+// the profiles and DESIGN.md refer to.
+enum class Datapath : int {
+  bf16x1 = 1,        // one bf16 MFMA per product (hi planes only)
+  bf16x3 = 3,        // three bf16 MFMAs per product (hi / lo planes of both operands)
+  f16mx = 4,         // plane-fed only: one f16 MFMA + one block-scaled 8-bit MFMA carrying both cross terms
+  f16x1 = 5,         // plane-fed only: the f16mx operator without its cross terms (the 16-bit planes alone)
+};
+enum class KLoop : int {
+  regs = 0,          // fp32 activations through two register stages, split into bf16 hi / lo while they are staged into LDS
+  planes3w = 3,      // plane-fed 128-row tiles: LDS-DMA, activations two LDS stages deep, weights three
+  tall = 5,          // plane-fed bf16x3 on the tall 256 x 320 tile (rotated two-stage schedule)
+  tall_geglu = 6,    // the same k-loop with the GEGLU output stage on value / gate wave pairs
+  tall_mx = 7,       // f16mx on the tall tile
+  tall_ring = 8,     // single-pass bf16 / f16 on the tall tile: four-stage LDS ring
+};
 
 // the f16mx cross-term MFMA: A = e5m2 (cbsz 1), B = e4m3 (blgp 0); the weight scale is byte `opb` of `sb` (op_sel is an immediate: the
 // switch folds away in unrolled callers)
@@ -235,7 +245,7 @@ struct EpiRows {
 
 // AFFINE: no upsampling / zero-insert in the gather, so the source address of tap (ky,kx) is rowptr + (ky*W + kx)*ld + ci
 // and all per-k-tile work is a mask test and one 64-bit add per row (the generic path recomputes coordinates).
-template <int BM, int BN, int NPASS, bool AFFINE>
+template <int BM, int BN, Datapath DP, bool AFFINE>
 __global__ void __launch_bounds__(BF_THREADS) gemm_conv_bf16_kernel(const ddpo_gemm_desc d, const uint16_t* __restrict__ w_hi,
                                                                    const uint16_t* __restrict__ w_lo, int ldw, int tiles_m,
                                                                    int tiles_n, int nblk, int kt_per_split,
@@ -244,7 +254,7 @@ __global__ void __launch_bounds__(BF_THREADS) gemm_conv_bf16_kernel(const ddpo_g
   constexpr int TM = BM / 64, TN = BN / 64;
   constexpr int AROWS = BM / 32;                 // float4 chunks per thread (A tile)
   constexpr int BCH = BN / 64;                   // 16-byte chunks per thread per plane (W tile)
-  constexpr int NPL = (NPASS == 3) ? 2 : 1;      // planes per operand
+  constexpr int NPL = (DP == Datapath::bf16x3) ? 2 : 1;      // planes per operand
   constexpr int A_BYTES = BM * 64, B_BYTES = BN * 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int STAGE = NPL * (A_BYTES + B_BYTES);      // per stage: A_hi | A_lo | B_hi | B_lo
@@ -372,7 +382,7 @@ __global__ void __launch_bounds__(BF_THREADS) gemm_conv_bf16_kernel(const ddpo_g
         else if (d.w_layout == 1) off = ((int64_t)(kb >> 5) * d.N + n) * 32 + (kb & 31);   // k-blocked (Kb, N, 32)
         else off = (int64_t)n * ldw + kb;
         h = *reinterpret_cast<const uint4*>(w_hi + off);
-        if (NPASS == 3) l = *reinterpret_cast<const uint4*>(w_lo + off);
+        if (DP == Datapath::bf16x3) l = *reinterpret_cast<const uint4*>(w_lo + off);
       }
       sg.bh[i] = h;
       sg.bl[i] = l;
@@ -397,13 +407,13 @@ __global__ void __launch_bounds__(BF_THREADS) gemm_conv_bf16_kernel(const ddpo_g
       uint2 hi, lo;
       split4(sg.a[i], hi, lo);
       *reinterpret_cast<uint2*>(st + a_st[i]) = hi;
-      if (NPASS == 3) *reinterpret_cast<uint2*>(st + A_BYTES + a_st[i]) = lo;
+      if (DP == Datapath::bf16x3) *reinterpret_cast<uint2*>(st + A_BYTES + a_st[i]) = lo;
     }
     char* sb = st + NPL * A_BYTES;
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
       *reinterpret_cast<uint4*>(sb + b_st[i]) = sg.bh[i];
-      if (NPASS == 3) *reinterpret_cast<uint4*>(sb + B_BYTES + b_st[i]) = sg.bl[i];
+      if (DP == Datapath::bf16x3) *reinterpret_cast<uint4*>(sb + B_BYTES + b_st[i]) = sg.bl[i];
     }
   };
 
@@ -434,18 +444,18 @@ __global__ void __launch_bounds__(BF_THREADS) gemm_conv_bf16_kernel(const ddpo_g
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         ah[i] = *reinterpret_cast<const bf16x8*>(sa + a_ld[ks][i]);
-        if (NPASS == 3) al[i] = *reinterpret_cast<const bf16x8*>(sa + A_BYTES + a_ld[ks][i]);
+        if (DP == Datapath::bf16x3) al[i] = *reinterpret_cast<const bf16x8*>(sa + A_BYTES + a_ld[ks][i]);
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         bh[j] = *reinterpret_cast<const bf16x8*>(sb + b_ld[ks][j]);
-        if (NPASS == 3) bl[j] = *reinterpret_cast<const bf16x8*>(sb + B_BYTES + b_ld[ks][j]);
+        if (DP == Datapath::bf16x3) bl[j] = *reinterpret_cast<const bf16x8*>(sb + B_BYTES + b_ld[ks][j]);
       }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          if (NPASS == 3) {
+          if (DP == Datapath::bf16x3) {
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
           }
@@ -518,21 +528,13 @@ __global__ void __launch_bounds__(BF_THREADS) gemm_conv_bf16_kernel(const ddpo_g
 // no per-load branches, no 64-bit address arithmetic, no zero-fill moves (the generic kernel above spends ~8 VALU +
 // 1 branch per MFMA on those; here the only VALU work left in the k-loop is the fp32 -> bf16 hi/lo split).
 // ------------------------------------------------------------------------------------------------
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-#define BUF_OOB 0x80000000u
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7FFFFFFF, 0x00020000);
-}
-
 // WM x WN waves of (BM / WM) x (BN / WN) each: 2 x 2 waves for the 128x128 / 128x64 tiles (256 threads, 2-3 workgroups per
 // CU); 4 x 2 waves of 32 x 160 for the 128x320 tile (512 threads, one workgroup per CU), which moves 233 B from L2 per
 // MFMA instead of 341 (128x128) / 512 (128x64) and makes N = 320 / 640 / 1280 tile counts multiples of the 256 CUs.
-// DEEP: global loads run two k-tiles ahead of the MFMAs (two register stages) instead of one.  Measured on the 8-wave tile:
-// one-ahead frees 26 VGPRs (no spills) but is 4-18 % slower than two-ahead with its 14 spilled dwords, so DEEP stays on.
+// KLoop::regs: global loads run TWO k-tiles ahead of the MFMAs (two register stages).  Measured on the 8-wave tile: one-ahead frees
+// 26 VGPRs (no spills) but is 4-18 % slower than two-ahead with its 14 spilled dwords, so one-ahead was deleted.
 //
-// APL ("A planes"): the activation operand arrives ALREADY split into bf16 hi / lo planes ([rows][ld] bf16, k contiguous;
+// Plane-fed k-loops (every KLoop but regs): the activation operand arrives ALREADY split into bf16 hi / lo planes ([rows][ld] bf16, k contiguous;
 // d.src = hi plane, d.w = lo plane, d.ld_src = row stride in ELEMENTS) written by the producing kernel (GroupNorm / LayerNorm
 // apply, ddpo_split_planes_bf16).  Both operands then go global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds): no staging
 // VGPRs, no v_cvt / v_sub split, no ds_write.  A wave instruction fills 16 rows x 64 B lane-linearly, so the XOR swizzle of
@@ -542,7 +544,17 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
 // FOLD (plane-fed only): one phase of a folded nearest-2x up-sampler per blockIdx.z (fold_row above): four taps with offsets {-1, 0} (phase 0) /
 // {0, +1} (phase 1) per axis on the source grid, the phase's own weight planes (K * N elements apart) and E8M0 scales (N apart), rows stored
 // through fold_row.  A compile-time switch: the instantiations without it are the same code as before it existed.
-template <int BM, int BN, int NPASS, int ABL = 0, int WM = 2, int WN = 2, bool DEEP = true, int APL = 0, bool FOLD = false>     // ABL: timing ablations (tools/ablate_gemm.py; wrong results)
+//
+// Instantiated combinations (35; kernel_exists() below is the same table for the host side):
+//   tile (BM x BN, WM x WN)                 k-loop       datapaths                          FOLD
+//   128x128, 128x64 (2x2), 128x320 (4x2)    regs         bf16x1, bf16x3                     no           6
+//   128x128, 128x64 (2x2), 128x320 (4x2)    planes3w     bf16x1, bf16x3, f16mx, f16x1       no          12
+//   128x128, 128x64 (2x2), 128x320 (4x2)    planes3w     bf16x1, bf16x3, f16mx              yes          9
+//   256x320 (4x2)                           tall         bf16x3                             no, yes      2
+//   256x320 (4x2)                           tall_geglu   bf16x3                             no           1
+//   256x320 (4x2)                           tall_mx      f16mx                              no, yes      2
+//   256x320 (4x2)                           tall_ring    bf16x1 (no, yes), f16x1 (no)                    3
+template <int BM, int BN, Datapath DP, int WM = 2, int WN = 2, KLoop KL = KLoop::regs, bool FOLD = false>
 __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) gemm_conv_bf16_buf_kernel(const ddpo_gemm_desc d, const uint16_t* __restrict__ w_hi_,
                                                                        const uint16_t* __restrict__ w_lo_, int ldw, int tiles_m,
                                                                        int tiles_n, int nblk, int kt_per_split,
@@ -556,13 +568,13 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
   constexpr int BCH = (BN + BR - 1) / BR;
   constexpr bool BFULL = (BN % BR) == 0;                // else the last W pass covers only part of the threads
   static_assert(BM % AR == 0 && WTM % 32 == 0 && WTN % 32 == 0, "tile / wave-grid mismatch");
-  constexpr bool MX = NPASS == 4;                       // f16mx datapath (plane-fed only): f16 plane + 8-bit plane per operand
-  static_assert(!MX || APL == 3 || APL == 7, "the f16mx datapath exists on the plane-fed 128-row tiles (APL 3) and on the tall tile (APL 7)");
-  static_assert(!FOLD || (APL != 0 && APL != 6), "folded up-sampler phases exist on the plane-fed kernels");
+  constexpr bool MX = DP == Datapath::f16mx;                       // f16mx datapath (plane-fed only): f16 plane + 8-bit plane per operand
+  static_assert(!MX || KL == KLoop::planes3w || KL == KLoop::tall_mx, "the f16mx datapath exists on the plane-fed 128-row tiles and on the tall tile");
+  static_assert(!FOLD || (KL != KLoop::regs && KL != KLoop::tall_geglu), "folded up-sampler phases exist on the plane-fed kernels");
   const int ph = FOLD ? (int)blockIdx.z : 0;                                   // phase (py, px) = (ph >> 1, ph & 1)
   const uint16_t* __restrict__ w_hi = FOLD ? w_hi_ + (int64_t)ph * d.K * d.N : w_hi_;
   const uint16_t* __restrict__ w_lo = (FOLD && w_lo_) ? w_lo_ + (int64_t)ph * d.K * d.N : w_lo_;
-  constexpr int NPL = (NPASS == 3 || NPASS == 4) ? 2 : 1;          // NPASS = 5: single-pass f16 (plane-fed only; the f16mx planes' 16-bit plane alone)
+  constexpr int NPL = (DP == Datapath::bf16x3 || DP == Datapath::f16mx) ? 2 : 1;          // (f16x1: the f16mx planes' 16-bit plane alone)
   constexpr int A_BYTES = BM * 64, B_BYTES = BN * 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int STAGE = NPL * (A_BYTES + B_BYTES);
@@ -621,7 +633,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       f.ah[i] = *reinterpret_cast<const bf16x8*>(pa + i * 2048);
-      if (NPASS == 3) f.al[i] = *reinterpret_cast<const bf16x8*>(pa + A_BYTES + i * 2048);
+      if (DP == Datapath::bf16x3) f.al[i] = *reinterpret_cast<const bf16x8*>(pa + A_BYTES + i * 2048);
       if (MX && ks) {
         const i32x4 x = *reinterpret_cast<const i32x4*>(sa + a_ld0 + A_BYTES + i * 2048), y = *reinterpret_cast<const i32x4*>(sa + a_ld1 + A_BYTES + i * 2048);
         f.a8[i] = i32x8{x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
@@ -630,7 +642,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       f.bh[j] = *reinterpret_cast<const bf16x8*>(pb + j * 2048);
-      if (NPASS == 3) f.bl[j] = *reinterpret_cast<const bf16x8*>(pb + B_BYTES + j * 2048);
+      if (DP == Datapath::bf16x3) f.bl[j] = *reinterpret_cast<const bf16x8*>(pb + B_BYTES + j * 2048);
       if (MX && ks) {
         const i32x4 x = *reinterpret_cast<const i32x4*>(sb + b_ld0 + B_BYTES + j * 2048), y = *reinterpret_cast<const i32x4*>(sb + b_ld1 + B_BYTES + j * 2048);
         f.b8[j] = i32x8{x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
@@ -666,20 +678,20 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
           if (ks) acc[i][j] = mx_mfma(f.a8[i], f.b8[j], acc[i][j], mx_sa, j & 3, mx_sbp[j >> 2]);
           continue;
         }
-        if (NPASS == 3) {
+        if (DP == Datapath::bf16x3) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.al[i], f.bh[j], acc[i][j], 0, 0, 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[i], f.bl[j], acc[i][j], 0, 0, 0);
         }
-        if constexpr (NPASS == 5) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, f.ah[i]), __builtin_bit_cast(f16x8, f.bh[j]), acc[i][j], 0, 0, 0);
+        if constexpr (DP == Datapath::f16x1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, f.ah[i]), __builtin_bit_cast(f16x8, f.bh[j]), acc[i][j], 0, 0, 0);
         else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[i], f.bh[j], acc[i][j], 0, 0, 0);
       }
     }
   };
 
-  if constexpr (APL != 0) {
+  if constexpr (KL != KLoop::regs) {
     // ---------------- LDS-DMA path: A planes + W planes straight into the swizzled LDS image ----------------
-    static_assert(NPASS == 1 || NPASS == 3 || NPASS == 4 || NPASS == 5, "the plane-fed path: bf16x3 / f16mx (two planes per operand) or single-pass bf16 / f16 (one)");
-    // two planes per operand: even waves move hi planes, odd waves lo planes (PAIRS loader groups per plane); ONE plane (NPASS = 1, round 6):
+    static_assert(DP == Datapath::bf16x1 || DP == Datapath::bf16x3 || DP == Datapath::f16mx || DP == Datapath::f16x1, "the plane-fed path: bf16x3 / f16mx (two planes per operand) or single-pass bf16 / f16 (one)");
+    // two planes per operand: even waves move hi planes, odd waves lo planes (PAIRS loader groups per plane); ONE plane (single-pass datapaths, round 6):
     // every wave is a loader group of the only plane.  NB is rounded up: with 8 waves the 20 weight pieces of a 320-column tile are 3 per wave,
     // the four surplus ones carry an out-of-range offset (they arrive as zeros, no memory traffic) and land in rows 320 .. 383 of a weight
     // stage padded to B_LDS bytes, which no fragment read touches — every wave issues the same number of pieces, so ONE counted vmcnt serves all.
@@ -687,7 +699,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
     constexpr int GA = BM / 16, GB = BN / 16;            // 16-row groups = 1 KiB LDS-DMA pieces per plane
     static_assert(NW % 2 == 0 && GA % PAIRS == 0 && (NPL == 1 || GB % PAIRS == 0), "pieces must divide evenly over the loader groups");
     constexpr int NA = GA / PAIRS, NB = (GB + PAIRS - 1) / PAIRS;
-    constexpr int B_LDS = NB * PAIRS * 1024;             // == B_BYTES unless padded (NPASS = 1, 320 columns on 8 waves: 24 KB for 20)
+    constexpr int B_LDS = NB * PAIRS * 1024;             // == B_BYTES unless padded (one plane, 320 columns on 8 waves: 24 KB for 20)
     const int wv = __builtin_amdgcn_readfirstlane(wid);
     const int plane = NPL == 2 ? (wv & 1) : 0, pr = NPL == 2 ? (wv >> 1) : wv;
     const int lr = lane >> 2;                            // row inside the 16-row piece
@@ -775,7 +787,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         if (conv && tap < ntaps) set_tap(tap);
       }
     };
-    if constexpr (APL == 5 || APL == 6) {
+    if constexpr (KL == KLoop::tall || KL == KLoop::tall_geglu) {
       // Schedule of the TALL 256x320 tile (64 x 160 per wave: 160 accumulator registers leave room for ONE fragment set;
       // the second wave of the SIMD covers the LDS latency).  28 fragment reads and 9 LDS-DMA pieces feed 60 MFMAs per wave and
       // k-tile, against 24 + 7 for 30 MFMAs on the 128x320 tile: 36 % fewer L2 and 42 % fewer LDS bytes per MFMA.
@@ -839,7 +851,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
           mma(g, 0, TM * TN);                            // ks = 1 of the last tile
         }
       }
-    } else if constexpr (APL == 3) {
+    } else if constexpr (KL == KLoop::planes3w) {
       // Mode 2's shape with the WEIGHT operand three LDS stages deep: [A s0 | A s1 | W s0 | W s1 | W s2] (128x320: 2 x 16 KB +
       // 3 x 40 KB = 152 KB).  At the barrier of k-tile s the activation pieces of tile s + 2 and the weight pieces of tile s + 3
       // are requested, in that order; the wait in front of the next barrier is a COUNTED vmcnt(NB): everything but the newest NB
@@ -922,7 +934,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         __builtin_amdgcn_sched_barrier(0);
         as = as_n; ws = ws_n;
       }
-    } else if constexpr (APL == 7) {
+    } else if constexpr (KL == KLoop::tall_mx) {
       // f16mx on the TALL 256 x 320 tile (round 5): eight waves of 64 x 160, two per SIMD (256 registers per lane: 160 accumulators + 96).
       // Why a tall tile: the f16mx kernels are bound by the chip's L2 -> LDS stream (8.4 - 11.4 TB/s, tools/native/dma_bench), not by the
       // matrix pipe — the 128 x 320 tile fetches 57 KB per k-tile for 1.31 M MAC (23 MAC / B), this one 73.7 KB for 2.62 M (35.5 MAC / B):
@@ -997,7 +1009,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         ktile(kt + 1, std::integral_constant<int, 1>{});
       }
       if (kt < nk) ktile(kt, std::integral_constant<int, 0>{});
-    } else if constexpr (APL == 8) {
+    } else if constexpr (KL == KLoop::tall_ring) {
       // SINGLE-PASS bf16 on the TALL 256 x 320 tile (round 6; BASELINE configs[4] names bf16: one v_mfma_f32_32x32x16_bf16 per product, XLA's TPU
       // default precision).  One plane per operand halves a k-tile's bytes (A 16 KB + W 20 KB, padded to 24), so the 160 KB of LDS hold a RING of
       // S = 4 stages instead of two: S - 1 k-tiles are requested ahead and the wait in front of a k-tile's barrier is a COUNTED vmcnt that leaves the
@@ -1008,7 +1020,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
       // (every wave's fragment reads of it returned: lgkmcnt(0)), so tile kt + S - 1 is requested into it.  Stage offsets are runtime values
       // (one v_add per fragment base: the 160 KB image exceeds the 64 KB reach of the ds_read offset field).  Per accumulator the order is
       // k half 0, k half 1 of consecutive k-tiles — the fp32-fed single-pass kernel's — so the two agree bit for bit.
-      static_assert((NPASS == 1 || NPASS == 5) && BM == 256 && BN == 320 && WM == 4 && WN == 2, "the single-pass tall tile");
+      static_assert((DP == Datapath::bf16x1 || DP == Datapath::f16x1) && BM == 256 && BN == 320 && WM == 4 && WN == 2, "the single-pass tall tile");
       constexpr int S = 4, ST = A_BYTES + B_LDS, P = NA + NB;
       static_assert(S * ST <= 160 * 1024 && P * (S - 2) < 64, "stage ring must fit the LDS and the vmcnt field");
       const uint32_t lds_a8 = lds0 + pr * 1024, lds_w8 = lds0 + A_BYTES + pr * 1024;
@@ -1056,7 +1068,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
           const bf16x8 bh0 = *reinterpret_cast<const bf16x8*>(sb + b_ld0 + j * 2048);
           const bf16x8 bh1 = *reinterpret_cast<const bf16x8*>(sb + b_ld1 + j * 2048);
           if (DBG_ABL(2)) { asm volatile("" :: "v"(ah0[0]), "v"(ah1[TM - 1]), "v"(bh0), "v"(bh1)); continue; }
-          if constexpr (NPASS == 5) {      // single-pass f16 (opt-in: the f16mx operator without its cross terms)
+          if constexpr (DP == Datapath::f16x1) {      // single-pass f16 (opt-in: the f16mx operator without its cross terms)
 #pragma unroll
             for (int i = 0; i < TM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah0[i]), __builtin_bit_cast(f16x8, bh0), acc[i][j], 0, 0, 0);
 #pragma unroll
@@ -1073,12 +1085,12 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         st_f = st_f + ST == S * ST ? 0 : st_f + ST;
       }
     } else {
-      static_assert(APL == 3 || APL == 5 || APL == 6, "plane-fed k-loops: 3 = three weight stages (128-row tiles), 5 = tall tile, 6 = tall tile with the GEGLU output stage, 7 = f16mx tall tile, 8 = single-pass tall tile");
+      static_assert(KL == KLoop::planes3w || KL == KLoop::tall || KL == KLoop::tall_geglu, "unknown plane-fed k-loop");
     }
   } else {
     const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(d.src);
     const __amdgpu_buffer_rsrc_t rs_wh = make_rsrc(w_hi);
-    const __amdgpu_buffer_rsrc_t rs_wl = make_rsrc(NPASS == 3 ? w_lo : w_hi);
+    const __amdgpu_buffer_rsrc_t rs_wl = make_rsrc(DP == Datapath::bf16x3 ? w_lo : w_hi);
 
     // ---- A rows of this thread: (t>>3) + 32*i, float4 index kq inside the 32-wide k-tile
     const int kq = t & 7;
@@ -1150,7 +1162,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
       for (int i = 0; i < BCH; ++i) {
         const u32x4 h = __builtin_amdgcn_raw_buffer_load_b128(rs_wh, bvoff[i], so_w, 0);
         sg.bh[i] = make_uint4(h.x, h.y, h.z, h.w);
-        if (NPASS == 3) {
+        if (DP == Datapath::bf16x3) {
           const u32x4 l = __builtin_amdgcn_raw_buffer_load_b128(rs_wl, bvoff[i], so_w, 0);
           sg.bl[i] = make_uint4(l.x, l.y, l.z, l.w);
         }
@@ -1177,14 +1189,14 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         uint2 hi, lo;
         split4(sg.a[i], hi, lo);
         *reinterpret_cast<uint2*>(st + a_st[i]) = hi;
-        if (NPASS == 3) *reinterpret_cast<uint2*>(st + A_BYTES + a_st[i]) = lo;
+        if (DP == Datapath::bf16x3) *reinterpret_cast<uint2*>(st + A_BYTES + a_st[i]) = lo;
       }
       char* sb = st + NPL * A_BYTES;
 #pragma unroll
       for (int i = 0; i < BCH; ++i) {
         if (!BFULL && (t >> 2) + BR * i >= BN) continue;
         *reinterpret_cast<uint4*>(sb + b_st[i]) = sg.bh[i];
-        if (NPASS == 3) *reinterpret_cast<uint4*>(sb + B_BYTES + b_st[i]) = sg.bl[i];
+        if (DP == Datapath::bf16x3) *reinterpret_cast<uint4*>(sb + B_BYTES + b_st[i]) = sg.bl[i];
       }
     };
 
@@ -1193,47 +1205,37 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
 
     // prologue: tile 0 -> LDS[0]; tile 1 in flight in s0.  The loop consumes k-tiles in pairs; an odd last tile is
     // computed after it (it already sits in LDS[0] with its ks=0 fragments in f0).
-    if (ABL & 32) {
-#pragma unroll
-      for (int i = 0; i < AROWS; ++i) s0.a[i] = make_float4(1.f, 1.f, 1.f, 1.f);
-#pragma unroll
-      for (int i = 0; i < BCH; ++i) s0.bh[i] = s0.bl[i] = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
-      store_tile(0, s0);
-    } else {
-      load_tile(0, s0);
-      store_tile(0, s0);
-      if (DEEP) load_tile(1, s0);
-    }
+    load_tile(0, s0);
+    store_tile(0, s0);
+    load_tile(1, s0);
     __syncthreads();
     DBG_T(1);
     ldfrag(0, 0, f0);
-    if (ABL & 8) ldfrag(0, 1, f1);
-    if (ABL & 1) s1 = s0;
     const int nk2 = nk & ~1;
 #pragma unroll 1
     for (int kt = 0; kt < nk2; kt += 2) {
-      // even step: MFMAs on LDS[0]; DEEP: s0 holds tile kt+1 and tile kt+2 starts loading into s1; else tile kt+1 loads into s0 now
-      if (!(ABL & 1)) { if (DEEP) load_tile(kt + 2, s1); else load_tile(kt + 1, s0); }
-      if (!(ABL & 8)) ldfrag(0, 1, f1);
+      // even step: MFMAs on LDS[0]; s0 holds tile kt+1 and tile kt+2 starts loading into s1
+      load_tile(kt + 2, s1);
+      ldfrag(0, 1, f1);
       mma(f0, 0, TT);
-      if (!(ABL & 2)) store_tile(1, s0);
+      store_tile(1, s0);
       __builtin_amdgcn_sched_barrier(0);          // LDS stores retire under the next MFMAs, not in front of the barrier
       mma(f1, 0, TH);
       __builtin_amdgcn_sched_barrier(0);
-      if (!(ABL & 4)) __syncthreads();
-      if (!(ABL & 8)) ldfrag(1, 0, f0);
+      __syncthreads();
+      ldfrag(1, 0, f0);
       __builtin_amdgcn_sched_barrier(0);
       mma(f1, TH, TT);
-      // odd step: MFMAs on LDS[1]
-      if (!(ABL & 1)) { if (DEEP) load_tile(kt + 3, s0); else load_tile(kt + 2, s0); }
-      if (!(ABL & 8)) ldfrag(1, 1, f1);
+      // odd step: MFMAs on LDS[1]; s1 holds tile kt+2 and tile kt+3 starts loading into s0
+      load_tile(kt + 3, s0);
+      ldfrag(1, 1, f1);
       mma(f0, 0, TT);
-      if (!(ABL & 2)) { if (DEEP) store_tile(0, s1); else store_tile(0, s0); }
+      store_tile(0, s1);
       __builtin_amdgcn_sched_barrier(0);
       mma(f1, 0, TH);
       __builtin_amdgcn_sched_barrier(0);
-      if (!(ABL & 4)) __syncthreads();
-      if (!(ABL & 8)) ldfrag(0, 0, f0);
+      __syncthreads();
+      ldfrag(0, 0, f0);
       __builtin_amdgcn_sched_barrier(0);
       mma(f1, TH, TT);
     }
@@ -1268,8 +1270,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
       Epi ep;
       const int colb = n0 + wn * WTN;
       static_assert(TM == 2, "the tall tile's output stage is written for two 32-row passes per wave");
-      if constexpr (APL == 6) {
-        // GEGLU on the tall tile (round 5; its own instantiation, APL = 6, so that the plain tall tile's code does not change by an instruction).  The weight columns of tile t come as [a (160) | gate (160)] of output columns 160 t .. 160 t + 159
+      if constexpr (KL == KLoop::tall_geglu) {
+        // GEGLU on the tall tile (round 5; its own instantiation, KLoop::tall_geglu, so that the plain tall tile's code does not change by an instruction).  The weight columns of tile t come as [a (160) | gate (160)] of output columns 160 t .. 160 t + 159
         // (ddpo_gemm_desc.epilogue == 2), so the wave pair (wm, 0) / (wm, 1) holds the value and the gate accumulators of the SAME 64 x 160
         // outputs.  Per 32-row pass: both waves add their bias IN REGISTERS (a lane's column is fixed per accumulator block) and transpose
         // the pre-activations into their LDS slices (adjacent: wid = 2 wm + wn); one barrier; then each wave of the pair takes 16 of the 32
@@ -1345,7 +1347,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
       return;
     }
   }
-  if (vec_ok && !(ABL & 16) && BM != 256) {
+  if (vec_ok && BM != 256) {
     constexpr int LPR = WTN / 4;                 // float4 per row of the wave sub-tile (WTM rows x WTN columns)
     constexpr int NIT = WTM * LPR / 64;          // wave instructions to move it
     static_assert((WTM * LPR) % 64 == 0, "wave sub-tile must be a whole number of 1 KiB rows");
@@ -1427,7 +1429,6 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
       for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
         if (row >= d.M) continue;
-        if ((ABL & 16) && (r | i | j)) { if (acc[i][j][r] == 123.456f) d.out[0] = 1.f; continue; }
         float v = d.alpha * acc[i][j][r] + bv;
         if (d.rowbias) v += d.rowbias[(int64_t)(row / d.rows_per_batch) * d.ld_rowbias + col];
         if (d.residual) v += d.residual[(int64_t)res_row(d, row) * d.ld_res + col];
@@ -1467,8 +1468,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const ddpo_gemm_desc
   }
 }
 
-// plane-emitting output stage: only the vector output stage of the buffer-addressed kernels (and the split-K reduce) writes planes
-// Shortest reduction, in 32-wide k-tiles, for which a forward launcher considers a split-K (launch_bf16 / wide_splits below).  The split follows
+// Shortest reduction, in 32-wide k-tiles, for which a forward launch considers a split-K (splits_128 / wide_splits below).  The split follows
 // the launch's tile count, i.e. its ROW count; callers that run one layer on a part of a batch and need the bits of the whole-batch launch
 // (UNet2DCondition.forward, cfg_dup) ask ddpo_gemm_splitk_min_ktiles() and do so only for reductions below the smaller of the two.
 constexpr int SPLITK_MIN_KTILES_128 = 32;       // 128 x 128 / 128 x 64 tiles
@@ -1527,75 +1527,51 @@ static bool buf_path_ok(const ddpo_gemm_desc& d, int ldw) {
 extern "C" void ddpo_debug_force_generic_gemm(int on) { g_force_generic = on != 0; }
 #endif
 
-// FOLD (all launchers below): the four phases of a folded up-sampler as blockIdx.z of the launch (ddpo_conv_up2x_folded_fwd) — the tile grid, and
-// with it every fill / split-K rule, counts NPH = 4 times the tiles of one phase; the partial sums of all phases must fit the scratch.
-template <int BM, int BN, int NPASS, int WM = 2, int WN = 2, int APL = 0, bool FOLD = false>
-static int launch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, float* ws, size_t ws_bytes,
-                       hipStream_t st) {
-  constexpr int NPH = FOLD ? 4 : 1;
-  const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
-  const int nblk = tiles_m * tiles_n;
-  const int ngrid = nblk * NPH;
-  // split-K when the tile grid under-fills the 256 CUs and the reduction is long (8x8 / 16x16 latent levels)
+// ---- tiles.  WM x WN waves of (BM / WM) x (BN / WN); TC: the launch counter of the tile class; EPI_BYTES: the LDS image of the output stage
+// (the whole C tile; on the tall tile eight 32 x 160 wave slices), a floor under the operand stages; SPLITK: the tile takes a split reduction.
+template <int BM_, int BN_, int WM_, int WN_, int TC_, size_t EPI_BYTES_, bool SPLITK_>
+struct Tile {
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, TC = TC_;
+  static constexpr bool SPLITK = SPLITK_;
+  // dynamic LDS: two stages of [A | W] planes (planes3w: two of A, three of W) or the output stage's image, whichever is larger — on the
+  // 128 x 320 and 256 x 320 tiles always the latter, 160 KB, which is also exactly the four 40 KB stages of the tall_ring k-loop
+  static constexpr size_t lds_bytes(Datapath dp, KLoop kl) {
+    const size_t npl = (dp == Datapath::bf16x3 || dp == Datapath::f16mx) ? 2 : 1;
+    const size_t stages = kl == KLoop::planes3w ? npl * (2 * BM + 3 * BN) * 64 : 2 * npl * (BM + BN) * 64;
+    return stages < EPI_BYTES_ ? EPI_BYTES_ : stages;
+  }
+};
+using Tile128x128 = Tile<128, 128, 2, 2, TC_128, 128 * 128 * 4, true>;      // 2-3 workgroups per CU
+using Tile128x64 = Tile<128, 64, 2, 2, TC_64, 128 * 64 * 4, true>;
+using TileWide = Tile<128, 320, 4, 2, TC_WIDE, 128 * 320 * 4, true>;        // 8 waves of 32 x 160, one workgroup per CU; buffer-addressed kernel only
+using TileTall = Tile<256, 320, 4, 2, TC_TALL, 8 * 32 * 160 * 4, false>;    // 8 waves of 64 x 160, plane-fed only, launched only where the grid fills the chip
+
+// the instantiations of gemm_conv_bf16_buf_kernel that exist (the table at its head); launch_tile instantiates nothing else
+template <class T, Datapath DP, KLoop KL, bool FOLD>
+constexpr bool kernel_exists() {
+  if (FOLD && (DP == Datapath::f16x1 || KL == KLoop::regs || KL == KLoop::tall_geglu)) return false;
+  if (T::BM == 256) {
+    if (DP == Datapath::bf16x3) return KL == KLoop::tall || KL == KLoop::tall_geglu;
+    return KL == (DP == Datapath::f16mx ? KLoop::tall_mx : KLoop::tall_ring);
+  }
+  return KL == KLoop::planes3w || (KL == KLoop::regs && (DP == Datapath::bf16x1 || DP == Datapath::bf16x3));
+}
+
+// ---- split-K: two pure rules (which split a tile grid WANTS) and the rounding every launch applies to it
+// 128 x 128 / 128 x 64 tiles: split when the tile grid under-fills the 256 CUs and the reduction is long (8x8 / 16x16 latent levels)
+static int splits_128(const ddpo_gemm_desc& d, int ngrid, bool have_ws, size_t ws_bytes, int nph) {
   const int nk_total = (d.K + BF_BK - 1) / BF_BK;
   int splits = 1;
-  if (ws && ngrid < 192 && nk_total >= SPLITK_MIN_KTILES_128 && (d.N & 3) == 0 && d.epilogue == 0) {
+  if (have_ws && ngrid < 192 && nk_total >= SPLITK_MIN_KTILES_128 && (d.N & 3) == 0 && d.epilogue == 0) {
     splits = (384 + ngrid - 1) / ngrid;
     if (splits > 8) splits = 8;
     if (splits > nk_total / 8) splits = nk_total / 8;
-    while (splits > 1 && (size_t)NPH * splits * d.M * d.N * sizeof(float) > ws_bytes) --splits;
+    while (splits > 1 && (size_t)nph * splits * d.M * d.N * sizeof(float) > ws_bytes) --splits;
   }
-  int ktps = (nk_total + splits - 1) / splits;
-  ktps = (ktps + 1) & ~1;                                  // the pipelined loop consumes k-tiles in pairs
-  splits = (nk_total + ktps - 1) / ktps;
-  float* part = splits > 1 ? ws : nullptr;
-  constexpr int NPL = (NPASS == 3 || NPASS == 4) ? 2 : 1;
-  size_t lds = (APL == 3) ? NPL * (size_t)(2 * BM + 3 * BN) * 64 : 2 * NPL * (size_t)(BM + BN) * 64;     // APL 3: three weight stages
-  if (lds < (size_t)BM * BN * 4) lds = (size_t)BM * BN * 4;     // the epilogue transposes the C tile through LDS
-  static bool attr_set = false;
-  if (!attr_set) {
-    if constexpr (APL == 0) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_kernel<BM, BN, NPASS, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_kernel<BM, BN, NPASS, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  count_tile(BN == 128 ? TC_128 : TC_64);
-  if constexpr (NPASS == 4) count_tile(TC_MX);
-  if constexpr (APL != 0) {                // the plane-fed entry points have already checked buf_path_ok
-    hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>), dim3(nblk, splits, NPH), dim3(64 * WM * WN), lds, st, d, w_hi,
-                       w_lo, ldw, tiles_m, tiles_n, nblk, ktps, part);
-  } else {
-    if (!buf_path_ok(d, ldw)) count_tile(TC_GENERIC);
-    if (buf_path_ok(d, ldw))
-      hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL>), dim3(nblk, splits), dim3(64 * WM * WN), lds, st, d, w_hi,
-                         w_lo, ldw, tiles_m, tiles_n, nblk, ktps, part);
-    else if (d.upsample == 0)
-      hipLaunchKernelGGL((gemm_conv_bf16_kernel<BM, BN, NPASS, true>), dim3(nblk, splits), dim3(BF_THREADS), lds, st, d, w_hi, w_lo, ldw,
-                         tiles_m, tiles_n, nblk, ktps, part);
-    else
-      hipLaunchKernelGGL((gemm_conv_bf16_kernel<BM, BN, NPASS, false>), dim3(nblk, splits), dim3(BF_THREADS), lds, st, d, w_hi, w_lo, ldw,
-                         tiles_m, tiles_n, nblk, ktps, part);
-  }
-  DDPO_LAUNCH_CHECK();
-  if (splits > 1) {
-    int64_t blocks = ((int64_t)d.M * (d.N >> 2) + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    count_tile(TC_SPLITK_REDUCE);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks, NPH), dim3(256), 0, st, d, part, splits);
-    DDPO_LAUNCH_CHECK();
-  }
-  return DDPO_OK;
+  return splits;
 }
-
-
-// 128x320 tiles, 8 waves (4 x 2), one workgroup per CU: buffer-addressed kernel only (caller checked buf_path_ok).
-// Tile counts of the U-Net layers are multiples of the 256 CUs at the 64x64 and 32x32 levels; below that the reduction is
-// split so that ~256 workgroups exist.
+// 128 x 320 tiles: their counts are multiples of the 256 CUs at the 64x64 and 32x32 levels of the U-Net; below that the reduction is
+// split so that ~256 workgroups exist
 static int wide_splits(const ddpo_gemm_desc& d, bool have_ws, size_t ws_bytes, int nph = 1) {
   const int nblk = nph * ((d.M + 127) / 128) * ((d.N + 319) / 320);
   const int nk_total = d.K / BF_BK;
@@ -1609,187 +1585,160 @@ static int wide_splits(const ddpo_gemm_desc& d, bool have_ws, size_t ws_bytes, i
   }
   return splits;
 }
-
-template <int NPASS, int APL = 0, bool FOLD = false>
-static int launch_bf16_wide(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, float* ws, size_t ws_bytes,
-                            hipStream_t st) {
-  constexpr int BM = 128, BN = 320, WM = 4, WN = 2;      // 8 waves of 32x160, two per SIMD
-  constexpr int NPH = FOLD ? 4 : 1;
-  const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
-  const int nblk = tiles_m * tiles_n;
-  const int nk_total = d.K / BF_BK;
-  int splits = wide_splits(d, ws != nullptr, ws_bytes, NPH);
+// k-tiles per split, an even number (the pipelined loops consume k-tiles in pairs), and the number of splits that leaves
+static int ktiles_per_split(int nk_total, int& splits) {
   int ktps = (nk_total + splits - 1) / splits;
   ktps = (ktps + 1) & ~1;
   splits = (nk_total + ktps - 1) / ktps;
-  float* part = splits > 1 ? ws : nullptr;
-  const size_t lds = (size_t)BM * BN * 4;                  // epilogue image (160 KB) > 2 stages of operand tiles (112 KB)
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  count_tile(TC_WIDE);
-  if constexpr (NPASS == 4) count_tile(TC_MX);
-  hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>), dim3(nblk, splits, NPH), dim3(64 * WM * WN), lds, st, d, w_hi,
-                     w_lo, ldw, tiles_m, tiles_n, nblk, ktps, part);
+  return ktps;
+}
+
+static int launch_splitk_reduce(const ddpo_gemm_desc& d, const float* part, int splits, int nph, hipStream_t st) {
+  int64_t blocks = ((int64_t)d.M * (d.N >> 2) + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  count_tile(TC_SPLITK_REDUCE);
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks, nph), dim3(256), 0, st, d, part, splits);
   DDPO_LAUNCH_CHECK();
-  if (splits > 1) {
-    int64_t blocks = ((int64_t)d.M * (d.N >> 2) + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    count_tile(TC_SPLITK_REDUCE);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks, NPH), dim3(256), 0, st, d, part, splits);
+  return DDPO_OK;
+}
+
+// The one launcher.  `splits` is what the route asked for (1 without a scratch `ws`); FOLD: the four phases of a folded up-sampler are
+// blockIdx.z of the launch (ddpo_conv_up2x_folded_fwd), and the partial sums of all phases lie in `ws`.  The register-staged k-loop of the
+// four-wave tiles falls back to the pointer-addressed generic kernel where buf_path_ok() fails; every other caller has checked it.
+template <class T, Datapath DP, KLoop KL, bool FOLD>
+static int launch_tile(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, float* ws, int splits, hipStream_t st) {
+  if constexpr (!kernel_exists<T, DP, KL, FOLD>()) {
+    return DDPO_EINVAL;
+  } else {
+    constexpr int NPH = FOLD ? 4 : 1;
+    constexpr bool GENERIC = KL == KLoop::regs && T::BN <= 128;
+    constexpr size_t lds = T::lds_bytes(DP, KL);
+    const auto kernel = &gemm_conv_bf16_buf_kernel<T::BM, T::BN, DP, T::WM, T::WN, KL, FOLD>;
+    const int tiles_m = (d.M + T::BM - 1) / T::BM, tiles_n = (d.N + T::BN - 1) / T::BN;
+    const int nblk = tiles_m * tiles_n;
+    const int nk_total = (d.K + BF_BK - 1) / BF_BK;
+    if (!T::SPLITK) splits = 1;
+    const int ktps = T::SPLITK ? ktiles_per_split(nk_total, splits) : nk_total;
+    float* part = splits > 1 ? ws : nullptr;
+    static bool attr_set = false;
+    if (!attr_set) {
+      if constexpr (GENERIC) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_kernel<T::BM, T::BN, DP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_kernel<T::BM, T::BN, DP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      }
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set = true;
+    }
+    count_tile(T::TC);
+    if constexpr (DP == Datapath::f16mx) count_tile(TC_MX);
+    bool generic = false;
+    if constexpr (GENERIC) generic = !buf_path_ok(d, ldw);
+    if (!generic) {
+      hipLaunchKernelGGL(kernel, dim3(nblk, splits, NPH), dim3(64 * T::WM * T::WN), lds, st, d, w_hi, w_lo, ldw, tiles_m, tiles_n, nblk, ktps, part);
+    } else if constexpr (GENERIC) {
+      count_tile(TC_GENERIC);
+      if (d.upsample == 0)      // AFFINE: no up-sampling / zero-insert in the gather
+        hipLaunchKernelGGL((gemm_conv_bf16_kernel<T::BM, T::BN, DP, true>), dim3(nblk, splits), dim3(BF_THREADS), lds, st, d, w_hi, w_lo, ldw, tiles_m, tiles_n, nblk, ktps, part);
+      else
+        hipLaunchKernelGGL((gemm_conv_bf16_kernel<T::BM, T::BN, DP, false>), dim3(nblk, splits), dim3(BF_THREADS), lds, st, d, w_hi, w_lo, ldw, tiles_m, tiles_n, nblk, ktps, part);
+    }
     DDPO_LAUNCH_CHECK();
+    return splits > 1 ? launch_splitk_reduce(d, part, splits, NPH, st) : DDPO_OK;
   }
-  return DDPO_OK;
 }
 
-// Tall 256x320 tiles (plane-fed path only, 8 waves of 64x160, one workgroup per CU, plain k-loop APL = 4): for layers whose tile
-// grid still covers the chip — the 64x64-latent level of the U-Net (M = 65536: 256 tiles per 320 columns).  No split-K.
-template <int APL, int NPASS = 3, bool FOLD = false>
-static int launch_bf16_tall(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, hipStream_t st) {
-  constexpr int BM = 256, BN = 320, WM = 4, WN = 2;
-  const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
-  const int nblk = tiles_m * tiles_n;
-  const int nk_total = d.K / BF_BK;
-  const size_t lds = 8 * 32 * 160 * 4;                     // epilogue slices (160 KB) > 2 stages of operand tiles (144 KB)
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
+// ---- the route of a layer: which tile, which split (runtime), then which instantiation (npass -> Datapath, tile -> k-loop)
+enum RouteTile { RT_TALL, RT_TALL_GEGLU, RT_WIDE, RT_128, RT_64 };
+struct Route { RouteTile tile; int splits; };
+
+template <bool PLANES, bool FOLD, Datapath DP>
+static int launch_route(const Route& r, const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, float* ws, hipStream_t st) {
+  constexpr KLoop KL = PLANES ? KLoop::planes3w : KLoop::regs;
+  constexpr KLoop KT = !PLANES ? KLoop::regs : (DP == Datapath::bf16x3 ? KLoop::tall : (DP == Datapath::f16mx ? KLoop::tall_mx : KLoop::tall_ring));
+  switch (r.tile) {
+    case RT_TALL: return launch_tile<TileTall, DP, KT, FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
+    case RT_TALL_GEGLU: return launch_tile<TileTall, DP, PLANES && DP == Datapath::bf16x3 ? KLoop::tall_geglu : KLoop::regs, FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
+    case RT_WIDE: return launch_tile<TileWide, DP, KL, FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
+    case RT_128: return launch_tile<Tile128x128, DP, KL, FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
+    default: return launch_tile<Tile128x64, DP, KL, FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
   }
-  count_tile(TC_TALL);
-  hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, NPASS, 0, WM, WN, true, APL, FOLD>), dim3(nblk, 1, FOLD ? 4 : 1), dim3(64 * WM * WN), lds, st, d, w_hi, w_lo, ldw,
-                     tiles_m, tiles_n, nblk, nk_total, (float*)nullptr);
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
+}
+template <bool PLANES, bool FOLD>
+static int launch_npass(int npass, const Route& r, const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, float* ws, hipStream_t st) {
+  switch (npass) {
+    case 1: return launch_route<PLANES, FOLD, Datapath::bf16x1>(r, d, w_hi, w_lo, ldw, ws, st);
+    case 3: return launch_route<PLANES, FOLD, Datapath::bf16x3>(r, d, w_hi, w_lo, ldw, ws, st);
+    case 4: return launch_route<PLANES, FOLD, Datapath::f16mx>(r, d, w_hi, w_lo, ldw, ws, st);
+    case 5: return launch_route<PLANES, FOLD, Datapath::f16x1>(r, d, w_hi, w_lo, ldw, ws, st);
+    default: return DDPO_EINVAL;
+  }
 }
 
-// f16mx on the tall tile: eight waves of 64x160 (APL = 7), 144 KB of operand stages, no split-K (launched only where the grid fills the chip).
-template <bool FOLD = false>
-static int launch_mx_tall(const ddpo_gemm_desc& d, const uint16_t* w16, const uint16_t* w8, hipStream_t st) {
-  constexpr int BM = 256, BN = 320, WM = 4, WN = 2;
-  const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
-  const int nblk = tiles_m * tiles_n;
-  const int nk_total = d.K / BF_BK;
-  const size_t lds = 8 * 32 * 160 * 4;                      // the output stage's slices (160 KB) > two stages of [A16 | A8 | W16 | W8] (144 KB)
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_conv_bf16_buf_kernel<BM, BN, 4, 0, WM, WN, true, 7, FOLD>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  count_tile(TC_TALL);
-  count_tile(TC_MX);
-  hipLaunchKernelGGL((gemm_conv_bf16_buf_kernel<BM, BN, 4, 0, WM, WN, true, 7, FOLD>), dim3(nblk, 1, FOLD ? 4 : 1), dim3(64 * WM * WN), lds, st, d, w16, w8, 0,
-                     tiles_m, tiles_n, nblk, nk_total, (float*)nullptr);
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
-}
-
-// Tile-shape / split-K selection shared by the fp32-fed and the plane-fed entry points: the SAME rules, so both produce
-// bit-identical results for the same layer (APL is only instantiated for npass == 3).
-// FOLD (APL = 3 only; npass 3 / 4 / 1): the same rules on the tile counts of all four phases of a folded up-sampler.
-template <int APL, bool FOLD = false>
+// Tile-shape / split-K selection shared by the fp32-fed (PLANES = false: npass 1 / 3) and the plane-fed entry points (npass 1 / 3 / 4 / 5): the
+// SAME rules, so both produce bit-identical results for the same layer.
+// FOLD (plane-fed; npass 1 / 3 / 4): the same rules on the tile counts of all four phases of a folded up-sampler.
+template <bool PLANES, bool FOLD = false>
 static int dispatch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, int npass, void* ws, size_t ws_bytes,
                          hipStream_t st) {
-  static_assert(!FOLD || APL == 3, "folded up-sampler phases exist on the plane-fed kernels");
+  static_assert(!FOLD || PLANES, "folded up-sampler phases exist on the plane-fed kernels");
   constexpr int NPH = FOLD ? 4 : 1;
-  if constexpr (FOLD) { if (d.epilogue != 0 || (npass != 1 && npass != 3 && npass != 4)) return DDPO_EINVAL; }
-  if constexpr (!FOLD) if (d.epilogue != 0) {       // GEGLU output stage: 128-wide tiles of the buffer-addressed kernel, vector epilogue only
+  if (FOLD && (d.epilogue != 0 || (npass != 1 && npass != 3 && npass != 4))) return DDPO_EINVAL;
+  if (d.epilogue != 0) {       // GEGLU output stage: 128-wide tiles of the buffer-addressed kernel, vector epilogue only, no split-K
     if ((d.epilogue != 1 && d.epilogue != 2) || (d.N & 127) || !buf_path_ok(d, ldw) || d.rowbias || d.residual || d.alpha != 1.0f || d.w_dgrad) return DDPO_EINVAL;
     if ((d.ld_out & 3) || (reinterpret_cast<uintptr_t>(d.out) & 15) || (d.bias && (reinterpret_cast<uintptr_t>(d.bias) & 15))) return DDPO_EINVAL;
     if (reinterpret_cast<uintptr_t>(d.aux_out) & 15) return DDPO_EINVAL;
-    if (d.epilogue == 2) {     // the tall 256 x 320 tile with value / gate wave pairs: plane-fed bf16x3 only, columns in [a (160) | gate (160)] blocks
-      if constexpr (APL == 3) {
-        if (npass != 3 || d.N % 320 || ((d.N >> 1) & 3)) return DDPO_EINVAL;
-        return launch_bf16_tall<6>(d, w_hi, w_lo, ldw, st);
-      }
-      return DDPO_EINVAL;
-    }
-    if constexpr (APL == 3) {
-      if (npass == 4) return launch_bf16<128, 128, 4, 2, 2, 3>(d, w_hi, w_lo, ldw, nullptr, 0, st);
-      if (npass == 1) return launch_bf16<128, 128, 1, 2, 2, 3>(d, w_hi, w_lo, ldw, nullptr, 0, st);
-      if (npass == 5) return launch_bf16<128, 128, 5, 2, 2, 3>(d, w_hi, w_lo, ldw, nullptr, 0, st);
-    }
-    return npass == 3 ? launch_bf16<128, 128, 3, 2, 2, APL>(d, w_hi, w_lo, ldw, nullptr, 0, st) : launch_bf16<128, 128, 1>(d, w_hi, w_lo, ldw, nullptr, 0, st);
+    // epilogue 2: the tall 256 x 320 tile with value / gate wave pairs: plane-fed bf16x3 only, columns in [a (160) | gate (160)] blocks
+    if (d.epilogue == 2 && (!PLANES || npass != 3 || d.N % 320 || ((d.N >> 1) & 3))) return DDPO_EINVAL;
+    return launch_npass<PLANES, FOLD>(npass, Route{d.epilogue == 2 ? RT_TALL_GEGLU : RT_128, 1}, d, w_hi, w_lo, ldw, nullptr, st);
   }
   float* wsf = (ws && !(reinterpret_cast<uintptr_t>(ws) & 15)) ? reinterpret_cast<float*>(ws) : nullptr;
-  constexpr int wide_mode = 1;
+  Route r;
+  // 256x320 tiles (plane-fed only) where they still give every CU a workgroup (the 64x64-latent level): 345 / 428 TF against 320 / 390 for the
+  // 128x320 tile on conv 320->320 / 960->320 (bit-identical; round-2 probe) ...
+  // ... and where their last round of 256 is not much emptier than the 128x320 grid's: 256 tall tiles (SD-1.5, 64x64 latents at batch 16)
+  // are exactly one round; 576 (SD-2.1, 96x96) are 2.25 rounds = 3 rounds of time, where 1152 wide tiles waste half a round of five.
+  // The rule is the same for every datapath: bf16x3 (KLoop::tall), single-pass bf16 / f16 (tall_ring, round 6) and f16mx (tall_mx; measured round 5,
+  // profiles/r05_probe_mx_tall.log, r05_ab_mx_tall.log: conv 320->320 @64^2 0.259 -> 0.236 ms, 960->320 0.930 -> 0.709 ms, up-conv 640->640
+  // 1.084 -> 0.878 ms, bit-identical; sampling +1.4 %.  A split-K grid of tall tiles for the 32x32 / 16x16 levels was built and measured with it:
+  // no gain over the 128x320 tile there (4.09 vs 4.09 images/s) — deleted).  DDPO_MX_TALL=0 (read per launch) keeps every f16mx layer on the
+  // 128-row tiles: the probe's and the tests' bit-identity comparison.
+  const long ntall = (long)NPH * ((d.M + 255) / 256) * (d.N / 320), nwide = (long)NPH * ((d.M + 127) / 128) * (d.N / 320);
+  const double eff_tall = (double)ntall / (double)(((ntall + 255) / 256) * 256), eff_wide = (double)nwide / (double)(((nwide + 255) / 256) * 256);
+  bool tall = PLANES && d.N % 320 == 0 && ntall >= 200 && eff_tall * 1.08 >= eff_wide;
+  if (tall && npass == 4) {
+    const char* mx_tall_env = getenv("DDPO_MX_TALL");
+    tall = !(mx_tall_env && mx_tall_env[0] == '0');
+  }
   // 128x320 tiles (one workgroup per CU) when they, times the split of the reduction, give every CU a workgroup; a
   // many-column GEMM with a very short reduction is better on 128x128 (measured: K=320, N=2560; the 160 KB epilogue image)
-  if constexpr (APL != 0) {
-    // 256x320 tiles where they still give every CU a workgroup (the 64x64-latent level): 345 / 428 TF against 320 / 390 for the
-    // 128x320 tile on conv 320->320 / 960->320 (bit-identical; round-2 probe).
-    constexpr int tall_mode = 1;
-    // ... and where their last round of 256 is not much emptier than the 128x320 grid's: 256 tall tiles (SD-1.5, 64x64 latents at batch 16)
-    // are exactly one round; 576 (SD-2.1, 96x96) are 2.25 rounds = 3 rounds of time, where 1152 wide tiles waste half a round of five
-    const long ntall = (long)NPH * ((d.M + 255) / 256) * (d.N / 320), nwide = (long)NPH * ((d.M + 127) / 128) * (d.N / 320);
-    const double eff_tall = (double)ntall / (double)(((ntall + 255) / 256) * 256), eff_wide = (double)nwide / (double)(((nwide + 255) / 256) * 256);
-    // (bf16x3 only.  An f16mx tall loop — the weight operand's ks = 1 fragments streamed per column block beside the 160 accumulators — was
-    // built twice in round 3: correct, but ~20 registers short at two waves per SIMD.  The compiler spills 44-58 values around the 8-register
-    // operands of the scaled MFMA (0 without the 8-bit weight fragments, 16 with one 8-bit activation fragment, the same 58 with the convolution
-    // bookkeeping compiled out — it is the fragments, not the addressing), and the reloads sit behind the LDS-DMA requests on the in-order
-    // vmcnt counter, so every k-tile waits for its own prefetch: 0.326 ms against 0.321 (bf16x3 tall) / 0.317 (f16mx 128x320) on conv 320->320
-    // @64^2, profiles/r03_probe_mx_tall.log.  The f16mx tall tile wants FOUR waves of 128 x 160 (one per SIMD, accumulators in AGPRs).)
-    if (tall_mode && npass == 3 && d.N % 320 == 0 && d.epilogue == 0 && ntall >= 200 && eff_tall * 1.08 >= eff_wide)
-      return launch_bf16_tall<5, 3, FOLD>(d, w_hi, w_lo, ldw, st);
-    if constexpr (APL == 3) {
-      // single-pass bf16, plane-fed (round 6): the tall tile with the four-stage ring (APL = 8) under the same rule
-      if (npass == 1 && d.N % 320 == 0 && d.epilogue == 0 && ntall >= 200 && eff_tall * 1.08 >= eff_wide)
-        return launch_bf16_tall<8, 1, FOLD>(d, w_hi, w_lo, ldw, st);
-      if constexpr (!FOLD)
-        if (npass == 5 && d.N % 320 == 0 && d.epilogue == 0 && ntall >= 200 && eff_tall * 1.08 >= eff_wide)
-          return launch_bf16_tall<8, 5>(d, w_hi, w_lo, ldw, st);
-      // f16mx layers on the tall tile (APL = 7) under the bf16x3 tall tile's rule: grids that fill whole rounds of the chip unsplit — the 64x64
-      // level at batch 16 and the up-sampled 32x32 -> 64x64 convolution.  Measured round 5 (profiles/r05_probe_mx_tall.log, r05_ab_mx_tall.log):
-      // conv 320->320 @64^2 0.259 -> 0.236 ms, 960->320 0.930 -> 0.709 ms, up-conv 640->640 1.084 -> 0.878 ms, bit-identical; sampling +1.4 %.
-      // A split-K grid of tall tiles for the 32x32 / 16x16 levels (128 / 64 tiles x 2 / 4 splits) was built and measured with it: no gain over
-      // the 128x320 tile there (4.09 vs 4.09 images/s) — deleted.  DDPO_MX_TALL=0 (read per launch) keeps every f16mx layer on the 128-row tiles:
-      // the probe's and the tests' bit-identity comparison.
-      const char* mx_tall_env = getenv("DDPO_MX_TALL");
-      if (npass == 4 && !(mx_tall_env && mx_tall_env[0] == '0') && d.N % 320 == 0 && d.epilogue == 0 && ntall >= 200 && eff_tall * 1.08 >= eff_wide)
-        return launch_mx_tall<FOLD>(d, w_hi, w_lo, st);
-    }
-  }
   const int wsplits = wide_splits(d, wsf != nullptr, ws_bytes, NPH);
-  if (wide_mode && d.N % 320 == 0 && (long)NPH * d.M >= 512 && buf_path_ok(d, ldw) && !(d.K / BF_BK < 16 && d.N > 1280) &&
-      (long)NPH * ((d.M + 127) / 128) * (d.N / 320) * wsplits >= 200 &&
-      !(wsplits > 1 && d.K / BF_BK < 64)) {     // a split short reduction only adds the reduce pass (measured equal to 128x128 unsplit)
-    if constexpr (APL == 3) {
-      if (npass == 4) return launch_bf16_wide<4, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-      if (npass == 1) return launch_bf16_wide<1, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-      if constexpr (!FOLD) if (npass == 5) return launch_bf16_wide<5, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-    }
-    if constexpr (FOLD) return launch_bf16_wide<3, APL, true>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-    else return npass == 3 ? launch_bf16_wide<3, APL>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16_wide<1>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-  }
-  const long t128 = (long)NPH * ((d.M + 127) / 128) * ((d.N + 127) / 128);
-  constexpr long big_min = 256;
-  // 128x128 tiles need >= 512 of them to fill both workgroup slots of every CU; a short reduction on 256..511 of them (the 16x16
-  // level's q / k / v / out projections: M = 4096, N = K = 1280 -> 320 tiles) runs ~15 % faster on 640 tiles of 128x64, three per CU
-  // (probe, cold weights: 0.084 -> 0.070 ms fp32-fed; profiles/r02_probe_tiles_small.log).
-  constexpr int mid64 = 1;
-  const bool mid_short = mid64 && t128 < 512 && d.K / BF_BK <= 64;
-  const bool big = (d.N % 128 == 0) && t128 >= big_min && !mid_short;
-  if constexpr (APL == 3) {
-    if (npass == 4)
-      return big ? launch_bf16<128, 128, 4, 2, 2, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 4, 2, 2, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-    if (npass == 1)
-      return big ? launch_bf16<128, 128, 1, 2, 2, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 1, 2, 2, 3, FOLD>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-    if constexpr (!FOLD)
-      if (npass == 5)
-        return big ? launch_bf16<128, 128, 5, 2, 2, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 5, 2, 2, 3>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-  }
-  if constexpr (FOLD) {
-    return big ? launch_bf16<128, 128, 3, 2, 2, APL, true>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 3, 2, 2, APL, true>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+  if (tall) {
+    r = Route{RT_TALL, 1};
+  } else if (d.N % 320 == 0 && (long)NPH * d.M >= 512 && buf_path_ok(d, ldw) && !(d.K / BF_BK < 16 && d.N > 1280) &&
+             (long)NPH * ((d.M + 127) / 128) * (d.N / 320) * wsplits >= 200 &&
+             !(wsplits > 1 && d.K / BF_BK < 64)) {     // a split short reduction only adds the reduce pass (measured equal to 128x128 unsplit)
+    r = Route{RT_WIDE, wsplits};
   } else {
-    if (npass == 3)
-      return big ? launch_bf16<128, 128, 3, 2, 2, APL>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 3, 2, 2, APL>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
-    return big ? launch_bf16<128, 128, 1>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st) : launch_bf16<128, 64, 1>(d, w_hi, w_lo, ldw, wsf, ws_bytes, st);
+    // 128x128 tiles need >= 512 of them to fill both workgroup slots of every CU; a short reduction on 256..511 of them (the 16x16
+    // level's q / k / v / out projections: M = 4096, N = K = 1280 -> 320 tiles) runs ~15 % faster on 640 tiles of 128x64, three per CU
+    // (probe, cold weights: 0.084 -> 0.070 ms fp32-fed; profiles/r02_probe_tiles_small.log).
+    const long t128 = (long)NPH * ((d.M + 127) / 128) * ((d.N + 127) / 128);
+    const bool mid_short = t128 < 512 && d.K / BF_BK <= 64;
+    const bool big = (d.N % 128 == 0) && t128 >= 256 && !mid_short;
+    const int ngrid = NPH * ((d.M + 127) / 128) * ((d.N + (big ? 127 : 63)) / (big ? 128 : 64));
+    r = Route{big ? RT_128 : RT_64, splits_128(d, ngrid, wsf != nullptr, ws_bytes, NPH)};
   }
+  return launch_npass<PLANES, FOLD>(npass, r, d, w_hi, w_lo, ldw, wsf, st);
+}
+
+// geometry rules common to the three GEMM entry points (the folded up-sampler builds its own geometry)
+static bool conv_geometry_ok(const ddpo_gemm_desc& d) {
+  if (d.M <= 0 || d.N <= 0 || d.K <= 0 || !planes_out_ok(d) || !res_rows_ok(d)) return false;
+  if (d.ksize > 0) {
+    if (d.ksize != 1 && d.ksize != 3) return false;
+    if (d.K != d.ksize * d.ksize * d.Cin || d.M != d.B * d.OH * d.OW || d.upsample < 0 || d.upsample > 2) return false;
+  }
+  return true;
 }
 
 extern "C" int ddpo_gemm_conv_fwd_bf16(const ddpo_gemm_desc* dp, const uint16_t* w_hi, const uint16_t* w_lo, int ldw, int npass,
@@ -1798,84 +1747,64 @@ extern "C" int ddpo_gemm_conv_fwd_bf16(const ddpo_gemm_desc* dp, const uint16_t*
   const ddpo_gemm_desc& d = *dp;
   if (npass != 1 && npass != 3) return DDPO_EINVAL;
   if (npass == 3 && !w_lo) return DDPO_EINVAL;
-  if (!d.src || d.M <= 0 || d.N <= 0 || d.K <= 0 || d.ld_src <= 0 || (d.ld_src & 3) || (reinterpret_cast<uintptr_t>(d.src) & 15)) return DDPO_EINVAL;
+  if (!d.src || d.ld_src <= 0 || (d.ld_src & 3) || (reinterpret_cast<uintptr_t>(d.src) & 15)) return DDPO_EINVAL;
   if ((reinterpret_cast<uintptr_t>(w_hi) & 15) || (w_lo && (reinterpret_cast<uintptr_t>(w_lo) & 15))) return DDPO_EINVAL;
-  if (!planes_out_ok(d) || !res_rows_ok(d) || (d.out_hi && !buf_path_ok(d, ldw))) return DDPO_EINVAL;
-  if (d.ksize > 0) {
-    if (d.ksize != 1 && d.ksize != 3) return DDPO_EINVAL;
-    if ((d.Cin & 7) || d.K != d.ksize * d.ksize * d.Cin || d.M != d.B * d.OH * d.OW) return DDPO_EINVAL;
-    if (d.upsample < 0 || d.upsample > 2) return DDPO_EINVAL;
-  } else if (d.K & 7) {
-    return DDPO_EINVAL;
-  }
+  if (!conv_geometry_ok(d) || (d.out_hi && !buf_path_ok(d, ldw))) return DDPO_EINVAL;      // only the buffer-addressed kernels (and the split-K reduce) write planes
+  if ((d.ksize > 0 ? d.Cin : d.K) & 7) return DDPO_EINVAL;
   if (d.w_layout != 0 && (d.w_layout != 1 || d.w_dgrad)) return DDPO_EINVAL;
   if (d.w_dgrad) {
-    if (d.ksize <= 0 || (d.Cin & 7)) return DDPO_EINVAL;       // W planes in forward [K][N] order; co chunks of 8 stay inside a tap
+    if (d.ksize <= 0) return DDPO_EINVAL;       // W planes in forward [K][N] order; co chunks of 8 stay inside a tap (Cin % 8 above)
   } else if (d.w_layout == 0 && (ldw < d.K || (ldw & 7))) {
     return DDPO_EINVAL;
   }
-  return dispatch_bf16<0>(d, w_hi, w_lo, ldw, npass, ws, ws_bytes, as_stream(stream));
+  return dispatch_bf16<false>(d, w_hi, w_lo, ldw, npass, ws, ws_bytes, as_stream(stream));
 }
 
-/* Plane-fed variant: the activation operand comes as bf16 hi / lo planes (see the APL note on gemm_conv_bf16_buf_kernel). */
-extern "C" int ddpo_gemm_conv_fwd_bf16_planes(const ddpo_gemm_desc* dp, const uint16_t* a_hi, const uint16_t* a_lo, int lda,
-                                              const uint16_t* w_hi, const uint16_t* w_lo, int ldw, void* ws, size_t ws_bytes,
-                                              void* stream) {
-  if (!dp || !a_hi || !w_hi || (a_lo == nullptr) != (w_lo == nullptr)) return DDPO_EINVAL;
-  const int npass = a_lo ? 3 : 1;          // ABI v14: BOTH lo planes NULL = single-pass bf16 (a_hi * w_hi only: XLA's TPU default precision)
-  ddpo_gemm_desc d = *dp;
-  if (d.M <= 0 || d.N <= 0 || d.K <= 0 || lda < 0 || (lda & 7) || d.w_dgrad || !planes_out_ok(d) || !res_rows_ok(d)) return DDPO_EINVAL;      // lda == 0: k-blocked planes
-  if (npass == 1 && d.epilogue == 2) return DDPO_EINVAL;      // the tall GEGLU tile exists on the three-pass datapath only
-  if ((reinterpret_cast<uintptr_t>(a_hi) | reinterpret_cast<uintptr_t>(a_lo) | reinterpret_cast<uintptr_t>(w_hi) |
-       reinterpret_cast<uintptr_t>(w_lo)) & 15) return DDPO_EINVAL;
-  if (d.w_layout != 0 && d.w_layout != 1) return DDPO_EINVAL;
-  if (d.w_layout == 0 && (ldw < d.K || (ldw & 7))) return DDPO_EINVAL;
-  if (d.ksize > 0) {
-    if (d.ksize != 1 && d.ksize != 3) return DDPO_EINVAL;
-    if (d.K != d.ksize * d.ksize * d.Cin || d.M != d.B * d.OH * d.OW || d.upsample < 0 || d.upsample > 2 || (lda && lda < d.Cin)) return DDPO_EINVAL;
-  } else if (lda && lda < d.K) {
-    return DDPO_EINVAL;
-  }
-  d.src = reinterpret_cast<const float*>(a_hi);      // the kernel reads d.src / d.w as the two planes and d.ld_src in elements
-  d.w = reinterpret_cast<const float*>(a_lo);
+// What the three plane-fed entry points share, on a descriptor whose geometry (ksize, Cin / K) is final: both operands come as a first plane with or
+// without a second one, 16-byte aligned; the activation planes' row stride `lda` (elements; 0 = k-blocked) is a multiple of `lda_mult` (a power of
+// two) and covers the reduction channels.  Then the kernel's view of the operands — d.src / d.w are the two activation planes, d.ld_src their row
+// stride in ELEMENTS — which must be buffer-addressable (Cin or K % 32 == 0, 31-bit byte offsets: callers keep other layers on the fp32-fed entry).
+static bool plane_operands_ok(ddpo_gemm_desc& d, const uint16_t* a0, const uint16_t* a1, int lda, int lda_mult, const uint16_t* w0, const uint16_t* w1, int ldw) {
+  if (!a0 || !w0 || (a1 == nullptr) != (w1 == nullptr)) return false;
+  if ((reinterpret_cast<uintptr_t>(a0) | reinterpret_cast<uintptr_t>(a1) | reinterpret_cast<uintptr_t>(w0) | reinterpret_cast<uintptr_t>(w1)) & 15) return false;
+  if (lda < 0 || (lda & (lda_mult - 1)) || (lda && lda < (d.ksize > 0 ? d.Cin : d.K))) return false;
+  d.src = reinterpret_cast<const float*>(a0);
+  d.w = reinterpret_cast<const float*>(a1);
   d.ld_src = lda;
-  if (!buf_path_ok(d, ldw)) return DDPO_EINVAL;      // Cin (K) % 32 == 0 and 31-bit byte offsets: callers keep such layers on the fp32-fed entry
   // k-loop of the 128-row tiles: weights three LDS stages deep (requested two k-tiles ahead, counted vmcnt), activations two; the upper half
   // of the waves requests its pieces half a k-tile later than the lower half (d.splits bit 0), so the two waves of a SIMD alternate between
   // DMA issue and MFMAs.  Measured and removed (rounds 1-3): the plain wait / barrier / request / compute loop, two weight stages, no stagger,
   // s_setprio around the MFMA clusters, four-wave 128x320 and 128x160 tiles, requests spread one per accumulator block (profiles/r03_probe_kloop.log).
   d.splits = 1;                                      // `splits` is a wgrad-only field: the forward kernel reads bit 0 as the stagger flag
-#ifdef DDPO_KLOOP_TIMING
-  { const char* e = getenv("DDPO_DBG_ABL"); if (e) d.splits |= atoi(e) << 4; }
-#endif
-  return dispatch_bf16<3>(d, w_hi, w_lo, ldw, npass, ws, ws_bytes, as_stream(stream));
+  return buf_path_ok(d, ldw);
 }
 
-/* f16mx plane-fed variant (include/ddpo_hip.h): same kernel family, NPASS = 4 */
+/* Plane-fed variant: the activation operand comes as bf16 hi / lo planes (see the plane-fed note on gemm_conv_bf16_buf_kernel). */
+extern "C" int ddpo_gemm_conv_fwd_bf16_planes(const ddpo_gemm_desc* dp, const uint16_t* a_hi, const uint16_t* a_lo, int lda,
+                                              const uint16_t* w_hi, const uint16_t* w_lo, int ldw, void* ws, size_t ws_bytes,
+                                              void* stream) {
+  if (!dp) return DDPO_EINVAL;
+  const int npass = a_lo ? 3 : 1;          // ABI v14: BOTH lo planes NULL = single-pass bf16 (a_hi * w_hi only: XLA's TPU default precision)
+  ddpo_gemm_desc d = *dp;
+  if (!conv_geometry_ok(d) || d.w_dgrad || (d.w_layout != 0 && d.w_layout != 1)) return DDPO_EINVAL;
+  if (d.w_layout == 0 && (ldw < d.K || (ldw & 7))) return DDPO_EINVAL;
+  if (npass == 1 && d.epilogue == 2) return DDPO_EINVAL;      // the tall GEGLU tile exists on the three-pass datapath only
+  if (!plane_operands_ok(d, a_hi, a_lo, lda, 8, w_hi, w_lo, ldw)) return DDPO_EINVAL;
+  dbg_abl_from_env(d);
+  return dispatch_bf16<true>(d, w_hi, w_lo, ldw, npass, ws, ws_bytes, as_stream(stream));
+}
+
+/* f16mx plane-fed variant (include/ddpo_hip.h): same kernel family, Datapath::f16mx */
 extern "C" int ddpo_gemm_conv_fwd_f16mx_planes(const ddpo_gemm_desc* dp, const uint16_t* a16, const uint16_t* a8, int lda,
                                                const uint16_t* w16, const uint16_t* w8, void* ws, size_t ws_bytes, void* stream) {
-  if (!dp || !a16 || !w16 || (a8 == nullptr) != (w8 == nullptr) || (a8 && !dp->w_scale)) return DDPO_EINVAL;
+  if (!dp || (a8 && !dp->w_scale)) return DDPO_EINVAL;
   const int npass = a8 ? 4 : 5;            // ABI v14: BOTH 8-bit planes NULL = single-pass f16 (a_h * w_h only: the operator without its cross terms; opt-in)
   ddpo_gemm_desc d = *dp;
+  if (!conv_geometry_ok(d) || d.w_dgrad || d.w_layout != 1) return DDPO_EINVAL;
   if (npass == 5 && d.epilogue == 2) return DDPO_EINVAL;
-  if (d.M <= 0 || d.N <= 0 || d.K <= 0 || lda < 0 || (lda & 31) || d.w_dgrad || d.w_layout != 1 || !planes_out_ok(d) || !res_rows_ok(d)) return DDPO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(a16) | reinterpret_cast<uintptr_t>(a8) | reinterpret_cast<uintptr_t>(w16) | reinterpret_cast<uintptr_t>(w8)) & 15)
-    return DDPO_EINVAL;
-  if (d.ksize > 0) {
-    if (d.ksize != 1 && d.ksize != 3) return DDPO_EINVAL;
-    if (d.K != d.ksize * d.ksize * d.Cin || d.M != d.B * d.OH * d.OW || d.upsample < 0 || d.upsample > 2 || (lda && lda < d.Cin)) return DDPO_EINVAL;
-  } else if (lda && lda < d.K) {
-    return DDPO_EINVAL;
-  }
-  d.src = reinterpret_cast<const float*>(a16);
-  d.w = reinterpret_cast<const float*>(a8);
-  d.ld_src = lda;
-  if (!buf_path_ok(d, 0)) return DDPO_EINVAL;
-  d.splits = 1;
-#ifdef DDPO_KLOOP_TIMING
-  { const char* e = getenv("DDPO_DBG_ABL"); if (e) d.splits |= atoi(e) << 4; }
-#endif
-  return dispatch_bf16<3>(d, w16, w8, 0, npass, ws, ws_bytes, as_stream(stream));
+  if (!plane_operands_ok(d, a16, a8, lda, 32, w16, w8, 0)) return DDPO_EINVAL;
+  dbg_abl_from_env(d);
+  return dispatch_bf16<true>(d, w16, w8, 0, npass, ws, ws_bytes, as_stream(stream));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1883,962 +1812,27 @@ extern "C" int ddpo_gemm_conv_fwd_f16mx_planes(const ddpo_gemm_desc* dp, const u
 // source pixel (y, x) read a 2x2 neighbourhood of the SOURCE image only, because neighbouring taps of the 3x3 kernel land on the same source
 // pixel: per axis, phase 0 reads offsets {-1, 0} with taps {w[0], w[1] + w[2]}, phase 1 offsets {0, +1} with taps {w[0] + w[1], w[2]} (the zero
 // padding of the virtual image at rows -1 / 2H coincides with source rows -1 / H).  So the layer is four stride-1 2x2 convolutions on the source
-// grid with pre-summed kernels — reduction length 4 Cin instead of 9 Cin — each writing one quarter of the output rows (fold_row).  All four
-// phases run as blockIdx.z of ONE launch of the FOLD instantiation of the plane-fed kernel, chosen by dispatch_bf16<3, true>: the tile and
-// split-K rules of every other layer, applied to a tile grid four times the source grid's.
+// grid with pre-summed kernels (ddpo_fold_up2x_weights, gemm_bf16_pack.hip) — reduction length 4 Cin instead of 9 Cin — each writing one quarter of
+// the output rows (fold_row).  All four phases run as blockIdx.z of ONE launch of the FOLD instantiation of the plane-fed kernel, chosen by
+// dispatch_bf16<true, true>: the tile and split-K rules of every other layer, applied to a tile grid four times the source grid's.
 // ------------------------------------------------------------------------------------------------
 extern "C" int ddpo_conv_up2x_folded_fwd(const ddpo_gemm_desc* dp, const uint16_t* a_hi, const uint16_t* a_lo, int lda, const uint16_t* w_hi,
                                          const uint16_t* w_lo, int f16mx, void* ws, size_t ws_bytes, void* stream) {
-  if (!dp || !a_hi || !w_hi || (a_lo == nullptr) != (w_lo == nullptr)) return DDPO_EINVAL;
+  if (!dp) return DDPO_EINVAL;
   if (f16mx && (!a_lo || !dp->w_scale)) return DDPO_EINVAL;
   const int npass = f16mx ? 4 : (a_lo ? 3 : 1);
   ddpo_gemm_desc d = *dp;
   if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.Cin <= 0 || d.N <= 0 || (d.Cin % BF_BK) || (d.N & 3)) return DDPO_EINVAL;
   if ((int64_t)d.B * d.H * d.W * 4 > 0x7FFFFFFF || (int64_t)d.Cin * 4 > 0x7FFFFFFF) return DDPO_EINVAL;      // output rows and K are 32-bit
-  if (lda < 0 || (lda & (f16mx ? 31 : 7)) || (lda && lda < d.Cin)) return DDPO_EINVAL;
   if (!d.out || d.out_hi || d.out_lo || d.rowbias || d.residual || d.res_rows || d.epilogue || d.w_dgrad || d.aux_out) return DDPO_EINVAL;
   if (d.ld_out < d.N || (d.ld_out & 3) || (reinterpret_cast<uintptr_t>(d.out) & 15) || (d.bias && (reinterpret_cast<uintptr_t>(d.bias) & 15))) return DDPO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(a_hi) | reinterpret_cast<uintptr_t>(a_lo) | reinterpret_cast<uintptr_t>(w_hi) | reinterpret_cast<uintptr_t>(w_lo)) & 15)
-    return DDPO_EINVAL;
   // the geometry of ONE phase, as the kernel reads it: a 2x2 stride-1 convolution on the source grid
   d.M = d.B * d.H * d.W; d.K = 4 * d.Cin;             // (both checked above to fit)
   d.alpha = 1.0f;                                     // the layer has no scale: whatever the caller left in the field is not applied
   d.OH = d.H; d.OW = d.W;
   d.ksize = 2; d.stride = 1; d.pad = 1; d.upsample = 3;
   d.w_layout = 1; d.planes_fmt = 0; d.ld_planes = 0;
-  d.src = reinterpret_cast<const float*>(a_hi);
-  d.w = reinterpret_cast<const float*>(a_lo);
-  d.ld_src = lda;
   if (!f16mx) d.w_scale = nullptr;
-  if (!buf_path_ok(d, 0) || (int64_t)4 * d.K * d.N * 2 >= 0x7FFFFFFF) return DDPO_EINVAL;
-  d.splits = 1;                                      // (the stagger flag of the plane-fed k-loops, as in ddpo_gemm_conv_fwd_bf16_planes)
-  return dispatch_bf16<3, true>(d, w_hi, w_lo, 0, npass, ws, ws_bytes, as_stream(stream));
-}
-
-// The four phase kernels (2, 2, Cin, Cout) of a 3x3 HWIO kernel w (3, 3, Cin, Cout): wf[(py 2 + px)][ty][tx] = the sum, in fp32, ky then kx
-// ascending, of w[ky][kx] over the taps that land on source offset (ty - 1 + py, tx - 1 + px).  cn = Cin * Cout.
-__global__ void __launch_bounds__(256) fold_up2x_weights_kernel(const float* __restrict__ w, int64_t cn, float* __restrict__ wf) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= cn) return;
-  float v[3][3];
-#pragma unroll
-  for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) v[ky][kx] = w[(ky * 3 + kx) * cn + i];
-#pragma unroll
-  for (int ph = 0; ph < 4; ++ph)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int py = ph >> 1, px = ph & 1, ty = t >> 1, tx = t & 1;
-      const int y0 = py ? (ty ? 2 : 0) : (ty ? 1 : 0), y1 = py ? (ty ? 2 : 1) : (ty ? 2 : 0);
-      const int x0 = px ? (tx ? 2 : 0) : (tx ? 1 : 0), x1 = px ? (tx ? 2 : 1) : (tx ? 2 : 0);
-      float sum = 0.f;
-      bool first = true;
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          if (ky < y0 || ky > y1 || kx < x0 || kx > x1) continue;
-          sum = first ? v[ky][kx] : sum + v[ky][kx];
-          first = false;
-        }
-      wf[(ph * 4 + t) * cn + i] = sum;
-    }
-}
-extern "C" int ddpo_fold_up2x_weights(const float* w, int Cin, int Cout, float* wf, void* stream) {
-  if (!w || !wf || Cin <= 0 || Cout <= 0) return DDPO_EINVAL;
-  const int64_t cn = (int64_t)Cin * Cout;
-  hipLaunchKernelGGL(fold_up2x_weights_kernel, dim3((unsigned)((cn + 255) / 256)), dim3(256), 0, as_stream(stream), w, cn, wf);
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// weight packing: fp32 W[K][N] -> bf16 hi/lo planes, forward order [N][Kp] (k contiguous, Kp = K rounded up to 8,
-// pad zero) and backward order [K][N] (the original order).  32x32 LDS-tiled transpose.
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) pack_weights_kernel(const float* __restrict__ w, int K, int N, int Kp,
-                                                           uint16_t* __restrict__ fwd_hi, uint16_t* __restrict__ fwd_lo,
-                                                           uint16_t* __restrict__ bwd_hi, uint16_t* __restrict__ bwd_lo) {
-  __shared__ uint32_t tile[32][33];      // hi | lo<<16
-  const int k0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int r = ty; r < 32; r += 8) {
-    const int k = k0 + r, n = n0 + tx;
-    uint32_t packed = 0;
-    if (k < K && n < N) {
-      const float x = w[(int64_t)k * N + n];
-      const uint32_t h = cvt_pk_bf16(x, 0.f) & 0xFFFFu;
-      const float rem = x - __uint_as_float(h << 16);
-      const uint32_t l = cvt_pk_bf16(rem, 0.f) & 0xFFFFu;
-      packed = h | (l << 16);
-      if (bwd_hi) { bwd_hi[(int64_t)k * N + n] = (uint16_t)h; bwd_lo[(int64_t)k * N + n] = (uint16_t)l; }
-    }
-    tile[r][tx] = packed;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int n = n0 + r, k = k0 + tx;
-    if (n < N && k < Kp) {
-      const uint32_t p = tile[tx][r];
-      fwd_hi[(int64_t)n * Kp + k] = (uint16_t)(p & 0xFFFFu);
-      fwd_lo[(int64_t)n * Kp + k] = (uint16_t)(p >> 16);
-    }
-  }
-}
-
-// k-blocked forward planes (Kb = ceil(K / 32), N, 32): same 32x32 tile transpose, the tile of k-block kb lands at [kb][n0 .. n0+31][0..31]
-__global__ void __launch_bounds__(256) pack_weights_kblocked_kernel(const float* __restrict__ w, int K, int N, uint16_t* __restrict__ fwd_hi,
-                                                                    uint16_t* __restrict__ fwd_lo) {
-  __shared__ uint32_t tile[32][33];
-  const int kb = blockIdx.y, k0 = kb * 32, n0 = blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int r = ty; r < 32; r += 8) {
-    const int k = k0 + r, n = n0 + tx;
-    uint32_t packed = 0;
-    if (k < K && n < N) {
-      const float x = w[(int64_t)k * N + n];
-      const uint32_t h = cvt_pk_bf16(x, 0.f) & 0xFFFFu;
-      const float rem = x - __uint_as_float(h << 16);
-      packed = h | ((cvt_pk_bf16(rem, 0.f) & 0xFFFFu) << 16);
-    }
-    tile[r][tx] = packed;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int n = n0 + r;
-    if (n < N) {
-      const uint32_t p = tile[tx][r];
-      const int64_t o = ((int64_t)kb * N + n) * 32 + tx;
-      fwd_hi[o] = (uint16_t)(p & 0xFFFFu);
-      fwd_lo[o] = (uint16_t)(p >> 16);
-    }
-  }
-}
-
-extern "C" int ddpo_pack_weights_bf16_kblocked(const float* w, int K, int N, uint16_t* fwd_hi, uint16_t* fwd_lo, void* stream) {
-  if (!w || !fwd_hi || !fwd_lo || K <= 0 || N <= 0) return DDPO_EINVAL;
-  dim3 grid((N + 31) / 32, (K + 31) / 32);
-  hipLaunchKernelGGL(pack_weights_kblocked_kernel, grid, dim3(256), 0, as_stream(stream), w, K, N, fwd_hi, fwd_lo);
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
-}
-
-// Data-gradient planes straight from the forward kernel w (taps, Cin, Cout) (HWIO flattened; dense: taps = 1): the forward-style operand of
-// dX = dY * W' is W'[k'][n'] = w[taps - 1 - tap'][n'][co] with k' = tap' * Cout + co (taps flipped, channels transposed), K' = taps * Cout rows,
-// N' = Cin columns.  For a fixed column n' consecutive k' are consecutive co: the reads are contiguous along the same index the k-blocked
-// layout stores contiguously, so no LDS transpose is needed (one thread per element: lanes along k').  Replaces the flip / permute /
-// contiguous copy torch made of every contraction weight after every optimizer update.
-__global__ void __launch_bounds__(256) pack_weights_kblocked_dgrad_kernel(const float* __restrict__ w, int taps, int Cin, int Cout,
-                                                                          uint16_t* __restrict__ hi, uint16_t* __restrict__ lo) {
-  const int kb = blockIdx.y, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int Kd = taps * Cout;
-  const int k = kb * 32 + tx;
-  const bool kok = k < Kd;
-  const int tap = kok ? k / Cout : 0, co = k - tap * Cout;
-  const float* src = w + ((int64_t)(taps - 1 - tap) * Cin) * Cout + co;
-  for (int r = ty; r < 32; r += 8) {
-    const int n = blockIdx.x * 32 + r;
-    if (n >= Cin) continue;
-    uint32_t h = 0, l = 0;
-    if (kok) {
-      const float x = src[(int64_t)n * Cout];
-      h = cvt_pk_bf16(x, 0.f) & 0xFFFFu;
-      l = cvt_pk_bf16(x - __uint_as_float(h << 16), 0.f) & 0xFFFFu;
-    }
-    const int64_t o = ((int64_t)kb * Cin + n) * 32 + tx;
-    hi[o] = (uint16_t)h;
-    lo[o] = (uint16_t)l;
-  }
-}
-extern "C" int ddpo_pack_weights_bf16_kblocked_dgrad(const float* w, int taps, int Cin, int Cout, uint16_t* hi, uint16_t* lo, void* stream) {
-  if (!w || !hi || !lo || taps <= 0 || Cin <= 0 || Cout <= 0) return DDPO_EINVAL;
-  dim3 grid((Cin + 31) / 32, (taps * Cout + 31) / 32);
-  hipLaunchKernelGGL(pack_weights_kblocked_dgrad_kernel, grid, dim3(256), 0, as_stream(stream), w, taps, Cin, Cout, hi, lo);
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
-}
-
-extern "C" int ddpo_pack_weights_bf16(const float* w, int K, int N, int Kp, uint16_t* fwd_hi, uint16_t* fwd_lo, uint16_t* bwd_hi,
-                                      uint16_t* bwd_lo, void* stream) {
-  if (!w || !fwd_hi || !fwd_lo || K <= 0 || N <= 0 || Kp < K || (Kp & 7) || (bwd_hi && !bwd_lo)) return DDPO_EINVAL;
-  dim3 grid((N + 31) / 32, (Kp + 31) / 32);
-  hipLaunchKernelGGL(pack_weights_kernel, grid, dim3(256), 0, as_stream(stream), w, K, N, Kp, fwd_hi, fwd_lo, bwd_hi, bwd_lo);
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// fp32 activations (rows, cols) with row stride ldx -> bf16 hi / lo planes (rows, ld_out): the operand format of
-// ddpo_gemm_conv_fwd_bf16_planes.  Stand-alone form of what the normalisation kernels do in their output stage
-// (same v_cvt_pk_bf16_f32 split as the GEMM loader: the planes hold exactly the bits the loader would have produced).
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) split_planes_kernel(const float* __restrict__ x, int ldx, uint16_t* __restrict__ hi,
-                                                           uint16_t* __restrict__ lo, int ld_out, int64_t rows, int cols4) {
-  const int64_t total = rows * cols4;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / cols4;
-    const int c = (int)(i - r * cols4) << 2;
-    uint2 h, l;
-    split4(*reinterpret_cast<const float4*>(x + r * ldx + c), h, l);
-    const int64_t o = plane_off(r, c, ld_out, rows);
-    *reinterpret_cast<uint2*>(hi + o) = h;
-    *reinterpret_cast<uint2*>(lo + o) = l;
-  }
-}
-
-extern "C" int ddpo_split_planes_bf16(const float* x, int ldx, uint16_t* hi, uint16_t* lo, int ld_out, int64_t rows, int cols, void* stream) {
-  if (!x || !hi || !lo || rows <= 0 || cols <= 0 || (cols & 3) || (ldx & 3) || (ld_out & 3) || ldx < cols) return DDPO_EINVAL;
-  if (ld_out == 0 ? (cols & 31) != 0 : ld_out < cols) return DDPO_EINVAL;          // ld_out == 0: k-blocked planes (cols / 32, rows, 32)
-  if ((reinterpret_cast<uintptr_t>(x) & 15) || ((reinterpret_cast<uintptr_t>(hi) | reinterpret_cast<uintptr_t>(lo)) & 7)) return DDPO_EINVAL;
-  int64_t blocks = (rows * (cols >> 2) + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(split_planes_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), x, ldx, hi, lo, ld_out, rows, cols >> 2);
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
-}
-
-__global__ void __launch_bounds__(256) split_planes_mx_kernel(const float* __restrict__ x, int ldx, uint16_t* __restrict__ p16,
-                                                              uint16_t* __restrict__ p8, int ld_out, int64_t rows, int cols4) {
-  const int64_t total = rows * cols4;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / cols4;
-    const int c = (int)(i - r * cols4) << 2;
-    mx_store4(p16, p8, r, c, ld_out, rows, *reinterpret_cast<const float4*>(x + r * ldx + c));
-  }
-}
-
-extern "C" int ddpo_split_planes_f16mx(const float* x, int ldx, uint16_t* p16, uint16_t* p8, int ld_out, int64_t rows, int cols, void* stream) {
-  if (!x || !p16 || !p8 || rows <= 0 || cols <= 0 || (cols & 31) || (ldx & 3) || (ld_out & 31) || ldx < cols) return DDPO_EINVAL;
-  if (ld_out != 0 && ld_out < cols) return DDPO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) || ((reinterpret_cast<uintptr_t>(p16) | reinterpret_cast<uintptr_t>(p8)) & 7)) return DDPO_EINVAL;
-  int64_t blocks = (rows * (cols >> 2) + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(split_planes_mx_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), x, ldx, p16, p8, ld_out, rows, cols >> 2);
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
-}
-
-// f16mx weight planes (include/ddpo_hip.h).  Pass 1 (a, b): biased exponent of every column's largest |w| -> scale byte; pass 2: the 32x32
-// tile transpose of the k-blocked packer, writing the f16 plane and the [l8 | h8] byte plane.
-// pass 1a: biased exponent of every column's largest |w|.  64 columns x 4 k-lanes per workgroup, the reduction split over blockIdx.y chunks of k
-// and combined with atomicMax on the (non-negative) fp32 bit patterns in a caller-provided uint32 scratch (N words, zeroed).
-__global__ void __launch_bounds__(256) mx_colmax_kernel(const float* __restrict__ w, int K, int N, int k_per_block, uint32_t* __restrict__ colmax) {
-  __shared__ uint32_t red[4][64];
-  const int c = threadIdx.x & 63, kl = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + c;
-  const int k0 = blockIdx.y * k_per_block, k1 = min(K, k0 + k_per_block);
-  uint32_t m = 0;
-  if (n < N)
-    for (int k = k0 + kl; k < k1; k += 4) m = max(m, __float_as_uint(w[(int64_t)k * N + n]) & 0x7FFFFFFFu);
-  red[kl][c] = m;
-  __syncthreads();
-  if (kl == 0 && n < N) {
-    m = max(max(red[0][c], red[1][c]), max(red[2][c], red[3][c]));
-    if (m) atomicMax(colmax + n, m);
-  }
-}
-// pass 1b: scale byte
-__global__ void __launch_bounds__(256) mx_colscale_kernel(const uint32_t* __restrict__ colmax, int N, uint8_t* __restrict__ scale) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  int e = (int)(colmax[n] >> 23);         // 2^(e - 127) <= max|w| < 2^(e - 126)
-  e = min(max(e, 32), 240);               // all-zero / denormal columns: any valid scale; keeps (byte - 11) and 2^(261 - e) in range
-  scale[n] = (uint8_t)(e - 7);            // max|w| / 2^(e - 7 - 127) in [128, 256) <= 448 (e4m3 range)
-}
-__global__ void __launch_bounds__(256) pack_weights_mx_kernel(const float* __restrict__ w, int K, int N, const uint8_t* __restrict__ scale,
-                                                              uint16_t* __restrict__ w16, uint8_t* __restrict__ w8) {
-  __shared__ uint32_t tile[32][33];       // f16 bits | h8 << 16 | l8 << 24
-  const int kb = blockIdx.y, k0 = kb * 32, n0 = blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int r = ty; r < 32; r += 8) {
-    const int k = k0 + r, n = n0 + tx;
-    uint32_t packed = 0;
-    if (k < K && n < N) {
-      const float x = fminf(fmaxf(w[(int64_t)k * N + n], -65504.f), 65504.f);
-      const _Float16 h = (_Float16)x;
-      const float hf = (float)h, inv = __uint_as_float((uint32_t)(254 - (int)scale[n]) << 23);       // 2^-(byte - 127)
-      const int p = __builtin_amdgcn_cvt_pk_fp8_f32(hf * inv, (x - hf) * 2048.f * inv, 0, false);
-      packed = (uint32_t)__builtin_bit_cast(uint16_t, h) | ((uint32_t)p << 16);
-    }
-    tile[r][tx] = packed;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int n = n0 + r;
-    if (n < N) {
-      const uint32_t p = tile[tx][r];
-      const int64_t row = (int64_t)kb * N + n;
-      w16[row * 32 + tx] = (uint16_t)(p & 0xFFFFu);
-      const int o = 2 * (tx & 16) + (tx & 15);              // chunks [l8 k0-15 | h8 k0-15 | l8 k16-31 | h8 k16-31]
-      w8[row * 64 + o] = (uint8_t)(p >> 24);                // l8 first: lane half 0 of the MFMA pairs it with the activations' h8
-      w8[row * 64 + o + 16] = (uint8_t)((p >> 16) & 0xFFu);
-    }
-  }
-}
-extern "C" int ddpo_pack_weights_f16mx(const float* w, int K, int N, uint16_t* w16, uint16_t* w8, uint8_t* scale, void* stream) {
-  if (!w || !w16 || !w8 || !scale || K <= 0 || N <= 0) return DDPO_EINVAL;
-  // the column maxima are gathered in the first N words of the f16 plane (>= 64 bytes per column; overwritten by the pack pass below)
-  uint32_t* colmax = reinterpret_cast<uint32_t*>(w16);
-  if (hipMemsetAsync(colmax, 0, (size_t)N * sizeof(uint32_t), as_stream(stream)) != hipSuccess) return DDPO_ELAUNCH;
-  int ky = (K + 255) / 256;
-  if (ky > 128) ky = 128;
-  const int kpb = ((K + ky - 1) / ky + 3) / 4 * 4;
-  hipLaunchKernelGGL(mx_colmax_kernel, dim3((N + 63) / 64, (K + kpb - 1) / kpb), dim3(256), 0, as_stream(stream), w, K, N, kpb, colmax);
-  DDPO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mx_colscale_kernel, dim3((N + 255) / 256), dim3(256), 0, as_stream(stream), colmax, N, scale);
-  DDPO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(pack_weights_mx_kernel, dim3((N + 31) / 32, (K + 31) / 32), dim3(256), 0, as_stream(stream), w, K, N, scale, w16,
-                     reinterpret_cast<uint8_t*>(w8));
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Weight gradient on the bf16x3 MFMA datapath:  dW[k][n] += sum_m A(m,k) * dY[m][n]   (k = (ky,kx,ci); m = pixels)
-// Both operands have the reduction index m as their SLOW memory dimension, so each is transposed while it is staged:
-// a thread loads float4s of two consecutive pixels and writes, per channel, the packed (pixel m, pixel m+1) bf16 pair
-// as one dword of the [row][m] LDS image.  Row pitch is 18 dwords (72 B): the pair writes of a half-wave hit 32
-// distinct banks (x2, free) and the two ds_read_b64 of a fragment are conflict free.  Fast path only: stride 1,
-// no upsampling (output pixel m == input pixel m, source address linear in m); other layers use gemm_wgrad_kernel.
-// ------------------------------------------------------------------------------------------------
-#define WG_PITCH 18     // dwords per LDS row (16 dwords = 32 pixels of the k-tile, +2 pad)
-
-__device__ __forceinline__ bf16x8 lds_frag(const uint32_t* base, int row, int dw) {
-  const uint2 a = *reinterpret_cast<const uint2*>(base + row * WG_PITCH + dw);
-  const uint2 b = *reinterpret_cast<const uint2*>(base + row * WG_PITCH + dw + 2);
-  return __builtin_bit_cast(bf16x8, make_uint4(a.x, a.y, b.x, b.y));
-}
-
-// APLN / BPLN: that operand arrives ALREADY split into bf16 hi / lo planes ((rows, ld) bf16, same element offsets as the fp32
-// tensor: the activation planes a forward GroupNorm / LayerNorm wrote, or dY planes from a plane-emitting output stage) — the
-// loader then only has to pair pixels m / m+1 of a channel into a dword (one v_perm_b32 per plane dword) instead of running the
-// fp32 -> bf16 split (2 v_cvt_pk + 2 v_sub + 2 mask / shift per pair): the split was ~2/3 of this kernel's VALU work, which
-// looked like its bound (measured in round 2: +0.5 % on the train step, so it is not).  Same values reach the MFMAs as in the fp32-fed form.
-// Also measured and rejected in round 2: unconditional loads + a second register stage (two k-tiles of prefetch): 256 VGPRs with
-// 12-24 spilled at two waves per SIMD, train step 9 % SLOWER (profiles/r02_ab_wgrad_deep.log).
-// ROWL ("row loader", round 2): the SQ counters of the loader below showed ~10 VALU + 4 SALU per MFMA at 31 % MFMA-pipe busy: 16 bytes per
-// fetch, ~25 VALU per fetch of 64-bit address arithmetic, per-pixel (batch, y, x) bookkeeping with loops and divergent branches around every
-// load.  For the regular layers (dense, or stride-1 "same" convolutions whose rows tile into the 32-pixel k-tiles: OW % 32 == 0 or
-// 32 % OW == 0; M % 32 == 0; operand tensors < 2 GiB) all of that collapses: a k-tile is 32 consecutive pixels starting at an image-row
-// boundary that is the SAME for the whole workgroup, so (oy, ox) of the tile live in scalars, every thread's four byte offsets relative
-// to the tile are CONSTANTS, the per-tile advance is one scalar soffset, and a masked element is an out-of-range buffer offset that reads
-// zeros (raw buffer loads) — ~6 VALU per activation fetch, none per dY fetch, no branches.
-template <bool APLN, bool BPLN, bool ROWL = false>
-__global__ void __launch_bounds__(BF_THREADS) gemm_wgrad_bf16_kernel(const ddpo_gemm_desc d, int tiles_n, int m_per_split,
-                                                                   const uint16_t* __restrict__ a_hi, const uint16_t* __restrict__ a_lo,
-                                                                   const uint16_t* __restrict__ b_hi, const uint16_t* __restrict__ b_lo) {
-  constexpr int BM = 128, BN = 128, BK = 32;
-  constexpr int PLANE = BM * WG_PITCH;                 // dwords per plane (BM == BN)
-  __shared__ __attribute__((aligned(16))) uint32_t smem[2][4 * PLANE];     // per stage: A_hi | A_lo | B_hi | B_lo
-  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-  const int wm = wid >> 1, wn = wid & 1;
-  const int tile_m = blockIdx.x / tiles_n, tile_n = blockIdx.x - tile_m * tiles_n;
-  const int k0 = tile_m * BM, n0 = tile_n * BN;
-  const int m_begin = blockIdx.y * m_per_split;
-  const int m_end = min(m_begin + m_per_split, d.M);
-  if (m_begin >= m_end) return;
-
-  const bool conv = d.ksize > 0;
-  // loader geometry: quad q = lane&7 (4 consecutive k or n), pixel pair pp = lane>>3, wave w covers rows 32w..32w+31
-  const int q = lane & 7, pp = lane >> 3;
-  const int arow = 32 * wid + 4 * q;                   // first of this thread's 4 LDS rows (same for A and B tiles)
-  const int kg = k0 + arow;                            // global k of those rows
-  const bool kvalid = kg < d.K;
-  int dky = 0, dkx = 0, ci = kg;
-  if (conv) {
-    const int tap = kg / d.Cin;
-    ci = kg - tap * d.Cin;
-    const int ky = tap / d.ksize;
-    dky = ky - d.pad;
-    dkx = tap - ky * d.ksize - d.pad;
-  }
-  const int ng = n0 + arow;
-  const bool nvalid = ng < d.N;
-  // the 4 OUTPUT pixels this thread stages per k-tile: m = m_begin + kt*32 + 16*p + 2*pp + e ; (batch, oy, ox) are tracked
-  // incrementally.  Stride-1 "same" convolutions read input pixel m + a constant tap offset (`simple`); strided and
-  // nearest-2x-upsampled ones compute the source pixel of the tap from (oy, ox).
-  const bool simple = !conv || (d.stride == 1 && d.upsample == 0 && d.OH == d.H && d.OW == d.W);
-  const int VH = d.upsample ? 2 * d.H : d.H, VW = d.upsample ? 2 * d.W : d.W;
-  int pb[2][2], poy[2][2], pox[2][2];
-#pragma unroll
-  for (int p = 0; p < 2; ++p)
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int m = m_begin + 16 * p + 2 * pp + e;
-      pox[p][e] = conv ? m % d.OW : 0;
-      poy[p][e] = conv ? (m / d.OW) % d.OH : 0;
-      pb[p][e] = conv ? m / (d.OW * d.OH) : 0;
-    }
-  // element strides / channel terms of the two operands.  A k-blocked PLANE operand (ld == 0: (C / 32, rows, 32), ABI v6) has pixel
-  // stride 32 and the channel quad's block base + offset inside the block as its "channel term"; everything below is written on these.
-  const bool kbA = APLN && d.ld_src == 0, kbB = BPLN && d.ld_w == 0;
-  const int64_t rowsA = conv ? (int64_t)d.B * d.H * d.W : (int64_t)d.M;
-  const int lda_e = kbA ? 32 : d.ld_src, ldb_e = kbB ? 32 : d.ld_w;
-  const int64_t a_c0 = kbA ? (int64_t)(ci >> 5) * rowsA * 32 + (ci & 31) : (int64_t)ci;          // dense: ci == kg
-  const int64_t b_c0 = kbB ? (int64_t)(ng >> 5) * (int64_t)d.M * 32 + (ng & 31) : (int64_t)ng;
-  const int64_t tap_off = conv ? ((int64_t)dky * d.W + dkx) * lda_e + a_c0 : a_c0;
-
-  float4 ra[2][2], rb[2][2];          // fp32 operands; a plane operand keeps (hi.x, hi.y, lo.x, lo.y) raw bits in the same registers
-  auto as_f4 = [](const uint2 h, const uint2 l) {
-    return make_float4(__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(l.x), __uint_as_float(l.y));
-  };
-  // ---- ROWL state (see the note above the kernel)
-  constexpr uint32_t ESA = APLN ? 2u : 4u, ESB = BPLN ? 2u : 4u;     // bytes per element of the operands as stored
-  uint32_t rl_va[2][2], rl_vb[2][2];   // byte offsets of this thread's elements for k-tile 0 (BUF_OOB: never valid)
-  int rl_cy[2][2], rl_cx[2][2];        // iy = oy_t + cy, ix = ox_t + cx of the element's tap
-  int rl_oy = 0, rl_ox = 0;            // image row / column of the CURRENT k-tile's first pixel (uniform)
-  // a tap above / left of the tile has a NEGATIVE offset relative to its pixel: the activation descriptors start `rl_guard` bytes in front of
-  // the tensor so that every offset is non-negative (such elements are only ever fetched when their tap is inside the image, i.e. in range)
-  const int64_t rl_guard = conv ? (int64_t)(d.W + 1) * lda_e * (int64_t)ESA : 0;
-  __amdgpu_buffer_rsrc_t rl_ra0 = make_rsrc(reinterpret_cast<const char*>(APLN ? (const void*)a_hi : (const void*)d.src) - rl_guard),
-                         rl_ra1 = make_rsrc(reinterpret_cast<const char*>(APLN ? (const void*)a_lo : (const void*)d.src) - rl_guard);
-  __amdgpu_buffer_rsrc_t rl_rb0 = make_rsrc(BPLN ? (const void*)b_hi : (const void*)d.w), rl_rb1 = make_rsrc(BPLN ? (const void*)b_lo : (const void*)d.w);
-  if constexpr (ROWL) {
-    const int rem = conv ? m_begin % (d.OH * d.OW) : 0;
-    rl_oy = conv ? rem / d.OW : 0;
-    rl_ox = conv ? rem - rl_oy * d.OW : 0;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int eoff = 16 * p + 2 * pp + e;
-        const int dy_e = (conv && d.OW < BK) ? eoff / d.OW : 0;
-        const int x_e = (conv && d.OW < BK) ? eoff - dy_e * d.OW : eoff;
-        rl_cy[p][e] = dy_e + dky;
-        rl_cx[p][e] = x_e + dkx;
-        const int64_t ao = ((int64_t)(m_begin + eoff) * lda_e + tap_off) * (int64_t)ESA + rl_guard;
-        const int64_t bo = ((int64_t)(m_begin + eoff) * ldb_e + b_c0) * (int64_t)ESB;
-        rl_va[p][e] = (kvalid && ao >= 0 && ao < 0x7FFFFFF0ll) ? (uint32_t)ao : BUF_OOB;
-        rl_vb[p][e] = (nvalid && bo >= 0 && bo < 0x7FFFFFF0ll) ? (uint32_t)bo : BUF_OOB;
-      }
-  }
-  auto load_tile_rows = [&](int kt) {
-    const uint32_t so_a = (uint32_t)kt * (uint32_t)(BK * lda_e) * ESA, so_b = (uint32_t)kt * (uint32_t)(BK * ldb_e) * ESB;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        uint32_t voa = rl_va[p][e];
-        if (conv) {
-          const bool ok = (unsigned)(rl_oy + rl_cy[p][e]) < (unsigned)d.H && (unsigned)(rl_ox + rl_cx[p][e]) < (unsigned)d.W;
-          voa = ok ? voa : BUF_OOB;
-        }
-        if (APLN) {
-          const u32x2 h2 = __builtin_amdgcn_raw_buffer_load_b64(rl_ra0, voa, so_a, 0), l2 = __builtin_amdgcn_raw_buffer_load_b64(rl_ra1, voa, so_a, 0);
-          ra[p][e] = make_float4(__uint_as_float(h2.x), __uint_as_float(h2.y), __uint_as_float(l2.x), __uint_as_float(l2.y));
-        } else {
-          const u32x4 v4 = __builtin_amdgcn_raw_buffer_load_b128(rl_ra0, voa, so_a, 0);
-          ra[p][e] = make_float4(__uint_as_float(v4.x), __uint_as_float(v4.y), __uint_as_float(v4.z), __uint_as_float(v4.w));
-        }
-        if (BPLN) {
-          const u32x2 h2 = __builtin_amdgcn_raw_buffer_load_b64(rl_rb0, rl_vb[p][e], so_b, 0), l2 = __builtin_amdgcn_raw_buffer_load_b64(rl_rb1, rl_vb[p][e], so_b, 0);
-          rb[p][e] = make_float4(__uint_as_float(h2.x), __uint_as_float(h2.y), __uint_as_float(l2.x), __uint_as_float(l2.y));
-        } else {
-          const u32x4 v4 = __builtin_amdgcn_raw_buffer_load_b128(rl_rb0, rl_vb[p][e], so_b, 0);
-          rb[p][e] = make_float4(__uint_as_float(v4.x), __uint_as_float(v4.y), __uint_as_float(v4.z), __uint_as_float(v4.w));
-        }
-      }
-    if (conv) {                           // next k-tile: 32 pixels on (uniform)
-      if (d.OW >= BK) {
-        rl_ox += BK;
-        if (rl_ox >= d.OW) { rl_ox = 0; rl_oy = rl_oy + 1 >= d.OH ? 0 : rl_oy + 1; }
-      } else {
-        rl_oy += BK / d.OW;
-        if (rl_oy >= d.OH) rl_oy -= d.OH;
-      }
-    }
-  };
-  auto load_tile_px = [&](int kt) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int m = m_begin + kt * BK + 16 * p + 2 * pp + e;
-        float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
-        if (m < m_end) {
-          bool ok = kvalid;
-          int64_t aoff = (int64_t)m * lda_e + tap_off;
-          if (conv) {
-            const int iy = poy[p][e] * d.stride + dky, ix = pox[p][e] * d.stride + dkx;       // virtual (upsampled) coordinates
-            ok = ok && iy >= 0 && iy < VH && ix >= 0 && ix < VW;
-            if (!simple) {
-              const int sy = d.upsample ? (iy >> 1) : iy, sx = d.upsample ? (ix >> 1) : ix;
-              aoff = ((int64_t)(pb[p][e] * d.H + sy) * d.W + sx) * lda_e + a_c0;
-            }
-          }
-          if (ok) {
-            if (APLN) va = as_f4(*reinterpret_cast<const uint2*>(a_hi + aoff), *reinterpret_cast<const uint2*>(a_lo + aoff));
-            else va = *reinterpret_cast<const float4*>(d.src + aoff);
-          }
-          if (nvalid) {
-            const int64_t boff = (int64_t)m * ldb_e + b_c0;
-            if (BPLN) vb = as_f4(*reinterpret_cast<const uint2*>(b_hi + boff), *reinterpret_cast<const uint2*>(b_lo + boff));
-            else vb = *reinterpret_cast<const float4*>(d.w + boff);
-          }
-        }
-        ra[p][e] = va;
-        rb[p][e] = vb;
-        if (conv) {          // advance this pixel by BK
-          pox[p][e] += BK;
-          while (pox[p][e] >= d.OW) { pox[p][e] -= d.OW; ++poy[p][e]; }
-          while (poy[p][e] >= d.OH) { poy[p][e] -= d.OH; ++pb[p][e]; }
-        }
-      }
-  };
-  auto load_tile = [&](int kt) {
-    if constexpr (ROWL) load_tile_rows(kt); else load_tile_px(kt);
-  };
-  // bias gradient (d.colsum, fp32 dY only): the k = 0 row of workgroups also sums the dY values it stages, per channel
-  const bool do_cs = !BPLN && d.colsum != nullptr && tile_m == 0;
-  float cs[4] = {0.f, 0.f, 0.f, 0.f};
-  auto store_tile = [&](int buf) {
-    uint32_t* st = smem[buf];
-    if (do_cs) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) cs[j] += ((&rb[0][0].x)[j] + (&rb[0][1].x)[j]) + ((&rb[1][0].x)[j] + (&rb[1][1].x)[j]);
-    }
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int dw = pp + 8 * p;                        // dword (= pixel pair) index within the row
-      const float* a0 = &ra[p][0].x; const float* a1 = &ra[p][1].x;
-      const float* b0 = &rb[p][0].x; const float* b1 = &rb[p][1].x;
-      // plane operand: registers hold [ch0|ch1, ch2|ch3] (hi) and the same for lo, per pixel; pair channel j of pixels m, m+1
-      auto pair = [](const float* p0, const float* p1, int j, int plane) {
-        const uint32_t w0 = __float_as_uint(p0[2 * plane + (j >> 1)]), w1 = __float_as_uint(p1[2 * plane + (j >> 1)]);
-        return __builtin_amdgcn_perm(w1, w0, (j & 1) ? 0x07060302u : 0x05040100u);
-      };
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t hi, lo;
-        if (APLN) { hi = pair(a0, a1, j, 0); lo = pair(a0, a1, j, 1); }
-        else split2(a0[j], a1[j], hi, lo);              // (pixel m, pixel m+1) of channel k+j
-        st[(arow + j) * WG_PITCH + dw] = hi;
-        st[PLANE + (arow + j) * WG_PITCH + dw] = lo;
-        if (BPLN) { hi = pair(b0, b1, j, 0); lo = pair(b0, b1, j, 1); }
-        else split2(b0[j], b1[j], hi, lo);
-        st[2 * PLANE + (arow + j) * WG_PITCH + dw] = hi;
-        st[3 * PLANE + (arow + j) * WG_PITCH + dw] = lo;
-      }
-    }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int nk = (m_end - m_begin + BK - 1) / BK;
-  const int li = lane & 31, h = lane >> 5;
-  load_tile(0);
-  store_tile(0);
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) load_tile(kt + 1);
-    const uint32_t* st = smem[cur];
-#pragma unroll
-    for (int ms = 0; ms < 2; ++ms) {
-      const int dw = 8 * ms + 4 * h;
-      bf16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        ah[i] = lds_frag(st, wm * 64 + i * 32 + li, dw);
-        al[i] = lds_frag(st + PLANE, wm * 64 + i * 32 + li, dw);
-        bh[i] = lds_frag(st + 2 * PLANE, wn * 64 + i * 32 + li, dw);
-        bl[i] = lds_frag(st + 3 * PLANE, wn * 64 + i * 32 + li, dw);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-    }
-    if (kt + 1 < nk) store_tile(cur ^ 1);
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = n0 + wn * 64 + j * 32 + li;
-      if (col >= d.N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = k0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (row >= d.K) continue;
-        atomicAdd(d.out + (int64_t)row * d.ld_out + col, d.alpha * acc[i][j][r]);
-      }
-    }
-  if (do_cs) {                                  // lanes q + 8 * pp of a wave hold the same 4 channels: fold the 8 pixel-pair lanes, lane pp == 0 adds
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float v = cs[j];
-      v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
-      if (pp == 0 && ng + j < d.N) atomicAdd(d.colsum + ng + j, v);
-    }
-  }
-}
-
-// WIDE weight-gradient tile (round 3): 128 (k) x 320 (n) per workgroup, 8 waves of 32 x 160, one workgroup per CU.  The 128 x 128 kernel above
-// moves 32 KB of operands per 0.52 M multiply-adds (61 B / kMAC) and sits at the CU's ~20 B / clk fetch rate with the matrix pipe 42 % busy
-// (236 TF); this tile moves 56 KB per 1.31 M (43 B / kMAC) — the forward 128x320 tile's ratio.  Row loader only (the regular layers: dense, and
-// stride-1 "same" convolutions whose rows tile into the 32-pixel k-tiles), N % 320 == 0; same staging (pixel pairs of a channel packed into one
-// dword of the [row][m] LDS image), same MFMA order per element as the 128 x 128 kernel.
-//   loader tasks (4 channels x 2 pixels, 8 quads x 8 pixel pairs per wave): A = 128 rows x 16 pairs = 8 wave tasks, one per wave;
-//   dY = 320 rows x 16 pairs = 20 wave tasks: waves 0-3 take three, waves 4-7 two.
-template <bool APLN, bool BPLN>
-__global__ void __launch_bounds__(512) gemm_wgrad_bf16_wide_kernel(const ddpo_gemm_desc d, int tiles_n, int m_per_split,
-                                                                   const uint16_t* __restrict__ a_hi, const uint16_t* __restrict__ a_lo,
-                                                                   const uint16_t* __restrict__ b_hi, const uint16_t* __restrict__ b_lo) {
-  constexpr int BM = 128, BN = 320, BK = 32, TN = 5, NBT = 3;
-  constexpr int PA = BM * WG_PITCH, PB = BN * WG_PITCH;          // dwords per plane
-  constexpr int STAGE = 2 * PA + 2 * PB;                         // A_hi | A_lo | B_hi | B_lo
-  extern __shared__ __attribute__((aligned(16))) uint32_t wsm[];
-  const int t = threadIdx.x, lane = t & 63, wid = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wm = wid >> 1, wn = wid & 1;
-  const int tile_m = blockIdx.x / tiles_n, tile_n = blockIdx.x - tile_m * tiles_n;
-  const int k0 = tile_m * BM, n0 = tile_n * BN;
-  const int m_begin = blockIdx.y * m_per_split;
-  const int m_end = min(m_begin + m_per_split, d.M);
-  if (m_begin >= m_end) return;
-  const bool conv = d.ksize > 0;
-  const int q = lane & 7, pp = lane >> 3;
-  // ---- this thread's A task: 4 channel rows, one pixel pair
-  const int a_row = 32 * (wid & 3) + 4 * q, a_dw = 8 * (wid >> 2) + pp;
-  const int kg = k0 + a_row;
-  const bool kvalid = kg < d.K;
-  int dky = 0, dkx = 0, ci = kg;
-  if (conv) {
-    const int tap = kg / d.Cin;
-    ci = kg - tap * d.Cin;
-    const int ky = tap / d.ksize;
-    dky = ky - d.pad;
-    dkx = tap - ky * d.ksize - d.pad;
-  }
-  const bool kbA = APLN && d.ld_src == 0, kbB = BPLN && d.ld_w == 0;
-  const int64_t rowsA = conv ? (int64_t)d.B * d.H * d.W : (int64_t)d.M;
-  const int lda_e = kbA ? 32 : d.ld_src, ldb_e = kbB ? 32 : d.ld_w;
-  const int64_t a_c0 = kbA ? (int64_t)(ci >> 5) * rowsA * 32 + (ci & 31) : (int64_t)ci;
-  const int64_t tap_off = conv ? ((int64_t)dky * d.W + dkx) * lda_e + a_c0 : a_c0;
-  constexpr uint32_t ESA = APLN ? 2u : 4u, ESB = BPLN ? 2u : 4u;
-  const int64_t rl_guard = conv ? (int64_t)(d.W + 1) * lda_e * (int64_t)ESA : 0;
-  const __amdgpu_buffer_rsrc_t rs_a0 = make_rsrc(reinterpret_cast<const char*>(APLN ? (const void*)a_hi : (const void*)d.src) - rl_guard),
-                               rs_a1 = make_rsrc(reinterpret_cast<const char*>(APLN ? (const void*)a_lo : (const void*)d.src) - rl_guard);
-  const __amdgpu_buffer_rsrc_t rs_b0 = make_rsrc(BPLN ? (const void*)b_hi : (const void*)d.w), rs_b1 = make_rsrc(BPLN ? (const void*)b_lo : (const void*)d.w);
-  uint32_t va[2], vb[NBT][2];
-  int cy[2], cx[2];
-  const int rem0 = conv ? m_begin % (d.OH * d.OW) : 0;
-  int t_oy = conv ? rem0 / d.OW : 0, t_ox = conv ? rem0 - (rem0 / d.OW) * d.OW : 0;      // image position of the current k-tile's first pixel (uniform)
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int eoff = 2 * a_dw + e;
-    const int dy_e = (conv && d.OW < BK) ? eoff / d.OW : 0;
-    const int x_e = (conv && d.OW < BK) ? eoff - dy_e * d.OW : eoff;
-    cy[e] = dy_e + dky;
-    cx[e] = x_e + dkx;
-    const int64_t ao = ((int64_t)(m_begin + eoff) * lda_e + tap_off) * (int64_t)ESA + rl_guard;
-    va[e] = (kvalid && ao >= 0 && ao < 0x7FFFFFF0ll) ? (uint32_t)ao : BUF_OOB;
-  }
-  int b_row[NBT], b_dw[NBT];
-#pragma unroll
-  for (int i = 0; i < NBT; ++i) {
-    const int T = wid + 8 * i;                         // wave task: channel block T >> 1 (of 10), pixel-pair half T & 1
-    b_row[i] = 32 * (T >> 1) + 4 * q;
-    b_dw[i] = 8 * (T & 1) + pp;
-    const int ng = n0 + b_row[i];
-    const int64_t b_c0 = kbB ? (int64_t)(ng >> 5) * (int64_t)d.M * 32 + (ng & 31) : (int64_t)ng;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int64_t bo = ((int64_t)(m_begin + 2 * b_dw[i] + e) * ldb_e + b_c0) * (int64_t)ESB;
-      vb[i][e] = (T < 20 && ng < d.N && bo >= 0 && bo < 0x7FFFFFF0ll) ? (uint32_t)bo : BUF_OOB;
-    }
-  }
-  const bool third = wid < 4;                          // wave-uniform: this wave stages a third dY task
-  // TWO register sets: tile T travels in set T & 1 and is requested two k-tiles before it is written to LDS (one workgroup per CU: nothing else
-  // covers the fetch latency; with one set the loop measured no faster than the 128 x 128 kernel's two workgroups per CU)
-  float4 ra[2][2], rb[2][NBT][2];
-  auto ld4 = [&](const __amdgpu_buffer_rsrc_t r0, const __amdgpu_buffer_rsrc_t r1, uint32_t vo, uint32_t so, bool pl) {
-    if (pl) {
-      const u32x2 h2 = __builtin_amdgcn_raw_buffer_load_b64(r0, vo, so, 0), l2 = __builtin_amdgcn_raw_buffer_load_b64(r1, vo, so, 0);
-      return make_float4(__uint_as_float(h2.x), __uint_as_float(h2.y), __uint_as_float(l2.x), __uint_as_float(l2.y));
-    }
-    const u32x4 v4 = __builtin_amdgcn_raw_buffer_load_b128(r0, vo, so, 0);
-    return make_float4(__uint_as_float(v4.x), __uint_as_float(v4.y), __uint_as_float(v4.z), __uint_as_float(v4.w));
-  };
-  const int nk = (m_end - m_begin + BK - 1) / BK;
-  auto load_tile = [&](int kt, auto sc) {              // requests past the last k-tile re-fetch it (unconditional loads: counted waits stay exact)
-    constexpr int S = decltype(sc)::value;
-    const int ktc = min(kt, nk - 1);
-    const uint32_t so_a = (uint32_t)ktc * (uint32_t)(BK * lda_e) * ESA, so_b = (uint32_t)ktc * (uint32_t)(BK * ldb_e) * ESB;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      uint32_t vo = va[e];
-      if (conv) vo = ((unsigned)(t_oy + cy[e]) < (unsigned)d.H && (unsigned)(t_ox + cx[e]) < (unsigned)d.W) ? vo : BUF_OOB;
-      ra[S][e] = ld4(rs_a0, rs_a1, vo, so_a, APLN);
-    }
-#pragma unroll
-    for (int i = 0; i < NBT; ++i) {
-      if (i == 2 && !third) continue;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) rb[S][i][e] = ld4(rs_b0, rs_b1, vb[i][e], so_b, BPLN);
-    }
-    if (conv && kt < nk - 1) {            // next k-tile: 32 pixels on (uniform)
-      if (d.OW >= BK) {
-        t_ox += BK;
-        if (t_ox >= d.OW) { t_ox = 0; t_oy = t_oy + 1 >= d.OH ? 0 : t_oy + 1; }
-      } else {
-        t_oy += BK / d.OW;
-        if (t_oy >= d.OH) t_oy -= d.OH;
-      }
-    }
-  };
-  auto pair = [](const float* p0, const float* p1, int j, int plane) {
-    const uint32_t w0 = __float_as_uint(p0[2 * plane + (j >> 1)]), w1 = __float_as_uint(p1[2 * plane + (j >> 1)]);
-    return __builtin_amdgcn_perm(w1, w0, (j & 1) ? 0x07060302u : 0x05040100u);
-  };
-  const bool do_cs = !BPLN && d.colsum != nullptr && tile_m == 0;      // bias gradient: see the 128 x 128 kernel
-  float cs[NBT][4];
-#pragma unroll
-  for (int i = 0; i < NBT; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) cs[i][j] = 0.f;
-  auto store_tile = [&](int buf, auto sc) {
-    constexpr int S = decltype(sc)::value;
-    uint32_t* st = wsm + buf * STAGE;
-    if (do_cs) {
-#pragma unroll
-      for (int i = 0; i < NBT; ++i) {
-        if (i == 2 && !third) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cs[i][j] += (&rb[S][i][0].x)[j] + (&rb[S][i][1].x)[j];
-      }
-    }
-    {
-      const float* a0 = &ra[S][0].x; const float* a1 = &ra[S][1].x;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t hi, lo;
-        if (APLN) { hi = pair(a0, a1, j, 0); lo = pair(a0, a1, j, 1); }
-        else split2(a0[j], a1[j], hi, lo);
-        st[(a_row + j) * WG_PITCH + a_dw] = hi;
-        st[PA + (a_row + j) * WG_PITCH + a_dw] = lo;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NBT; ++i) {
-      if (i == 2 && !third) continue;
-      const float* b0 = &rb[S][i][0].x; const float* b1 = &rb[S][i][1].x;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t hi, lo;
-        if (BPLN) { hi = pair(b0, b1, j, 0); lo = pair(b0, b1, j, 1); }
-        else split2(b0[j], b1[j], hi, lo);
-        st[2 * PA + (b_row[i] + j) * WG_PITCH + b_dw[i]] = hi;
-        st[2 * PA + PB + (b_row[i] + j) * WG_PITCH + b_dw[i]] = lo;
-      }
-    }
-  };
-
-  f32x16 acc[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-  const int li = lane & 31, h = lane >> 5;
-  auto compute = [&](int cur) {
-    const uint32_t* st = wsm + cur * STAGE;
-#pragma unroll
-    for (int ms = 0; ms < 2; ++ms) {
-      const int dw = 8 * ms + 4 * h;
-      const bf16x8 ah = lds_frag(st, wm * 32 + li, dw), al = lds_frag(st + PA, wm * 32 + li, dw);
-      bf16x8 bh[TN], bl[TN];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        bh[j] = lds_frag(st + 2 * PA, wn * 160 + j * 32 + li, dw);
-        bl[j] = lds_frag(st + 2 * PA + PB, wn * 160 + j * 32 + li, dw);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[j], acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[j], acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[j], acc[j], 0, 0, 0);
-      }
-    }
-  };
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
-  load_tile(0, S0{});
-  store_tile(0, S0{});
-  load_tile(1, S1{});
-  load_tile(2, S0{});
-  __syncthreads();
-  // iteration kt: tile kt + 1 (requested two iterations ago) -> the LDS stage everybody left at the last barrier; request tile kt + 3 into
-  // the registers just freed; multiply tile kt
-  auto step = [&](int kt, auto sc) {
-    constexpr int S = decltype(sc)::value;             // == (kt + 1) & 1
-    if (kt + 1 < nk) store_tile(S, sc);
-    load_tile(kt + 3, sc);
-    compute(S ^ 1);
-    __syncthreads();
-  };
-  int kt = 0;
-#pragma unroll 1
-  for (; kt + 1 < nk; kt += 2) {
-    step(kt, S1{});
-    step(kt + 1, S0{});
-  }
-  if (kt < nk) step(kt, S1{});
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int col = n0 + wn * 160 + j * 32 + li;
-    if (col >= d.N) continue;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = k0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      if (row >= d.K) continue;
-      atomicAdd(d.out + (int64_t)row * d.ld_out + col, d.alpha * acc[j][r]);
-    }
-  }
-  if (do_cs) {
-#pragma unroll
-    for (int i = 0; i < NBT; ++i) {
-      if (i == 2 && !third) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float v = cs[i][j];
-        v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
-        const int n = n0 + b_row[i] + j;
-        if (pp == 0 && vb[i][0] != BUF_OOB && n < d.N) atomicAdd(d.colsum + n, v);
-      }
-    }
-  }
-}
-
-static int wgrad_bf16x3(const ddpo_gemm_desc* dp, const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* b_hi, const uint16_t* b_lo,
-                       void* stream) {
-  if (!dp) return DDPO_EINVAL;
-  ddpo_gemm_desc d = *dp;
-  if ((!d.src && !a_hi) || (!d.w && !b_hi) || !d.out || d.M <= 0 || d.N <= 0 || d.K <= 0 || d.res_rows) return DDPO_EINVAL;
-  if ((a_hi && !a_lo) || (b_hi && !b_lo)) return DDPO_EINVAL;
-  if (d.colsum && b_hi) return DDPO_EINVAL;          // the fused bias gradient sums the fp32 dY registers
-  if ((d.ld_src & 3) || (d.ld_w & 3) || (d.N & 3) || (d.K & 3)) return DDPO_EINVAL;
-  if (!a_hi && (reinterpret_cast<uintptr_t>(d.src) & 15)) return DDPO_EINVAL;
-  if (!b_hi && (reinterpret_cast<uintptr_t>(d.w) & 15)) return DDPO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(a_hi) | reinterpret_cast<uintptr_t>(a_lo) | reinterpret_cast<uintptr_t>(b_hi) | reinterpret_cast<uintptr_t>(b_lo)) & 7)
-    return DDPO_EINVAL;
-  // ld == 0 marks a k-blocked PLANE operand (channels / 32, rows, 32): planes only, whole 32-channel blocks
-  if (d.ld_src < 0 || d.ld_w < 0) return DDPO_EINVAL;
-  if (d.ld_src == 0 && (!a_hi || ((d.ksize > 0 ? d.Cin : d.K) & 31))) return DDPO_EINVAL;
-  if (d.ld_w == 0 && (!b_hi || (d.N & 31))) return DDPO_EINVAL;
-  if (d.ksize > 0) {
-    if (d.ksize != 1 && d.ksize != 3) return DDPO_EINVAL;
-    if ((d.Cin & 3) || d.K != d.ksize * d.ksize * d.Cin || d.M != d.B * d.OH * d.OW) return DDPO_EINVAL;
-    if (d.stride < 1 || d.stride > 2 || d.upsample < 0 || d.upsample > 1 || d.pad != d.ksize / 2) return DDPO_EINVAL;
-    if ((int64_t)d.B * d.H * d.W * d.ld_src >= ((int64_t)1 << 40)) return DDPO_EINVAL;
-  }
-  const int tiles_m = (d.K + 127) / 128, tiles_n = (d.N + 127) / 128, tiles = tiles_m * tiles_n;
-  int splits = d.splits;
-  if (splits <= 0) {
-    // two workgroups fit a CU (74 KB LDS): pick the split of the pixel reduction whose tiles x splits fills whole rounds
-    // of the 512 slots best (1035 workgroups cost three rounds, 966 two); among near-equal fills prefer fewer splits
-    // (fewer atomic adds, longer k-loops).
-    const int max_splits = (d.M + 255) / 256;
-    int best = 1;
-    double best_eff = 0.0;
-    for (int r = 1; r <= 4; ++r) {
-      int cand = (512 * r) / tiles;
-      if (cand > max_splits) cand = max_splits;
-      if (cand < 1) cand = 1;
-      const long wgs = (long)tiles * cand;
-      const double eff = (double)wgs / (double)(((wgs + 511) / 512) * 512);
-      if (eff > best_eff + 0.03 || (best_eff == 0.0)) { best_eff = eff; best = cand; }
-    }
-    splits = best;
-  }
-  int mps = (d.M + splits - 1) / splits;
-  mps = (mps + 31) / 32 * 32;
-  splits = (d.M + mps - 1) / mps;
-  hipStream_t st = as_stream(stream);
-  const dim3 grid(tiles, splits), blk(BF_THREADS);
-  // row loader for the regular layers (the per-pixel loader takes the rest): conv 320->320 @ 64^2, U-Net batch 64:
-  // 2.54 -> 2.05 ms (190 -> 236 TF), profiles/r02_ab_wgrad_rows.log
-  constexpr int rows_mode = 1;
-  const bool conv_ = d.ksize > 0;
-  const bool simple_ = !conv_ || (d.stride == 1 && d.upsample == 0 && d.OH == d.H && d.OW == d.W);
-  const int64_t lda_b = d.ld_src ? d.ld_src : (conv_ ? d.Cin : d.K), ldb_b = d.ld_w ? d.ld_w : d.N;      // k-blocked planes: the same bytes in all
-  const int64_t a_bytes = (int64_t)d.M * lda_b * (a_hi ? 2 : 4), b_bytes = (int64_t)d.M * ldb_b * (b_hi ? 2 : 4);
-  const bool rows_ok = rows_mode && simple_ && (d.M % 32) == 0 && a_bytes + (conv_ ? (int64_t)(d.W + 1) * lda_b * 4 : 0) < 0x7FFFFFF0ll && b_bytes < 0x7FFFFFF0ll &&
-                       (!conv_ || (((d.OW % 32) == 0 || (32 % d.OW) == 0) && ((d.OH * d.OW) % 32) == 0));
-  // wide 128 x 320 tile (one workgroup per CU) where it measured faster (tools/native/kernel_probe wgrad, profiles/r03_probe_wgrad.log): the
-  // 320-column layers with a long k and many pixels — the 3x3 convolutions of the 64x64 level: 320->320 0.67 -> 0.48 ms (181 -> 254 TF) from
-  // fp32 operands, 0.57 -> 0.45 from planes; 960->320 1.62 -> 1.23 / 1.44 -> 1.29; train step +0.6 % (profiles/r03_ab_wgrad_wide.log).  With two or more 320-column tiles, short reductions or
-  // few pixels it ties or loses against two 128 x 128 workgroups per CU (LDS read bytes per MFMA of a 32 x 160 wave tile), so those stay there.
-  const bool wide_ok = rows_ok && d.N == 320 && d.K >= 2560 && d.M >= 16384 && dp->splits <= 0;
-  if (wide_ok) {
-    const int wt = ((d.K + 127) / 128) * (d.N / 320);
-    const int max_splits = (d.M + 255) / 256;
-    int ws_ = 1;                                         // split of the pixel reduction whose tiles x splits fills whole rounds of the 256 CUs best
-    double best_eff = 0.0;
-    for (int r = 1; r <= 3; ++r) {
-      int cand = (256 * r) / wt;
-      if (cand > max_splits) cand = max_splits;
-      if (cand < 1) cand = 1;
-      const long wgs = (long)wt * cand;
-      const double eff = (double)wgs / (double)(((wgs + 255) / 256) * 256);
-      if (eff > best_eff + 0.04 || best_eff == 0.0) { best_eff = eff; ws_ = cand; }
-    }
-    int wmps = (d.M + ws_ - 1) / ws_;
-    wmps = (wmps + 31) / 32 * 32;
-    ws_ = (d.M + wmps - 1) / wmps;
-    const size_t lds = (size_t)2 * (2 * 128 + 2 * 320) * WG_PITCH * 4;
-    const dim3 wgrid(wt, ws_), wblk(512);
-#define WGW_LAUNCH(A, B)                                                                                                           \
-  do {                                                                                                                             \
-    static bool attr_ = false;                                                                                                     \
-    if (!attr_) {                                                                                                                  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wgrad_bf16_wide_kernel<A, B>),                                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                             \
-      attr_ = true;                                                                                                                \
-    }                                                                                                                              \
-    hipLaunchKernelGGL((gemm_wgrad_bf16_wide_kernel<A, B>), wgrid, wblk, lds, st, d, d.N / 320, wmps, a_hi, a_lo, b_hi, b_lo);     \
-  } while (0)
-    if (a_hi && b_hi) WGW_LAUNCH(true, true);
-    else if (a_hi) WGW_LAUNCH(true, false);
-    else if (b_hi) WGW_LAUNCH(false, true);
-    else WGW_LAUNCH(false, false);
-#undef WGW_LAUNCH
-    DDPO_LAUNCH_CHECK();
-    return DDPO_OK;
-  }
-#define WG_LAUNCH(A, B)                                                                                                                        \
-  do {                                                                                                                                         \
-    if (rows_ok) hipLaunchKernelGGL((gemm_wgrad_bf16_kernel<A, B, true>), grid, blk, 0, st, d, tiles_n, mps, a_hi, a_lo, b_hi, b_lo);          \
-    else hipLaunchKernelGGL((gemm_wgrad_bf16_kernel<A, B, false>), grid, blk, 0, st, d, tiles_n, mps, a_hi, a_lo, b_hi, b_lo);                 \
-  } while (0)
-  if (a_hi && b_hi) WG_LAUNCH(true, true);
-  else if (a_hi) WG_LAUNCH(true, false);
-  else if (b_hi) WG_LAUNCH(false, true);
-  else WG_LAUNCH(false, false);
-#undef WG_LAUNCH
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
-}
-
-extern "C" int ddpo_gemm_conv_wgrad_bf16x3(const ddpo_gemm_desc* dp, void* stream) {
-  return wgrad_bf16x3(dp, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-/* Same contraction with one or both operands pre-split into bf16 hi / lo planes (NULL pair = that operand is fp32 in the descriptor):
- * a_* replace d->src (row stride d->ld_src ELEMENTS), dy_* replace d->w (row stride d->ld_w elements). */
-extern "C" int ddpo_gemm_conv_wgrad_bf16x3_planes(const ddpo_gemm_desc* dp, const uint16_t* a_hi, const uint16_t* a_lo,
-                                                  const uint16_t* dy_hi, const uint16_t* dy_lo, void* stream) {
-  if (!a_hi && !dy_hi) return DDPO_EINVAL;
-  return wgrad_bf16x3(dp, a_hi, a_lo, dy_hi, dy_lo, stream);
+  if (!plane_operands_ok(d, a_hi, a_lo, lda, f16mx ? 32 : 8, w_hi, w_lo, 0) || (int64_t)4 * d.K * d.N * 2 >= 0x7FFFFFFF) return DDPO_EINVAL;
+  return dispatch_bf16<true, true>(d, w_hi, w_lo, 0, npass, ws, ws_bytes, as_stream(stream));
 }

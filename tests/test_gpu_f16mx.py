@@ -73,7 +73,7 @@ CASES = [  # (B, H, Cin, Cout, ksize, stride, upsample)  ksize 0: dense with M =
     (2, 8, 64, 64, 3, 1, 1),         # nearest-neighbour upsample in the gather
     (2, 16, 96, 160, 1, 1, 0),       # 1x1
     (3, 77, 768, 320, 0, 1, 0),      # dense, ragged M
-    (1, 640, 320, 1280, 0, 1, 0),    # dense, 128x128 tiles
+    (1, 640, 320, 1280, 0, 1, 0),    # dense, many columns (50 tiles of 128x128 would under-fill the chip: 128x64 tiles)
 ]
 
 
@@ -216,3 +216,33 @@ def test_single_pass_f16_is_the_f16_term_of_the_operator(B, H, Cin, Cout, ks):
     assert float((out.double() - ref_planes).abs().max()) < 3e-6 * scale
     err = float((out.double() - ref_true).pow(2).mean().sqrt() / ref_true.pow(2).mean().sqrt())
     assert 5e-5 < err < 6e-4, err
+
+
+@pytest.mark.parametrize("single", [False, True])
+@pytest.mark.parametrize("M,K,N,cls", [(16384, 64, 512, "t128x128"),          # 512 tiles of 128x128 (N % 320 != 0), two k-tiles
+                                       (25600, 512, 320, "wide_128x320")])    # 200 tiles of 128x320, unsplit; 100 tall tiles would not fill the chip
+def test_128x128_and_wide_tiles_of_both_f16_datapaths(M, K, N, cls, single):
+    """The smallest dense geometries the routing rules send to the 128 x 128 and the 128 x 320 tile, on f16mx and on its single-pass form
+    (both 8-bit planes NULL): the tile-class counter moves, and the result is the exact product of the DECODED planes up to fp32 accumulation."""
+    from ctypes import byref
+    torch.manual_seed(11)
+    x = torch.randn(M, K, device="cuda")
+    w = torch.randn(K, N, device="cuda") / K ** 0.5
+    (p16, p8), wp = L.split_planes_f16mx(x), L.pack_weights_f16mx(w)
+    ah, ah8, al8 = _dec_planes(p16, p8)
+    wh, wh8, wl8 = _dec_weights(wp)
+    before = L.gemm_tile_launch_counts()
+    if single:
+        d = L.GemmDesc()
+        out = torch.empty(M, N, device="cuda")
+        d.out = out.data_ptr(); d.ld_out = N; d.alpha = 1.0; d.M, d.N, d.K = M, N, K; d.w_layout = 1
+        assert L.load().ddpo_gemm_conv_fwd_f16mx_planes(byref(d), L._p(p16), None, K, L._p(wp["w16"]), None, None, 0, None) == 0
+        ref = ah @ wh
+    else:
+        out = L.gemm_conv_f16mx((p16, p8), wp, M=M)
+        ref = ah @ wh + ah8 @ wl8 + al8 @ wh8
+    torch.cuda.synchronize()
+    after = L.gemm_tile_launch_counts()
+    assert after[cls] == before[cls] + 1 and after["tall_256x320"] == before["tall_256x320"], (before, after)
+    assert after["f16mx"] == before["f16mx"] + (0 if single else 1)
+    assert float((out.double() - ref).abs().max()) < 3e-6 * float(ref.abs().max())

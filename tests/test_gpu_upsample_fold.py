@@ -172,7 +172,8 @@ def test_strided_destination_leaves_the_neighbouring_columns_untouched(datapath,
 
 
 @pytest.mark.parametrize("mode", ["bf16x3", "bf16", "f16mx"])
-@pytest.mark.parametrize("B,H,W,C,N,cls", [(2, 8, 8, 1280, 1280, "splitk_reduce"), (8, 32, 32, 640, 640, "tall_256x320")])
+@pytest.mark.parametrize("B,H,W,C,N,cls", [(2, 8, 8, 1280, 1280, "splitk_reduce"), (8, 32, 32, 640, 640, "tall_256x320"),
+                                           (2, 32, 32, 640, 512, "t128x128")])      # 256 tiles of 128x128 over the four phases, 80 k-tiles
 def test_split_k_and_tall_tile_routes_are_taken_correct_and_deterministic(datapath, mode, B, H, W, C, N, cls):
     L.DATAPATH = mode
     x, w, bias = _inputs(B, H, W, C, N, 3)

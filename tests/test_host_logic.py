@@ -145,7 +145,7 @@ def test_byte_tokenizer_framing():
 
 @pytest.mark.parametrize("BM,BN,NW", [(128, 320, 8), (128, 128, 4), (128, 64, 4), (256, 320, 8)])
 def test_lds_dma_piece_map_reproduces_the_swizzled_lds_image(BM, BN, NW):
-    """Index algebra of the plane-fed GEMM's operand fill (csrc/gemm_bf16.hip, APL path), modelled lane by lane: every
+    """Index algebra of the plane-fed GEMM's operand fill (csrc/gemm_bf16.hip, the plane-fed k-loops), modelled lane by lane: every
     16-byte slot of every tile row is written exactly once per plane, by the lane whose SOURCE chunk is the one swz_off()
     places there (LDS-DMA writes lane-linearly: 64 lanes x 16 B = 16 rows x 64 B per wave instruction)."""
     PAIRS = NW // 2

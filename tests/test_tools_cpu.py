@@ -52,3 +52,29 @@ def test_rocpd_summary_ranks_kernels_by_total_time(tmp_path):
     assert text.startswith("# title") and "2 distinct kernels" in text
     table = [l for l in text.splitlines() if l.startswith("| `")]
     assert table[0].startswith("| `k_big()` | 1 | 1.00 |") and table[1].startswith("| `k_small()` | 2 | 0.00 |")
+
+
+def test_isa_diff_tells_a_renamed_kernel_from_a_changed_one(tmp_path):
+    def asm(kernels):
+        return "".join(f"\t.globl {n}\n{n}:\n\ts_load_dword s0, s[4:5], 0x0 ; comment\n.LBB{i}_1:\n{body}\ts_cbranch_scc1 .LBB{i}_1\n\ts_endpgm\n"
+                       f"\t.end_amdhsa_kernel\n.Lfunc_end{i}:\n" for i, (n, body) in enumerate(kernels))
+    mul, add = "\tv_mul_f32 v0, v1, v2\n", "\tv_add_f32 v0, v1, v2\n"
+    tool = os.path.join(ROOT, "tools", "isa_diff.py")
+    before = tmp_path / "before.s"
+    before.write_text(asm([("_Z4keepPf", mul), ("_Z3bufILi3ELi0ELb1EEvPf", mul + add), ("_Z5otherPf", add)]))
+    # the translation unit split in two (label numbers restart), one kernel's template parameters changed, every stream as it was
+    fwd, rest = tmp_path / "fwd.s", tmp_path / "rest.s"
+    fwd.write_text(asm([("_Z3bufIL2DP3EEvPf", mul + add)]))
+    rest.write_text(asm([("_Z5otherPf", add), ("_Z4keepPf", mul)]))
+    r = subprocess.run([sys.executable, tool, str(before), "--", str(fwd), str(rest)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "RENAMED  _Z3bufILi3ELi0ELb1EEvPf\n      -> _Z3bufIL2DP3EEvPf" in r.stdout
+    assert "CHANGED" not in r.stdout and "NEW" not in r.stdout and "REMOVED" not in r.stdout
+    assert r.stdout.splitlines()[-1] == "3 -> 3 kernels, 0 changed, 1 renamed"
+    # one instruction of a kernel that kept its name differs: CHANGED, exit status 1; a new name with a new stream is NEW, not RENAMED
+    rest.write_text(asm([("_Z5otherPf", mul), ("_Z4keepPf", mul)]))
+    fwd.write_text(asm([("_Z3bufIL2DP3EEvPf", add + add)]))
+    r = subprocess.run([sys.executable, tool, f"{before}", f"{fwd},{rest}"], capture_output=True, text=True)
+    assert r.returncode == 1
+    assert "CHANGED  _Z5otherPf  (5 -> 5 instructions)" in r.stdout
+    assert "NEW      _Z3bufIL2DP3EEvPf" in r.stdout and "REMOVED  _Z3bufILi3ELi0ELb1EEvPf" in r.stdout and "RENAMED" not in r.stdout

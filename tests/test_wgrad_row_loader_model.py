@@ -1,4 +1,4 @@
-"""CPU model of the weight-gradient row loader's index arithmetic (ddpo_amd/csrc/gemm_bf16.hip, `ROWL`).
+"""CPU model of the weight-gradient row loader's index arithmetic (ddpo_amd/csrc/gemm_bf16_wgrad.hip, `ROWL`).
 
 The kernel keeps the image row / column of a k-tile's first pixel in scalars, gives every thread constant byte offsets relative to the tile
 and advances one scalar offset per tile; a tap outside the image becomes an out-of-range buffer offset.  This test restates exactly that
