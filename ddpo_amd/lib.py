@@ -155,6 +155,10 @@ _SIGS = {
     "ddpo_attention_causal_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ddpo_gather_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "ddpo_cosine_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
+    # JPEG file size without the file (additive to ABI v14; csrc/jpeg_size.hip)
+    "ddpo_jpeg_size_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "ddpo_jpeg_size": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ddpo_jpeg_size_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1638,6 +1642,62 @@ def cosine_rows(a, b, scale=1.0, out=None):
     if out is None:
         out = torch.empty(rows, dtype=torch.float32, device=a.device)
     _check(load().ddpo_cosine_rows(_p(_f32(a, "a")), _p(_f32(b, "b")), rows, cols, float(scale), _p(out), _stream()), "ddpo_cosine_rows")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ JPEG file size
+JPEG_FIXED_BYTES = 625        # DDPO_JPEG_FIXED_BYTES of include/ddpo_hip.h: the bytes of a file that are not entropy-coded data
+JPEG_SIZE_RULE = "height and width must be multiples of 16 (the 4:2:0 MCU): edge replication and dummy blocks are not built"
+
+
+def _jpeg_size_args(shape, quality):
+    if len(shape) != 4 or shape[3] != 3 or shape[0] < 1:
+        raise ValueError(f"jpeg_size needs N x H x W x 3 images, got shape {tuple(shape)}")
+    n, h, w = int(shape[0]), int(shape[1]), int(shape[2])
+    if h < 16 or w < 16 or h % 16 or w % 16:
+        raise ValueError(f"jpeg_size: {h} x {w} images: {JPEG_SIZE_RULE}")
+    if int(quality) != quality or not 1 <= quality <= 100:
+        raise ValueError(f"jpeg_size: quality must be an integer in 1..100, got {quality!r}")
+    return n, h, w, int(quality)
+
+
+def jpeg_size_workspace_bytes(n, h, w):
+    nb = c_size_t(0)
+    rc = load().ddpo_jpeg_size_workspace_bytes(int(n), int(h), int(w), byref(nb))
+    if rc == -1:
+        raise ValueError(f"jpeg_size: {n} images of {h} x {w}: {JPEG_SIZE_RULE}")
+    _check(rc, "ddpo_jpeg_size_workspace_bytes")
+    return int(nb.value)
+
+
+def jpeg_size(images, quality=95, workspace=None, out=None):
+    """len(PIL JPEG bytes at `quality`) of every image of an N x H x W x 3 CUDA tensor — uint8, or float32 in [0, 1] truncated as
+    (x * 255).astype(uint8) — as an int64 CUDA tensor, on the current stream; no file is produced (ddpo_jpeg_size).  H and W must be multiples of 16
+    (ValueError).  `workspace`: a uint8 CUDA tensor of at least jpeg_size_workspace_bytes(N, H, W) bytes; default: this stream's scratch."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype not in (torch.float32, torch.uint8):
+        raise DdpoHipError("jpeg_size needs a float32 or uint8 CUDA tensor")
+    n, h, w, quality = _jpeg_size_args(images.shape, quality)
+    nb = jpeg_size_workspace_bytes(n, h, w)
+    if workspace is None:
+        workspace = _scratch(nb, images.device, "jpeg_size")
+    if workspace.dtype != torch.uint8 or workspace.numel() < nb or workspace.device != images.device:
+        raise DdpoHipError(f"jpeg_size: the workspace must be a uint8 tensor of >= {nb} bytes on {images.device}")
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=images.device)
+    _check(load().ddpo_jpeg_size(_p(images), int(images.dtype == torch.float32), n, h, w, quality, _p(workspace), workspace.numel(), _p(out),
+                                 _stream()), "ddpo_jpeg_size")
+    return out
+
+
+def jpeg_size_host(images_u8, quality=95):
+    """The same count computed serially on the host (ddpo_jpeg_size_host) for a uint8 N x H x W x 3 numpy array: the GPU-free reference."""
+    import numpy as np
+    a = np.ascontiguousarray(images_u8)
+    if a.dtype != np.uint8:
+        raise ValueError("jpeg_size_host needs uint8 images")
+    n, h, w, quality = _jpeg_size_args(a.shape, quality)
+    out = np.zeros(n, dtype=np.int64)
+    _check(load().ddpo_jpeg_size_host(a.ctypes.data_as(c_void_p), n, h, w, quality, out.ctypes.data_as(c_void_p)), "ddpo_jpeg_size_host")
     return out
 
 

@@ -6,9 +6,9 @@ Behavioural mirror of the registry / calling convention of /root/reference/ddpo/
 images: float32 (N,H,W,3) in [0,1]; scores: (N,) or (N,1) numpy; info: dict of numpy arrays.
 Callbacks run in a worker thread of the entrypoint (ThreadPoolExecutor, max_workers=2) next to the sampling of the
 following batch, so they must not touch the sampler's HIP stream: the host ones below are pure CPU code and the
-on-device ones (aesthetic, clip_score) use their own streams.
+on-device ones (aesthetic, clip_score, jpeg_device, neg_jpeg_device) use their own streams.
 
-In scope (BASELINE.json configs): jpeg, neg_jpeg, aesthetic, llava_bertscore (+ its sibling llava_vqa wire format), and clip_score: the
+In scope (BASELINE.json configs): jpeg, neg_jpeg (+ jpeg_device, neg_jpeg_device: the same rewards counted on the device), aesthetic, llava_bertscore (+ its sibling llava_vqa wire format), and clip_score: the
 prompt-alignment reward that needs no server (CLIPScore on the engine's own CLIP towers; not in the reference, which aligns through LLaVA).
 The other reward ideas of the reference (rotational / mirror symmetry, thumbnail, BLIP-2 vqa, ...) are not part of
 any benchmark config; add them as plugins with `register`.
@@ -61,6 +61,35 @@ def neg_jpeg_fn(*a, **kw):
         scores, info = inner(*args, **kwargs)
         return -scores, info
 
+    return _fn
+
+
+def jpeg_device_fn(devices=None, jit=False, quality=95):
+    """`jpeg` computed on the device: the same reward — -(len of PIL's JPEG at quality 95) / 1000, (N,1) float64, equal to `jpeg`'s byte for
+    byte — from the engine's JPEG byte counter (models/jpeg_size.py, csrc/jpeg_size.hip) on a private HIP stream, without producing the files.
+    Takes host images like every callback, or a CUDA tensor straight from the VAE decoder (`wants_device_images`: the entrypoint then keeps the
+    batch in HBM, see evaluate_callbacks_device).  Image height and width must be multiples of 16."""
+    del devices, jit
+    from ..models.jpeg_size import JpegSizer
+    sizer = JpegSizer(quality=quality)
+
+    def _fn(images, prompts, metadata, ready=None):
+        del prompts, metadata
+        return -(sizer(images, ready=ready) / 1000.0)[:, None], {}
+
+    _fn.wants_device_images = True
+    return _fn
+
+
+def neg_jpeg_device_fn(*a, **kw):
+    """`neg_jpeg` computed on the device: +(JPEG size in kB), see jpeg_device_fn."""
+    inner = jpeg_device_fn(*a, **kw)
+
+    def _fn(*args, **kwargs):
+        scores, info = inner(*args, **kwargs)
+        return -scores, info
+
+    _fn.wants_device_images = True
     return _fn
 
 
@@ -175,6 +204,21 @@ def evaluate_callbacks(fns, images, prompts, metadata):
     return {key: fn(images, prompts, metadata) for key, fn in fns.items()}
 
 
+def evaluate_callbacks_device(fns, images_dev, prompts, metadata, ready=None):
+    """evaluate_callbacks for callbacks that carry `wants_device_images`: `images_dev` is the decoder's float32 (N,H,W,3) CUDA tensor and is handed
+    over as it is — nothing is copied to the host.  `ready`: an event recorded on the producing stream when the images were complete (the
+    callbacks' streams wait for it); without one, the caller's current stream as of this call is waited for."""
+    missing = [key for key, fn in fns.items() if not getattr(fn, "wants_device_images", False)]
+    if missing:
+        raise ValueError(f"callbacks {missing} do not take device images; use evaluate_callbacks")
+    if type(prompts[0]) == list:
+        prompts = [random.choice(p) for p in prompts]
+    if ready is None:
+        import torch
+        ready = torch.cuda.current_stream(images_dev.device).record_event()
+    return {key: fn(images_dev, prompts, metadata, ready=ready) for key, fn in fns.items()}
+
+
 def vae_fn(devices=None, dtype="float32", jit=True, encoder=None):
     """The `vae` field of the RWR sampler (reference :37-57): images (N,H,W,3) in [0,1] -> VAE posterior moments
     concat([mean, logvar], -1) (N,H/8,W/8,8) from the engine's VAE encoder (ddpo_amd/models/vae.py:VAEEncoder).  The reference
@@ -204,6 +248,8 @@ callback_fns = {
     "vae": vae_fn,
     "jpeg": jpeg_fn,
     "neg_jpeg": neg_jpeg_fn,
+    "jpeg_device": jpeg_device_fn,
+    "neg_jpeg_device": neg_jpeg_device_fn,
     "aesthetic": aesthetic_fn,
     "clip_score": clip_score_fn,
     "llava_bertscore": llava_bertscore,

@@ -444,6 +444,18 @@ int ddpo_attention_causal_fwd(const float* q, int ldq, const float* k, int ldk, 
 int ddpo_gather_rows(const float* table, int ld, int table_rows, const int32_t* idx, int rows, int cols, const float* add, int add_period,
                      float* out, void* stream);
 int ddpo_cosine_rows(const float* a, const float* b, int rows, int cols, float scale, float* out, void* stream);
+/* JPEG file size without the file (csrc/jpeg_size.hip; additive to ABI v14): bytes_out[n] = len of the baseline JPEG a libjpeg encoder writes for
+ *   image n at `quality` (1..100) with its defaults — 4:2:0, standard Huffman tables, one scan, JFIF header — i.e. what PIL's
+ *   Image.save(buf, "JPEG", quality=q) returns.  images: N x H x W x 3 (NHWC, contiguous), uint8 or (is_float32) float32 in [0, 1], which is
+ *   truncated as (uint8)(x * 255.0f).  H and W must be multiples of 16 (no edge replication / dummy blocks): anything else is DDPO_EINVAL.
+ *   All scratch is the caller's `workspace` (device, >= ddpo_jpeg_size_workspace_bytes, 16-byte aligned); the launch sequence zeroes what it needs
+ *   on `stream`, so calls on different streams with different workspaces may overlap.  ddpo_jpeg_size_host: the same arithmetic, serially, on
+ *   host memory (no GPU).  DDPO_JPEG_FIXED_BYTES: the bytes of such a file that are not entropy-coded data (623 before the scan data + EOI). */
+#define DDPO_JPEG_FIXED_BYTES 625
+int ddpo_jpeg_size_workspace_bytes(int N, int H, int W, size_t* out_host);
+int ddpo_jpeg_size(const void* images, int is_float32, int N, int H, int W, int quality, void* workspace, size_t workspace_bytes,
+                   int64_t* bytes_out, void* stream);
+int ddpo_jpeg_size_host(const uint8_t* rgb, int N, int H, int W, int quality, int64_t* bytes_out_host);
 int ddpo_timestep_embedding(const int32_t* ts, float* out, int B, int dim, void* stream); /* concat([cos, sin]) */
 int ddpo_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, void* stream);
 int ddpo_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, void* stream);

@@ -149,6 +149,8 @@ def main(argv=None):
     # ------------------------------ callbacks -------------------------------#
     callback_fns = {args.filter_field: training.callback_fns[args.filter_field]()}
     executor = futures.ThreadPoolExecutor(max_workers=2)     # rewards run next to the sampling of the following batch
+    # rewards that read the decoder's output where it is (jpeg_device, neg_jpeg_device): the batch stays in HBM, only the inspection PNG's image leaves it
+    device_images = all(getattr(fn, "wants_device_images", False) for fn in callback_fns.values())
 
     per_prompt_stats = None
     if args.per_prompt_stats_bufsize is not None:
@@ -211,10 +213,19 @@ def main(argv=None):
                 dp.sample_key(sample_seeds), args.n_inference_steps, jit=True, height=args.resolution, width=args.resolution,
                 guidance_scale=args.guidance_scale, eta=args.eta)
             # ----------------------------- decode latents ----------------------------- #
-            images = vae.decode(final_latents).cpu().numpy()
+            if device_images:
+                images_dev = vae.decode(final_latents)
+                decoded = torch.cuda.current_stream().record_event()
+                images = images_dev[:1].cpu().numpy()
+            else:
+                images = vae.decode(final_latents).cpu().numpy()
             print(f"[ sample ] epoch {epoch} batch {i}: {len(sample_prompts)} images in {timer():.2f}s")
             # ----------------------------- evaluate callbacks ----------------------------- #
-            callbacks = executor.submit(training.evaluate_callbacks, callback_fns, images, sample_prompts, prompt_metadata)
+            if device_images:
+                callbacks = executor.submit(training.evaluate_callbacks_device, callback_fns, images_dev, sample_prompts, prompt_metadata, decoded)
+                del images_dev
+            else:
+                callbacks = executor.submit(training.evaluate_callbacks, callback_fns, images, sample_prompts, prompt_metadata)
             time.sleep(0)
             samples.append({"prompts": np.array(sample_prompts), "embeds": sample_prompt_embeds, "latents": latents,
                             "next_latents": next_latents, "log_probs": log_probs, "ts": ts, "callbacks": callbacks})
