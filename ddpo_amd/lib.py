@@ -4,6 +4,7 @@ PyTorch is used only as the device allocator / stream provider: every wrapper ta
 their raw device pointers plus the current HIP stream to the C entry point and returns torch tensors.
 There is NO fallback path: if the shared library is missing or a call fails, an exception is raised.
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -279,7 +280,9 @@ def norm_planes(w, cin, rows, training=False):
 
 
 SPLITK_WS_BYTES = 64 << 20       # scratch for the deterministic split-K of under-filled launches
-PACKED = {}          # data_ptr of an fp32 weight tensor -> dict(fwd=(hi, lo, Kp), bwd=(hi, lo) | None, K, N)
+# data_ptr of an fp32 weight tensor -> dict(K, N, fwd=(hi, lo, Kp), bwd=(hi, lo) | None, w_layout) and, where registered: dg (data-gradient planes,
+# _pack_dgrad_planes), mx (f16mx planes, pack_weights), geglu (pack_weights_geglu), fold (pack_weights_up2x_folded)
+PACKED = {}
 
 # Plane-fed GEMMs (bf16x3 datapath): GroupNorm / LayerNorm write their result as bf16
 # hi / lo planes and the consuming conv / linear layers fetch both operands by LDS-DMA (ddpo_gemm_conv_fwd_bf16_planes).
@@ -366,13 +369,33 @@ def planes_ok(w, cin, rows):
     of a convolution's input, M of a dense layer) can take a plane-fed activation: bf16x3 datapath, weight planes registered
     (pack_weights), 32-channel k-tiles that never straddle a tap, and 31-bit byte offsets (the conditions of the
     buffer-addressed kernel, buf_path_ok() in csrc/gemm_bf16.hip — the VAE's 512x512 levels at batch 8 exceed them)."""
-    if not (PLANES and _planes_dp() and cin % 32 == 0):
-        return False
+    return bool(PLANES and _planes_dp() and cin % 32 == 0) and _planes_fit(w, cin, rows)
+
+
+def _planes_fit(w, cin, rows):
+    """What planes_ok and planes_out_ok share: weight planes registered, activation and weight planes within the buffer-addressed kernels' offsets."""
     ent = PACKED.get(w.data_ptr())
-    if ent is None:
-        return False
-    lim = 0x7FFFFFFF
-    return rows * cin * 4 < lim and ent["N"] * ent["fwd"][2] * 2 < lim
+    return ent is not None and _fits_buf(rows * cin * 4, ent["N"] * ent["fwd"][2] * 2)
+
+
+def _buf_room(unit_bytes=1):
+    """How many units of `unit_bytes` an operand of the buffer-addressed kernels can hold: their byte offsets are 31-bit (buf_path_ok() in
+    csrc/gemm_bf16.hip)."""
+    return (0x7FFFFFFF - 1) // unit_bytes
+
+
+def _fits_buf(*nbytes):
+    """True when operands of these byte counts all fit the buffer-addressed kernels.  Every count asked about is a multiple of 4 (fp32 elements,
+    16-bit planes of a multiple of 8 columns), so `< 0x7FFFFFFF` here and `< 1 << 31` are the same statement."""
+    return all(n <= _buf_room() for n in nbytes)
+
+
+def _tall_tiles_fill(rows, N):
+    """The tall-tile fill rule of the C++ dispatch (dispatch_bf16): the grid of 256 x 320 tiles over `rows` x N has at least 200 tiles and fills its
+    rounds of 256 CUs within 8 % of the 128 x 320 grid's efficiency."""
+    ntall, nwide = -(-rows // 256) * (N // 320), -(-rows // 128) * (N // 320)
+    eff = lambda n: n / (-(-n // 256) * 256)
+    return ntall >= 200 and eff(ntall) * 1.08 >= eff(nwide)
 
 
 def planes_pay(w, cin, rows):
@@ -392,12 +415,11 @@ def planes_pay(w, cin, rows):
         # single-pass bf16 (round 6): the fp32-fed single-pass kernels already run the long reductions at 750-980 TF; the plane-fed form wins only
         # where the 256 x 320 tile with the four-stage ring (APL = 8) takes the layer — 1.15-1.27x on the 64x64-level convolutions of SD-1.5,
         # 1.12x on SD-2.1's 960-column projection — and loses 5-10 % on the 128-row tiles (profiles/r06_breakdown_bf16_planes.log).  Same rule as
-        # the C++ dispatch (dispatch_bf16: >= 200 tall tiles, round efficiency within 8 % of the 128 x 320 grid's), and K >= 1280.
+        # the C++ dispatch (_tall_tiles_fill), and K >= 1280.
+        # KNOWN DIFFERENCE from the dispatcher (advisor finding, left as it is here): the rule is asked about SOURCE rows, the dispatcher uses
+        # output rows — an up-sampling convolution has 4x as many, a stride-2 one a quarter.
         N, K = ent["N"], ent["K"]
-        m_out = rows                         # (source rows: an up-sampling convolution has 4x the output rows — it only gains more)
-        ntall, nwide = -(-m_out // 256) * (N // 320), -(-m_out // 128) * (N // 320)
-        eff = lambda n: n / (-(-n // 256) * 256) if n else 0.0
-        return 1 if (N % 320 == 0 and K >= 1280 and ntall >= 200 and eff(ntall) * 1.08 >= eff(nwide)) else 0
+        return 1 if (N % 320 == 0 and K >= 1280 and _tall_tiles_fill(rows, N)) else 0
     return 1 if (ent["K"] >= 2560 or rows >= 32768) else 0
 
 
@@ -405,13 +427,7 @@ def planes_out_ok(w, cin, rows, N):
     """True when the GEMM / conv with weight `w` (reduction channels per tap `cin`, `rows` source rows, N output columns) runs on a
     buffer-addressed bf16x3 kernel, i.e. can emit its result as planes (ddpo_gemm_desc.out_hi): the conditions of planes_ok()
     except that the ACTIVATION may be fp32 (then only K % 32 and the 31-bit offsets matter), plus N % 4 == 0."""
-    if not (PLANES and PLANES_OUT and _planes_dp() and cin % 32 == 0 and N % 4 == 0):
-        return False
-    ent = PACKED.get(w.data_ptr())
-    if ent is None:
-        return False
-    lim = 0x7FFFFFFF
-    return rows * cin * 4 < lim and ent["N"] * ent["fwd"][2] * 2 < lim
+    return bool(PLANES and PLANES_OUT and _planes_dp() and cin % 32 == 0 and N % 4 == 0) and _planes_fit(w, cin, rows)
 
 
 def split_planes(x, fmt=0):
@@ -458,27 +474,13 @@ def gemm_conv_f16mx(planes, wp, *, M, bias=None, residual=None, conv=None, out=N
     planes_out: also return the result as f16mx planes (p16, p8) written by the output stage."""
     p16, p8 = planes
     N, K = wp["N"], wp["K"]
-    d = GemmDesc()
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=p16.device)
-    d.out = out.data_ptr(); d.ld_out = N
-    d.bias = bias.data_ptr() if bias is not None else None
-    if residual is not None:
-        d.residual = residual.data_ptr(); d.ld_res = N
-    d.alpha = 1.0
-    d.M, d.N, d.K = int(M), int(N), int(K)
-    d.w_layout = 1
-    d.w_scale = wp["scale"].data_ptr()
-    if conv:
-        for k in ("ksize", "stride", "pad", "upsample", "B", "H", "W", "Cin", "OH", "OW"):
-            setattr(d, k, int(conv[k]))
     opl = None
     if planes_out:
         opl = (torch.empty(M, N, dtype=torch.int16, device=p16.device), torch.empty(M, N // 32, 64, dtype=torch.uint8, device=p16.device))
-        d.out_hi, d.out_lo, d.ld_planes, d.planes_fmt = opl[0].data_ptr(), opl[1].data_ptr(), N, 1
-    ws = _scratch(SPLITK_WS_BYTES, p16.device, "splitk")
-    _check(load().ddpo_gemm_conv_fwd_f16mx_planes(byref(d), _p(p16), _p(p8), int(p16.shape[1]), _p(wp["w16"]), _p(wp["w8"]), _p(ws), SPLITK_WS_BYTES,
-                                                  _stream()), "ddpo_gemm_conv_fwd_f16mx_planes")
+    d = _gemm_desc(M, N, K, conv=conv, out=out, bias=bias, residual=residual, out_planes=opl and (opl[0], opl[1], N, 1))
+    _launch_fwd(d, (p16, p8, int(p16.shape[1])), wp, cross=True, ws_device=p16.device)       # (the raw operator: cross terms whatever MX_CROSS says)
     return (out, opl) if planes_out else out
 
 
@@ -492,9 +494,8 @@ TILE_CLASSES = ("tall_256x320", "wide_128x320", "t128x128", "t128x64", "generic_
 
 def gemm_tile_launch_counts():
     """Cumulative host-side launch counts of the bf16-MFMA GEMM / conv template per tile class (ddpo_gemm_tile_launch_counts)."""
-    import ctypes as _ct
-    buf = (_ct.c_ulonglong * 8)()
-    _check(load().ddpo_gemm_tile_launch_counts(_ct.cast(buf, c_void_p), 8), "ddpo_gemm_tile_launch_counts")
+    buf = (ctypes.c_ulonglong * 8)()
+    _check(load().ddpo_gemm_tile_launch_counts(ctypes.cast(buf, c_void_p), 8), "ddpo_gemm_tile_launch_counts")
     return dict(zip(TILE_CLASSES, (int(v) for v in buf)))
 
 
@@ -693,6 +694,93 @@ def _scratch(nbytes, device, tag):
     return ws
 
 
+def _conv_geom(B, H, W, Cin, ksize, stride, pad, upsample):
+    """The conv dict of gemm_conv / gemm_wgrad (ddpo_gemm_desc's geometry fields); pad None = ksize // 2.  upsample: 0 / 1 = nearest 2x gather,
+    2 = zero insertion (the transposed view of a stride-2 convolution, conv2d_dgrad)."""
+    if pad is None:
+        pad = ksize // 2
+    VH, VW = (2 * H, 2 * W) if upsample else (H, W)
+    OH = (VH + 2 * pad - ksize) // stride + 1
+    OW = (VW + 2 * pad - ksize) // stride + 1
+    return dict(ksize=ksize, stride=stride, pad=pad, upsample=int(upsample), B=B, H=H, W=W, Cin=Cin, OH=OH, OW=OW)
+
+
+def _gemm_desc(M, N, K, *, conv=None, src=None, ld_src=0, out=None, ld_out=None, bias=None, residual=None, ld_res=None, res_rows=0, alpha=1.0,
+               out_planes=None, aux_out=None, **fields):
+    """A ddpo_gemm_desc: what is not given stays zero / NULL.  conv: the geometry fields by name (_conv_geom); ld_out / ld_res default to N;
+    out_planes = (hi, lo, ld_planes, planes_fmt) of a plane-emitting output stage; **fields: any other field of the structure, as its raw value."""
+    d = GemmDesc()
+    d.M, d.N, d.K = int(M), int(N), int(K)
+    d.alpha = float(alpha)
+    for k, v in (conv or {}).items():
+        setattr(d, k, int(v))
+    if src is not None:
+        d.src = src.data_ptr()
+    d.ld_src = int(ld_src)
+    if out is not None:
+        d.out = out.data_ptr(); d.ld_out = int(ld_out if ld_out is not None else N)
+    d.bias = bias.data_ptr() if bias is not None else None
+    if residual is not None:
+        d.residual = residual.data_ptr(); d.ld_res = int(ld_res if ld_res is not None else N)
+    d.res_rows = int(res_rows)
+    if out_planes is not None:
+        hi, lo, d.ld_planes, d.planes_fmt = out_planes
+        d.out_hi, d.out_lo = hi.data_ptr(), lo.data_ptr()
+    d.aux_out = aux_out.data_ptr() if aux_out is not None else None
+    for k, v in fields.items():
+        setattr(d, k, v)
+    return d
+
+
+def _launch_fwd(d, act, weights, *, w_layout=0, cross=None, ws_device=None, tag=""):
+    """The one forward launch: picks the entry point from the operands.
+    act: None (fp32-fed: the activation is d.src), `Planes`, or (hi, lo, ld) plane tensors.
+    weights: None -> exact fp32 (ddpo_gemm_conv_fwd reads d.w); (hi, lo, ldw, npass) bf16 planes stored as `w_layout`; dict(w16, w8, scale) f16mx.
+    A single bf16 pass (npass 1) reads the hi planes only: both lo pointers NULL on the plane-fed entry.  f16mx without its cross terms (`cross`,
+    default MX_CROSS): both 8-bit planes NULL.  ws_device: fetch the split-K scratch there and pass it; None: no workspace (no split-K).
+    tag: appended to the symbol in the error message."""
+    lib = load()
+    a_hi, a_lo, a_ld = (act.hi, act.lo, act.ld) if isinstance(act, Planes) else (act or (None, None, 0))
+    ws = None if ws_device is None else _scratch(SPLITK_WS_BYTES, ws_device, "splitk")
+    ws_args = (_p(ws), SPLITK_WS_BYTES if ws is not None else 0, _stream())
+    if weights is None:
+        name, rc = "ddpo_gemm_conv_fwd", lib.ddpo_gemm_conv_fwd(byref(d), _stream())
+    elif isinstance(weights, dict):
+        cross = MX_CROSS if cross is None else cross
+        d.w_layout = 1
+        d.w_scale = weights["scale"].data_ptr()
+        name, rc = "ddpo_gemm_conv_fwd_f16mx_planes", lib.ddpo_gemm_conv_fwd_f16mx_planes(
+            byref(d), _p(a_hi), _p(a_lo) if cross else None, a_ld, _p(weights["w16"]), _p(weights["w8"]) if cross else None, *ws_args)
+    else:
+        hi, lo, ldw, npass = weights
+        d.w_layout = w_layout
+        if a_hi is None:
+            name, rc = "ddpo_gemm_conv_fwd_bf16", lib.ddpo_gemm_conv_fwd_bf16(byref(d), _p(hi), _p(lo), ldw, npass, *ws_args)
+        else:
+            one = npass == 1
+            name, rc = "ddpo_gemm_conv_fwd_bf16_planes", lib.ddpo_gemm_conv_fwd_bf16_planes(
+                byref(d), _p(a_hi), None if one else _p(a_lo), a_ld, _p(hi), None if one else _p(lo), ldw, *ws_args)
+    _check(rc, name + tag)
+
+
+def _family(fp32=False, mx=False):
+    """Family tag of a PROFILE entry: "fp32" (exact-fp32 kernel), "f16mx" (the launch ran the f16 + MX-fp8 kernel), else the bf16 datapath's name."""
+    return "fp32" if fp32 else ("f16mx" if mx else ("bf16x3" if _x3() else current_datapath()))
+
+
+@contextlib.contextmanager
+def _profiled(flops, io_bytes, family):
+    """While PROFILE is a list: brackets the launch(es) inside with two events and appends (start, end, algorithmic flops, family, unique operand bytes)."""
+    if PROFILE is None:
+        yield
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    yield
+    e1.record()
+    PROFILE.append((e0, e1, flops, family, io_bytes))
+
+
 def groupnorm(x, B, HW, gamma, beta, groups, eps, silu, out=None, ld_x=None, ld_out=None, return_stats=False, planes=False):
     """x: (B*HW, C) NHWC rows (row stride ld_x).  Returns (B*HW, C) [and the saved statistics for the backward].
     planes (the value of planes_pay / norm_planes for the consumer; 1 / True = bf16 hi / lo, 2 = f16mx): the result comes back as `Planes`
@@ -700,22 +788,19 @@ def groupnorm(x, B, HW, gamma, beta, groups, eps, silu, out=None, ld_x=None, ld_
     C = gamma.numel()
     if ld_x is None and x.dim() == 2 and x.stride(0) != C:          # a column slice of a wider row-major buffer (skip-concat storage)
         ld_x = x.stride(0)
-    _p = _p_rows if ld_x else globals()["_p"]
     if planes:
         pl = Planes(B * HW, C, x.device, fmt=1 if planes == 2 else 0)
         ws = _scratch(load().ddpo_groupnorm_ws_bytes(B, HW, C, groups), x.device, "gn")
         stats = torch.empty(load().ddpo_groupnorm_stats_floats(B, C, groups), dtype=torch.float32, device=x.device)
-        _p2 = globals()["_p"]
-        _check(load().ddpo_groupnorm_fwd_planes(_p(x), int(ld_x or C), _p2(pl.hi), _p2(pl.lo), pl.ld, _p2(gamma), _p2(beta), B, HW, C, groups,
-                                                float(eps), int(bool(silu)) | (2 * pl.fmt), _p2(ws), _p2(stats), _stream()), "ddpo_groupnorm_fwd_planes")
+        _check(load().ddpo_groupnorm_fwd_planes(_pr(x, ld_x), int(ld_x or C), _p(pl.hi), _p(pl.lo), pl.ld, _p(gamma), _p(beta), B, HW, C, groups,
+                                                float(eps), int(bool(silu)) | (2 * pl.fmt), _p(ws), _p(stats), _stream()), "ddpo_groupnorm_fwd_planes")
         return (pl, stats) if return_stats else pl
     if out is None:
         out = torch.empty(B * HW, C, dtype=torch.float32, device=x.device)
     ws = _scratch(load().ddpo_groupnorm_ws_bytes(B, HW, C, groups), x.device, "gn")
     stats = torch.empty(load().ddpo_groupnorm_stats_floats(B, C, groups), dtype=torch.float32, device=x.device)
-    _p2 = globals()["_p"]
-    _check(load().ddpo_groupnorm_fwd(_p(x), int(ld_x or C), _p2(out), int(ld_out or C), _p2(gamma), _p2(beta), B, HW, C, groups,
-                                     float(eps), int(bool(silu)), _p2(ws), _p2(stats), _stream()), "ddpo_groupnorm_fwd")
+    _check(load().ddpo_groupnorm_fwd(_pr(x, ld_x), int(ld_x or C), _p(out), int(ld_out or C), _p(gamma), _p(beta), B, HW, C, groups,
+                                     float(eps), int(bool(silu)), _p(ws), _p(stats), _stream()), "ddpo_groupnorm_fwd")
     return (out, stats) if return_stats else out
 
 
@@ -882,8 +967,7 @@ def up2x_fold_ok(w, cin, rows):
         return False
     if _mx() and fo["K"] >= MX_MIN_K and "mx" not in fo:      # packed under another datapath: no f16mx planes for an f16mx layer
         return False
-    lim = 0x7FFFFFFF
-    return rows * cin * 4 < lim and 4 * fo["N"] * fo["K"] * 2 < lim and rows * 4 < lim
+    return _fits_buf(rows * cin * 4, 4 * fo["N"] * fo["K"] * 2, rows * 4)
 
 
 def up2x_planes_pay(w, cin, rows):
@@ -918,16 +1002,7 @@ def conv2d_up2x_folded(x, w, bias, B, H, W, Cin, Cout, out=None, ld_out=None):
     M = 4 * rows
     if out is None:
         out = torch.empty(M, Cout, dtype=torch.float32, device=pl.device)
-    d = GemmDesc()
-    d.bias = bias.data_ptr() if bias is not None else None
-    d.out = out.data_ptr(); d.ld_out = int(ld_out if ld_out is not None else Cout)
-    d.alpha = 1.0
-    d.N = int(Cout)
-    d.B, d.H, d.W, d.Cin = int(B), int(H), int(W), int(Cin)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    ws = _scratch(SPLITK_WS_BYTES, pl.device, "splitk")
+    d = _gemm_desc(0, Cout, 0, conv=dict(B=B, H=H, W=W, Cin=Cin), out=out, ld_out=ld_out, bias=bias)      # (M, K and the taps are the kernel's own)
     one = not _x3()
     if mxl:
         m = fo["mx"]
@@ -935,13 +1010,12 @@ def conv2d_up2x_folded(x, w, bias, B, H, W, Cin, Cout, out=None, ld_out=None):
         wh, wl = m["w16"], m["w8"]
     else:
         wh, wl = fo["hi"], (None if one else fo["lo"])
-    _check(load().ddpo_conv_up2x_folded_fwd(byref(d), _p(pl.hi), None if (one and not mxl) else _p(pl.lo), pl.ld, _p(wh), None if wl is None else _p(wl),
-                                            int(mxl), _p(ws), SPLITK_WS_BYTES, _stream()), "ddpo_conv_up2x_folded_fwd")
-    if PROFILE is not None:
-        e1.record()
-        K = 4 * Cin                          # the FLOPs actually executed: 2 * M * 4 Cin * N
-        io_bytes = 4.0 * rows * Cin + (4.0 if _x3() else 2.0) * 4 * K * Cout + 4.0 * M * Cout
-        PROFILE.append((e0, e1, 2.0 * M * Cout * K, "f16mx" if mxl else ("bf16x3" if _x3() else current_datapath()), io_bytes))
+    K = 4 * Cin                              # the FLOPs actually executed: 2 * M * 4 Cin * N
+    io_bytes = 4.0 * rows * Cin + (4.0 if _x3() else 2.0) * 4 * K * Cout + 4.0 * M * Cout
+    with _profiled(2.0 * M * Cout * K, io_bytes, _family(mx=mxl)):
+        ws = _scratch(SPLITK_WS_BYTES, pl.device, "splitk")
+        _check(load().ddpo_conv_up2x_folded_fwd(byref(d), _p(pl.hi), None if (one and not mxl) else _p(pl.lo), pl.ld, _p(wh), None if wl is None else _p(wl),
+                                                int(mxl), _p(ws), SPLITK_WS_BYTES, _stream()), "ddpo_conv_up2x_folded_fwd")
     return out, 2 * H, 2 * W
 
 
@@ -972,46 +1046,30 @@ def _dgrad_fwd(dy, dg, *, M, conv=None, residual=None, ld_res=None, out=None):
     Kd, Nd = dg["K"], dg["N"]
     cin = conv["Cin"] if conv else Kd
     rows = conv["B"] * conv["H"] * conv["W"] if conv else M
-    lim = 0x7FFFFFFF
-    if conv is None and rows * cin * 4 >= lim and not isinstance(dy, Planes):
+    if conv is None and not _fits_buf(rows * cin * 4) and not isinstance(dy, Planes):
         # a dense dY of >= 2 GiB (FF1's (M, 8C) gradient at training batch sizes) would leave the buffer-addressed kernels: run it in row chunks
         # (the chunk is rounded DOWN to whole 256-row tiles so that it stays below the limit and can never re-enter this branch)
-        step = (lim - 1) // (cin * 4) // 256 * 256
+        step = _buf_room(cin * 4) // 256 * 256
         if step <= 0:
             raise DdpoHipError(f"_dgrad_fwd: one 256-row chunk of a {cin}-wide dY does not fit the buffer-addressed kernels")
         if out is None:
             out = torch.empty(M, Nd, dtype=torch.float32, device=dy.device)
         for r0 in range(0, rows, step):
             r1 = min(rows, r0 + step)
-            assert (r1 - r0) * cin * 4 < lim
+            assert _fits_buf((r1 - r0) * cin * 4)
             _dgrad_fwd(dy[r0:r1], dg, M=r1 - r0, residual=None if residual is None else residual[r0:r1], ld_res=ld_res, out=out[r0:r1])
         return out
-    buf_ok = cin % 32 == 0 and rows * cin * 4 < lim and Nd * ((Kd + 31) // 32 * 32) * 2 < lim
+    buf_ok = cin % 32 == 0 and _fits_buf(rows * cin * 4, Nd * ((Kd + 31) // 32 * 32) * 2)
     pl = dy if isinstance(dy, Planes) else None
     if pl is not None and (pl.fmt != 0 or not buf_ok):
         dy, pl = pl.float(), None
     if pl is None and buf_ok and PLANES and (Kd >= 2560 or PLANES_ALL):
         pl = split_planes(dy)                # bf16 hi / lo planes, whatever the datapath (see _pack_dgrad_planes)
-    d = GemmDesc()
     dev = pl.device if pl is not None else dy.device
     if out is None:
         out = torch.empty(M, Nd, dtype=torch.float32, device=dev)
-    if residual is not None:
-        d.residual = residual.data_ptr(); d.ld_res = int(ld_res if ld_res is not None else Nd)
-    d.out = out.data_ptr(); d.ld_out = int(Nd)
-    d.alpha = 1.0
-    d.M, d.N, d.K = int(M), int(Nd), int(Kd)
-    d.w_layout = 1
-    if conv:
-        for k in ("ksize", "stride", "pad", "upsample", "B", "H", "W", "Cin", "OH", "OW"):
-            setattr(d, k, int(conv[k]))
-    ws = _scratch(SPLITK_WS_BYTES, dev, "splitk")
-    if pl is not None:
-        _check(load().ddpo_gemm_conv_fwd_bf16_planes(byref(d), _p(pl.hi), _p(pl.lo), pl.ld, _p(dg["hi"]), _p(dg["lo"]), 0, _p(ws), SPLITK_WS_BYTES, _stream()),
-               "ddpo_gemm_conv_fwd_bf16_planes(dgrad)")
-    else:
-        d.src = dy.data_ptr(); d.ld_src = int(cin)
-        _check(load().ddpo_gemm_conv_fwd_bf16(byref(d), _p(dg["hi"]), _p(dg["lo"]), 0, 3, _p(ws), SPLITK_WS_BYTES, _stream()), "ddpo_gemm_conv_fwd_bf16(dgrad)")
+    d = _gemm_desc(M, Nd, Kd, conv=conv, src=None if pl is not None else dy, ld_src=0 if pl is not None else cin, out=out, residual=residual, ld_res=ld_res)
+    _launch_fwd(d, pl, (dg["hi"], dg["lo"], 0, 3), w_layout=1, ws_device=dev, tag="(dgrad)")
     return out
 
 
@@ -1064,19 +1122,17 @@ def pack_weights_geglu(w, bias):
 
 def geglu_tall_pays(w, rows):
     """True when the fused FF1 + GEGLU of weight `w` on `rows` rows should run on the 256 x 320 tile (epilogue = 2): registered with the tall column
-    order and the grid of tall tiles fills whole rounds of the 256 CUs well — the same rule as the C++ dispatch
-    applies to the plain tall tile (>= 200 tiles, round efficiency within 8 % of the 128 x 320 grid's).  The caller then feeds bf16 hi / lo PLANES
+    order and the grid of tall tiles fills whole rounds of the 256 CUs well — the rule the C++ dispatch
+    applies to the plain tall tile (_tall_tiles_fill).  The caller then feeds bf16 hi / lo PLANES
     (LayerNorm `planes=1`).  Why: at K = 320 .. 1280 the 128 x 128 GEGLU tile streams 16 MAC per operand byte and FF1 sits on the chip's L2 -> LDS
     stream (3.3 GB per launch at the 64 x 64 level = 8 TB/s); the tall tile moves 35 MAC per byte."""
     ent = PACKED.get(w.data_ptr())
     if not (GEGLU_TALL and PLANES and _x3() and ent is not None and "geglu" in ent and not ent["geglu"]["stale"] and "tall" in ent["geglu"]):
         return False
     K, N = ent["K"], ent["N"]
-    if rows * K * 4 >= 0x7FFFFFFF or K % 32:
+    if not _fits_buf(rows * K * 4) or K % 32:
         return False
-    ntall, nwide = -(-rows // 256) * (N // 320), -(-rows // 128) * (N // 320)
-    eff = lambda n: n / (-(-n // 256) * 256)
-    return ntall >= 200 and eff(ntall) * 1.08 >= eff(nwide)
+    return _tall_tiles_fill(rows, N)
 
 
 def linear_geglu(x, w, out=None, planes_out=False, pre_out=False):
@@ -1090,7 +1146,7 @@ def linear_geglu(x, w, out=None, planes_out=False, pre_out=False):
     g = ent["geglu"]
     M, K = x.shape
     N = w.shape[1]
-    if (M * K * 4) >= (1 << 31):
+    if not _fits_buf(M * K * 4):
         return None
     pl = x if isinstance(x, Planes) else None
     mxl = _mx() and "mx" in g
@@ -1099,49 +1155,25 @@ def linear_geglu(x, w, out=None, planes_out=False, pre_out=False):
     if pl is not None and (not _planes_dp() or K % 32 or (pl.fmt == 1) != mxl):
         raise DdpoHipError("plane-fed linear_geglu needs the bf16x3 / f16mx datapath, K % 32 == 0 and planes of the layer's format "
                            "(ask planes_pay / norm_planes for it)")
-    d = GemmDesc()
     opl = None
     if planes_out:
         if not _planes_dp():
             raise DdpoHipError("plane-emitting linear_geglu needs the bf16x3 / f16mx datapath")
         opl = Planes(M, N // 2, x.device, fmt=1 if planes_out == 2 else 0)            # planes_out = the CONSUMER's planes_pay value
-        d.out_hi, d.out_lo, d.ld_planes, d.planes_fmt = opl.hi.data_ptr(), opl.lo.data_ptr(), opl.ld, opl.fmt
-    else:
-        if out is None:
-            out = torch.empty(M, N // 2, dtype=torch.float32, device=x.device)
-        d.out = out.data_ptr(); d.ld_out = N // 2
+    elif out is None:
+        out = torch.empty(M, N // 2, dtype=torch.float32, device=x.device)
     tall = pl is not None and pl.fmt == 0 and geglu_tall_pays(w, M)
     gw = g["tall"] if tall else g
-    d.src = x.data_ptr(); d.ld_src = K
-    d.bias = gw["bias"].data_ptr()
-    d.alpha = 1.0
-    d.M, d.N, d.K = int(M), int(N), int(K)
-    d.epilogue = 2 if tall else 1
-    d.w_layout = 1 if tall else g["w_layout"]
-    pre = None
-    if pre_out:
-        pre = torch.empty(M, N, dtype=torch.float32, device=x.device)
-        d.aux_out = pre.data_ptr()
-    npass = 3 if _x3() else 1
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if pl is not None and pl.fmt == 1:
-        m = g["mx"]
-        d.w_layout = 1
-        d.w_scale = m["scale"].data_ptr()
-        _check(load().ddpo_gemm_conv_fwd_f16mx_planes(byref(d), _p(pl.hi), _p(pl.lo) if MX_CROSS else None, pl.ld, _p(m["w16"]), _p(m["w8"]) if MX_CROSS else None,
-                                                      None, 0, _stream()), "ddpo_gemm_conv_fwd_f16mx_planes")
-    elif pl is not None:
-        one = npass == 1
-        _check(load().ddpo_gemm_conv_fwd_bf16_planes(byref(d), _p(pl.hi), None if one else _p(pl.lo), pl.ld, _p(gw["hi"]), None if one else _p(gw["lo"]), K,
-                                                     None, 0, _stream()), "ddpo_gemm_conv_fwd_bf16_planes")
-    else:
-        _check(load().ddpo_gemm_conv_fwd_bf16(byref(d), _p(g["hi"]), _p(g["lo"]), K, npass, None, 0, _stream()), "ddpo_gemm_conv_fwd_bf16")
-    if PROFILE is not None:
-        e1.record()
-        fam = "f16mx" if (pl is not None and pl.fmt == 1) else ("bf16x3" if _x3() else current_datapath())
-        PROFILE.append((e0, e1, 2.0 * M * N * K, fam, 4.0 * (M * K + K * N + M * N // 2)))
+    pre = torch.empty(M, N, dtype=torch.float32, device=x.device) if pre_out else None
+    d = _gemm_desc(M, N, K, src=x, ld_src=K, out=None if planes_out else out, ld_out=N // 2, bias=gw["bias"], aux_out=pre,
+                   out_planes=opl and (opl.hi, opl.lo, opl.ld, opl.fmt), epilogue=2 if tall else 1)
+    with _profiled(2.0 * M * N * K, 4.0 * (M * K + K * N + M * N // 2), _family(mx=mxl)):     # (past the checks above, mxl = "pl holds f16mx planes")
+        if mxl:
+            _launch_fwd(d, pl, g["mx"])
+        elif pl is not None:
+            _launch_fwd(d, pl, (gw["hi"], gw["lo"], K, 3 if _x3() else 1), w_layout=1 if tall else g["w_layout"])
+        else:
+            _launch_fwd(d, None, (g["hi"], g["lo"], K, 3 if _x3() else 1), w_layout=g["w_layout"])
     res = opl if planes_out else out
     return (res, pre) if pre_out else res
 
@@ -1194,68 +1226,35 @@ def gemm_conv(src, w, *, M, N, K, bias=None, rowbias=None, rows_per_batch=0, res
             ld_src = None
     if pl is not None and (pl.fmt == 1) != bool(mxl):
         raise DdpoHipError("activation planes of the wrong format for this layer (ask planes_pay / norm_planes: 1 = bf16 hi / lo, 2 = f16mx)")
-    d = GemmDesc()
-    d.src = src.data_ptr(); d.ld_src = int(ld_src if ld_src is not None else (conv["Cin"] if conv else K))
-    d.w = w.data_ptr(); d.w_trans = int(bool(w_trans))
-    d.bias = bias.data_ptr() if bias is not None else None
-    if rowbias is not None:
-        d.rowbias = rowbias.data_ptr(); d.rows_per_batch = int(rows_per_batch); d.ld_rowbias = int(rowbias.shape[-1])
     opl = None
     if planes_out is not None:
         if planes_out not in ("both", "only"):
             raise ValueError(planes_out)
         opl = Planes(M, N, src.device, fmt=1 if planes_fmt == 2 else 0)
-        d.out_hi, d.out_lo, d.ld_planes, d.planes_fmt = opl.hi.data_ptr(), opl.lo.data_ptr(), opl.ld, opl.fmt
     if out is None and planes_out != "only":
         out = torch.empty(M, N, dtype=torch.float32, device=src.device)
-    if residual is not None:
-        d.residual = residual.data_ptr(); d.ld_res = int(ld_res if ld_res is not None else N)
-    d.res_rows = int(res_rows)
-    if out is not None:
-        d.out = out.data_ptr(); d.ld_out = int(ld_out if ld_out is not None else N)
-    d.alpha = float(alpha)
-    d.M, d.N, d.K = int(M), int(N), int(K)
-    if conv:
-        for k in ("ksize", "stride", "pad", "upsample", "B", "H", "W", "Cin", "OH", "OW"):
-            setattr(d, k, int(conv[k]))
+    cin = conv["Cin"] if conv else K
+    d = _gemm_desc(M, N, K, conv=conv, src=src, ld_src=ld_src if ld_src is not None else cin, out=out, ld_out=ld_out, bias=bias, residual=residual,
+                   ld_res=ld_res, res_rows=res_rows, alpha=alpha, out_planes=opl and (opl.hi, opl.lo, opl.ld, opl.fmt),
+                   w=w.data_ptr(), w_trans=int(bool(w_trans)))
+    if rowbias is not None:
+        d.rowbias = rowbias.data_ptr(); d.rows_per_batch = int(rows_per_batch); d.ld_rowbias = int(rowbias.shape[-1])
     route = None if w_trans else _bf16_route(w, K, N, conv, False)
-    if route is not None:
-        d.w_layout = PACKED[w.data_ptr()].get("w_layout", 0)
     if opl is not None and (route is None or not _planes_dp()):
         raise DdpoHipError("a plane-emitting GEMM needs the bf16x3 / f16mx datapath and registered weight planes (check planes_out_ok)")
-    if pl is not None and (route is None or not _planes_dp() or (conv["Cin"] if conv else K) % 32 or ld_src is not None):
+    if pl is not None and (route is None or not _planes_dp() or cin % 32 or ld_src is not None):
         raise DdpoHipError("a plane-fed GEMM needs the bf16x3 / f16mx datapath, registered weight planes (of the planes' format) and 32-channel "
                            "k-tiles (check planes_ok before asking a producer for planes)")
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if pl is not None and pl.fmt == 1:
-        m = PACKED[w.data_ptr()]["mx"]
-        d.w_layout = 1
-        d.w_scale = m["scale"].data_ptr()
-        ws = _scratch(SPLITK_WS_BYTES, src.device, "splitk")
-        _check(load().ddpo_gemm_conv_fwd_f16mx_planes(byref(d), _p(pl.hi), _p(pl.lo) if MX_CROSS else None, pl.ld, _p(m["w16"]), _p(m["w8"]) if MX_CROSS else None,
-                                                      _p(ws), SPLITK_WS_BYTES, _stream()), "ddpo_gemm_conv_fwd_f16mx_planes")
-    elif pl is not None:
-        hi, lo, ldw, npass = route
-        ws = _scratch(SPLITK_WS_BYTES, src.device, "splitk")
-        one = npass == 1                      # single-pass bf16: the hi planes only (ABI v14: both lo pointers NULL)
-        _check(load().ddpo_gemm_conv_fwd_bf16_planes(byref(d), _p(pl.hi), None if one else _p(pl.lo), pl.ld, _p(hi), None if one else _p(lo), ldw, _p(ws),
-                                                     SPLITK_WS_BYTES, _stream()), "ddpo_gemm_conv_fwd_bf16_planes")
-    elif route is not None:
-        hi, lo, ldw, npass = route
-        ws = _scratch(SPLITK_WS_BYTES, src.device, "splitk")
-        _check(load().ddpo_gemm_conv_fwd_bf16(byref(d), _p(hi), _p(lo), ldw, npass, _p(ws), SPLITK_WS_BYTES, _stream()), "ddpo_gemm_conv_fwd_bf16")
-    else:
-        _check(load().ddpo_gemm_conv_fwd(byref(d), _stream()), "ddpo_gemm_conv_fwd")
-    if PROFILE is not None:
-        e1.record()
-        a_bytes = 4.0 * (conv["B"] * conv["H"] * conv["W"] * conv["Cin"] if conv else M * K)       # unique operand bytes
-        w_bytes = (4.0 if route is None else (4.0 if _x3() else 2.0)) * K * N
-        io_bytes = a_bytes + w_bytes + 4.0 * N * (M + (0 if residual is None else (res_rows or M)))      # a periodic residual is read once per period
-        # family tag: "fp32" (exact-fp32 kernel), "f16mx" (this launch ran the f16 + MX-fp8 kernel), else the bf16 datapath's name
-        fam = "fp32" if route is None else ("f16mx" if (pl is not None and pl.fmt == 1) else ("bf16x3" if _x3() else current_datapath()))
-        PROFILE.append((e0, e1, 2.0 * M * N * K, fam, io_bytes))
+    a_bytes = 4.0 * (conv["B"] * conv["H"] * conv["W"] * conv["Cin"] if conv else M * K)       # unique operand bytes
+    w_bytes = (4.0 if route is None else (4.0 if _x3() else 2.0)) * K * N
+    io_bytes = a_bytes + w_bytes + 4.0 * N * (M + (0 if residual is None else (res_rows or M)))      # a periodic residual is read once per period
+    with _profiled(2.0 * M * N * K, io_bytes, _family(fp32=route is None, mx=mxl)):            # (past the checks above, mxl = "pl holds f16mx planes")
+        if mxl:
+            _launch_fwd(d, pl, PACKED[w.data_ptr()]["mx"], ws_device=src.device)
+        elif route is None:
+            _launch_fwd(d, None, None)
+        else:
+            _launch_fwd(d, pl, route, w_layout=PACKED[w.data_ptr()].get("w_layout", 0), ws_device=src.device)
     if planes_out == "only":
         return opl
     return (out, opl) if planes_out == "both" else out
@@ -1263,14 +1262,9 @@ def gemm_conv(src, w, *, M, N, K, bias=None, rowbias=None, rows_per_batch=0, res
 
 def conv2d(x, w, bias, B, H, W, Cin, Cout, ksize, stride=1, pad=None, upsample=False, **kw):
     """x: (B*H*W, Cin) NHWC rows; w: (ksize,ksize,Cin,Cout) HWIO.  Returns ((B*OH*OW, Cout), OH, OW)."""
-    if pad is None:
-        pad = ksize // 2
-    VH, VW = (2 * H, 2 * W) if upsample else (H, W)
-    OH = (VH + 2 * pad - ksize) // stride + 1
-    OW = (VW + 2 * pad - ksize) // stride + 1
-    conv = dict(ksize=ksize, stride=stride, pad=pad, upsample=int(upsample), B=B, H=H, W=W, Cin=Cin, OH=OH, OW=OW)
-    out = gemm_conv(x, w, M=B * OH * OW, N=Cout, K=ksize * ksize * Cin, bias=bias, conv=conv, **kw)
-    return out, OH, OW
+    conv = _conv_geom(B, H, W, Cin, ksize, stride, pad, upsample)
+    out = gemm_conv(x, w, M=B * conv["OH"] * conv["OW"], N=Cout, K=ksize * ksize * Cin, bias=bias, conv=conv, **kw)
+    return out, conv["OH"], conv["OW"]
 
 
 def linear(x, w, bias=None, **kw):
@@ -1451,17 +1445,9 @@ def linear_dgrad(dy, w, residual=None):
         return _dgrad_fwd(dy, ent["dg"], M=M, residual=residual)
     if ent is not None and ent["bwd"] is not None and N % 8 == 0:
         # the original (K, N) order is exactly "output column k, reduction index n contiguous": forward-style planes with ldw = N
-        d = GemmDesc()
         out = torch.empty(M, K, dtype=torch.float32, device=dy.device)
-        d.src = dy.data_ptr(); d.ld_src = int(N)
-        if residual is not None:
-            d.residual = residual.data_ptr(); d.ld_res = int(K)
-        d.out = out.data_ptr(); d.ld_out = int(K)
-        d.alpha = 1.0
-        d.M, d.N, d.K = int(M), int(K), int(N)
-        ws = _scratch(SPLITK_WS_BYTES, dy.device, "splitk")
-        _check(load().ddpo_gemm_conv_fwd_bf16(byref(d), _p(ent["bwd"][0]), _p(ent["bwd"][1]), int(N), 3 if _x3() else 1,
-                                              _p(ws), SPLITK_WS_BYTES, _stream()), "ddpo_gemm_conv_fwd_bf16(dgrad)")
+        d = _gemm_desc(M, K, N, src=dy, ld_src=N, out=out, residual=residual)
+        _launch_fwd(d, None, (ent["bwd"][0], ent["bwd"][1], int(N), 3 if _x3() else 1), ws_device=dy.device, tag="(dgrad)")
         return out
     return gemm_conv(dy, w, M=M, N=K, K=N, w_trans=True, residual=residual)
 
@@ -1491,13 +1477,10 @@ def gemm_wgrad(src, dy, dw, *, M, N, K, conv=None, ld_src=None, ld_dy=None, accu
         src, spl = spl.float(), None              # fp32 activations for the backward in front of an f16mx layer, lib.norm_planes())
     if dpl is not None and dpl.fmt == 1:
         dy, dpl = dpl.float(), None
-    d = GemmDesc()
-    if spl is None:
-        d.src = src.data_ptr()
+    d = _gemm_desc(M, N, K, conv=conv, src=src if spl is None else None, ld_src=ld_src if ld_src is not None else (conv["Cin"] if conv else K),
+                   out=dw, alpha=alpha, ld_w=int(ld_dy if ld_dy is not None else N), accumulate=int(bool(accumulate)), splits=int(splits))
     if dpl is None:
         d.w = dy.data_ptr()
-    d.ld_src = int(ld_src if ld_src is not None else (conv["Cin"] if conv else K))
-    d.ld_w = int(ld_dy if ld_dy is not None else N)
     if spl is not None:                  # plane operands carry their own layout (row stride 0 = k-blocked)
         if ld_src is not None and spl.kblocked:
             raise DdpoHipError("a column slice of k-blocked planes cannot be a wgrad operand")
@@ -1506,13 +1489,6 @@ def gemm_wgrad(src, dy, dw, *, M, N, K, conv=None, ld_src=None, ld_dy=None, accu
         if ld_dy is not None and dpl.kblocked:
             raise DdpoHipError("a column slice of k-blocked planes cannot be a wgrad operand")
         d.ld_w = dpl.ld if ld_dy is None else d.ld_w
-    d.out = dw.data_ptr(); d.ld_out = int(N)
-    d.alpha = float(alpha)
-    d.M, d.N, d.K = int(M), int(N), int(K)
-    d.accumulate = int(bool(accumulate)); d.splits = int(splits)
-    if conv:
-        for k in ("ksize", "stride", "pad", "upsample", "B", "H", "W", "Cin", "OH", "OW"):
-            setattr(d, k, int(conv[k]))
     fused_bias = dbias is not None and fast and dpl is None
     if fused_bias:
         d.colsum = dbias.data_ptr()
@@ -1529,15 +1505,6 @@ def gemm_wgrad(src, dy, dw, *, M, N, K, conv=None, ld_src=None, ld_dy=None, accu
     return dw
 
 
-def _conv_geom(B, H, W, Cin, ksize, stride, pad, upsample):
-    if pad is None:
-        pad = ksize // 2
-    VH, VW = (2 * H, 2 * W) if upsample else (H, W)
-    OH = (VH + 2 * pad - ksize) // stride + 1
-    OW = (VW + 2 * pad - ksize) // stride + 1
-    return dict(ksize=ksize, stride=stride, pad=pad, upsample=int(bool(upsample)), B=B, H=H, W=W, Cin=Cin, OH=OH, OW=OW)
-
-
 def conv2d_wgrad(x, dy, dw, B, H, W, Cin, Cout, ksize, stride=1, pad=None, upsample=False, ld_src=None, dbias=None):
     """dw (ksize,ksize,Cin,Cout) += im2col(x)^T @ dy, x: forward input (B*H*W, Cin), dy: (B*OH*OW, Cout)  [dbias (Cout,) += column sums of dy]."""
     conv = _conv_geom(B, H, W, Cin, ksize, stride, pad, upsample)
@@ -1547,36 +1514,21 @@ def conv2d_wgrad(x, dy, dw, B, H, W, Cin, Cout, ksize, stride=1, pad=None, upsam
 def conv2d_dgrad(dy, w, B, H, W, Cin, Cout, ksize, stride=1, residual=None):
     """Gradient w.r.t. the input of y = conv(x, w) (pad = ksize//2, no upsample): x was (B*H*W, Cin), dy is (B*OH*OW, Cout).
     Returns (B*H*W, Cin).  stride 2 uses the zero-insert gather (transposed convolution)."""
-    pad = ksize // 2
-    OH = (H + 2 * pad - ksize) // stride + 1
-    OW = (W + 2 * pad - ksize) // stride + 1
+    fwd = _conv_geom(B, H, W, Cin, ksize, stride, None, False)
+    OH, OW = fwd["OH"], fwd["OW"]
     if stride == 2 and (H != 2 * OH or W != 2 * OW):
         raise DdpoHipError("stride-2 dgrad expects even input sizes")
-    conv = dict(ksize=ksize, stride=1, pad=pad, upsample=2 if stride == 2 else 0, B=B, H=OH, W=OW, Cin=Cout, OH=H, OW=W)
+    # the transposed view: a stride-1 convolution of dY (zero-inserted for stride 2) with the channel roles swapped, back onto the (H, W) grid
+    conv = _conv_geom(B, OH, OW, Cout, ksize, 1, None, 2 if stride == 2 else 0)
     ent = PACKED.get(w.data_ptr()) if current_datapath() != "fp32" else None
     if ent is not None and ent.get("dg") is not None and _x3():
         return _dgrad_fwd(dy, ent["dg"], M=B * H * W, conv=conv, residual=residual)
     if isinstance(dy, Planes):
         dy = dy.float()
-    d = GemmDesc()
-    d.src = dy.data_ptr(); d.ld_src = int(Cout)
-    d.w = w.data_ptr(); d.w_trans = 1; d.w_dgrad = 1
     out = torch.empty(B * H * W, Cin, dtype=torch.float32, device=dy.device)
-    if residual is not None:
-        d.residual = residual.data_ptr(); d.ld_res = int(Cin)
-    d.out = out.data_ptr(); d.ld_out = int(Cin)
-    d.alpha = 1.0
-    d.M, d.N, d.K = B * H * W, int(Cin), ksize * ksize * int(Cout)
-    for k, v in conv.items():
-        setattr(d, k, int(v))
+    d = _gemm_desc(B * H * W, Cin, ksize * ksize * Cout, conv=conv, src=dy, ld_src=Cout, out=out, residual=residual, w=w.data_ptr(), w_trans=1, w_dgrad=1)
     route = _bf16_route(w, d.K, d.N, conv, True)
-    if route is not None:
-        hi, lo, _, npass = route
-        ws = _scratch(SPLITK_WS_BYTES, dy.device, "splitk")
-        _check(load().ddpo_gemm_conv_fwd_bf16(byref(d), _p(hi), _p(lo), 0, npass, _p(ws), SPLITK_WS_BYTES, _stream()),
-               "ddpo_gemm_conv_fwd_bf16(dgrad)")
-    else:
-        _check(load().ddpo_gemm_conv_fwd(byref(d), _stream()), "ddpo_gemm_conv_fwd(dgrad)")
+    _launch_fwd(d, None, route, ws_device=None if route is None else dy.device, tag="(dgrad)")
     return out
 
 
