@@ -1,0 +1,209 @@
+// CLIP image preprocessing on the device (the aesthetic_device / clip_score_device rewards): decoder images in HBM -> the patch matrix the
+// patch-embedding GEMM reads, in ONE launch.  Byte conversion by truncation, Pillow's 8-bit two-pass bicubic resize of the short side, centre
+// crop, (x / 255 - mean) / std through a 256 x 3 table, im2col of the stride-p p x p convolution.  The arithmetic is csrc/clip_preprocess_core.h,
+// shared with the serial host entry at the bottom; the coefficient tables are the caller's (lib.clip_preprocess_tables), nothing here is
+// computed in double precision.
+//
+// One workgroup per (image, patch row):
+//   1. the input rows the p output rows of that patch row need (from the vertical bound table) are staged CP_STAGE_ROWS at a time into LDS as
+//      bytes — 16-byte loads, coalesced along W — and resampled horizontally, only over the cropped window, into `rows` x size x 3 bytes of LDS;
+//   2. the vertical pass runs out of LDS, each byte indexes the normalisation table and the finished patch-matrix rows leave as 16-byte stores,
+//      pad columns (3 p p .. ld) as zeros.
+// No workspace, no atomics, no state outside the arguments: calls on different streams may overlap.  Neighbouring patch rows re-read the input
+// rows their kernels share (about support / p of the image); nothing else is read twice from HBM.
+#include "common.h"
+#include "clip_preprocess_core.h"
+#include <algorithm>
+#include <vector>
+
+namespace {
+
+constexpr int CP_TB = 512;
+
+struct CpArgs {
+  const void* images;
+  int N, H, W, rh, rw, top, left, size, patch;
+  const int32_t *hcoef, *hbounds;
+  int hk;
+  const int32_t *vcoef, *vbounds;
+  int vk, rows;
+  const float* norm;
+  float* out;
+  int ld;
+};
+
+__host__ __device__ inline int cp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Everything the device and the host entry refuse alike (pointers and the LDS rule are checked by the callers)
+bool cp_geometry_ok(const CpArgs& a) {
+  if (a.N < 1 || a.H < 1 || a.W < 1 || a.rh < 1 || a.rw < 1 || a.size < 1 || a.patch < 1 || a.size % a.patch) return false;
+  if (a.patch > 1024 || a.size > (1 << 15) || a.H > (1 << 24) || a.W > (1 << 24)) return false;
+  if (a.ld < 3 * a.patch * a.patch || (a.ld & 3)) return false;
+  if (a.top < 0 || a.left < 0 || a.top > a.rh - a.size || a.left > a.rw - a.size) return false;      // crop window inside the resized image
+  if (a.hk < 1 || a.vk < 1) return false;
+  if ((int64_t)a.N * (a.size / a.patch) > 0x7fffffff) return false;
+  return true;
+}
+
+template <bool F32, bool VEC>
+__global__ __launch_bounds__(CP_TB) void clip_preprocess_kernel(const CpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int t = threadIdx.x;
+  const int g = a.size / a.patch;
+  const int n = blockIdx.x / g, gy = blockIdx.x % g;
+  const int hrow = (int)cp_row_bytes(a.size), srow = (int)cp_row_bytes(a.W);
+  uint8_t* s_h = reinterpret_cast<uint8_t*>(smem);                          // [rows][hrow]: horizontally resampled bytes
+  uint8_t* s_in = s_h + (size_t)a.rows * hrow;                              // [CP_STAGE_ROWS][srow]: input rows as bytes
+  float* s_norm = reinterpret_cast<float*>(s_in + (size_t)CP_STAGE_ROWS * srow);
+  for (int i = t; i < 256 * 3; i += CP_TB) s_norm[i] = a.norm[i];
+
+  // input rows [y_lo, y_lo + nrows) feed the output rows Y0 .. Y0 + p - 1 (the first bound of a table never decreases).  Bounds are clamped to
+  // the image and to the LDS the launch was given, so a bad table cannot make the kernel read or write outside its arguments.
+  const int Y0 = a.top + gy * a.patch;
+  int y_lo = a.vbounds[2 * Y0], y_hi = y_lo;
+  for (int r = 0; r < a.patch; ++r) y_hi = max(y_hi, a.vbounds[2 * (Y0 + r)] + a.vbounds[2 * (Y0 + r) + 1]);
+  y_lo = cp_clampi(y_lo, 0, a.H);
+  const int nrows = cp_clampi(min(y_hi, a.H) - y_lo, 0, a.rows);
+  const int s3 = a.size * 3, w3 = a.W * 3;
+
+  for (int r0 = 0; r0 < nrows; r0 += CP_STAGE_ROWS) {
+    const int nr = min(CP_STAGE_ROWS, nrows - r0);
+    const size_t row0 = ((size_t)n * a.H + (size_t)(y_lo + r0)) * w3;      // element index of the first staged row
+    if (VEC) {                                                              // W % 4 == 0 and an aligned base: rows start on 16 B (float) / 4 B (uint8)
+      const int q = w3 >> 2;
+      for (int i = t; i < nr * q; i += CP_TB) {
+        const int r = i / q, e = (i - r * q) * 4;
+        const size_t src = row0 + (size_t)r * w3 + e;
+        uint32_t pk;
+        if (F32) {
+          const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(a.images) + src);
+          pk = (uint32_t)cp_float_to_u8(v.x) | ((uint32_t)cp_float_to_u8(v.y) << 8) | ((uint32_t)cp_float_to_u8(v.z) << 16) |
+               ((uint32_t)cp_float_to_u8(v.w) << 24);
+        } else {
+          pk = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(a.images) + src);
+        }
+        *reinterpret_cast<uint32_t*>(s_in + r * srow + e) = pk;
+      }
+    } else {
+      for (int i = t; i < nr * w3; i += CP_TB) {
+        const int r = i / w3, e = i - r * w3;
+        const size_t src = row0 + (size_t)r * w3 + e;
+        s_in[r * srow + e] = F32 ? (uint8_t)cp_float_to_u8(static_cast<const float*>(a.images)[src]) : static_cast<const uint8_t*>(a.images)[src];
+      }
+    }
+    __syncthreads();
+    for (int i = t; i < nr * s3; i += CP_TB) {
+      const int r = i / s3, rem = i - r * s3, xo = rem / 3, c = rem - xo * 3;
+      const int X = a.left + xo;
+      const int xmin = cp_clampi(a.hbounds[2 * X], 0, a.W);
+      const int cnt = cp_clampi(a.hbounds[2 * X + 1], 0, min(a.hk, a.W - xmin));
+      s_h[(r0 + r) * hrow + rem] = (uint8_t)cp_taps(s_in + r * srow + xmin * 3 + c, 3, a.hcoef + (size_t)X * a.hk, cnt);
+    }
+    __syncthreads();
+  }
+  __syncthreads();                                                          // s_norm, also when no row was staged
+
+  const int ld4 = a.ld >> 2, pp = a.patch * a.patch, kp = 3 * pp;
+  for (int i = t; i < g * ld4; i += CP_TB) {
+    const int gx = i / ld4, col0 = (i - gx * ld4) * 4;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int col = col0 + j;
+      float val = 0.0f;                                                     // pad columns
+      if (col < kp) {
+        const int c = col / pp, rem = col - c * pp, ky = rem / a.patch, kx = rem - ky * a.patch;
+        const int Y = Y0 + ky;
+        const int ymin = cp_clampi(a.vbounds[2 * Y] - y_lo, 0, nrows);
+        const int cnt = cp_clampi(a.vbounds[2 * Y + 1], 0, min(a.vk, nrows - ymin));
+        const int b = cp_taps(s_h + ymin * hrow + (gx * a.patch + kx) * 3 + c, hrow, a.vcoef + (size_t)Y * a.vk, cnt);
+        val = s_norm[b * 3 + c];
+      }
+      v[j] = val;
+    }
+    float* dst = a.out + ((size_t)(n * g + gy) * g + gx) * a.ld + col0;
+    *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+template <bool F32, bool VEC>
+int cp_launch(const CpArgs& a, size_t lds, hipStream_t s) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&clip_preprocess_kernel<F32, VEC>), hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS_LIMIT);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((clip_preprocess_kernel<F32, VEC>), dim3((unsigned)(a.N * (a.size / a.patch))), dim3(CP_TB), lds, s, a);
+  DDPO_LAUNCH_CHECK();
+  return DDPO_OK;
+}
+
+}  // namespace
+
+extern "C" int ddpo_clip_preprocess(const void* images, int is_float32, int N, int H, int W, int rh, int rw, int top, int left, int size, int patch,
+                                    const int32_t* hcoef, const int32_t* hbounds, int hksize, const int32_t* vcoef, const int32_t* vbounds,
+                                    int vksize, int rows, const float* norm, float* out, int ld, void* stream) {
+  if (!images || !hcoef || !hbounds || !vcoef || !vbounds || !norm || !out) return DDPO_EINVAL;
+  const CpArgs a{images, N, H, W, rh, rw, top, left, size, patch, hcoef, hbounds, hksize, vcoef, vbounds, vksize, rows, norm, out, ld};
+  if (!cp_geometry_ok(a) || rows < 1 || rows > H) return DDPO_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(out) & 15) || (is_float32 && (reinterpret_cast<uintptr_t>(images) & 3))) return DDPO_EINVAL;
+  const size_t lds = cp_lds_bytes(rows, size, W);
+  if (lds > CP_LDS_LIMIT) return DDPO_EINVAL;                               // the LDS rule
+  const bool vec = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(images) & (is_float32 ? 15 : 3)) == 0;
+  hipStream_t s = as_stream(stream);
+  if (is_float32) return vec ? cp_launch<true, true>(a, lds, s) : cp_launch<true, false>(a, lds, s);
+  return vec ? cp_launch<false, true>(a, lds, s) : cp_launch<false, false>(a, lds, s);
+}
+
+// Serial host path over the same functions (no GPU involved): what the kernel is held to, and what is held to Pillow.  The whole cropped window is
+// resampled horizontally at once instead of a patch row at a time; every output byte is the same sum.  resized_out_host (may be null):
+// the N x size x size x 3 bytes before normalisation.
+extern "C" int ddpo_clip_preprocess_host(const void* images, int is_float32, int N, int H, int W, int rh, int rw, int top, int left, int size,
+                                         int patch, const int32_t* hcoef, const int32_t* hbounds, int hksize, const int32_t* vcoef,
+                                         const int32_t* vbounds, int vksize, const float* norm, float* out_host, int ld, uint8_t* resized_out_host) {
+  if (!images || !hcoef || !hbounds || !vcoef || !vbounds || !norm || !out_host) return DDPO_EINVAL;
+  const CpArgs a{images, N, H, W, rh, rw, top, left, size, patch, hcoef, hbounds, hksize, vcoef, vbounds, vksize, 0, norm, out_host, ld};
+  if (!cp_geometry_ok(a)) return DDPO_EINVAL;
+  for (int X = left; X < left + size; ++X)
+    if (hbounds[2 * X] < 0 || hbounds[2 * X + 1] < 0 || hbounds[2 * X + 1] > hksize || hbounds[2 * X] > W - hbounds[2 * X + 1]) return DDPO_EINVAL;
+  for (int Y = top; Y < top + size; ++Y)
+    if (vbounds[2 * Y] < 0 || vbounds[2 * Y + 1] < 0 || vbounds[2 * Y + 1] > vksize || vbounds[2 * Y] > H - vbounds[2 * Y + 1] ||
+        (Y > top && vbounds[2 * Y] < vbounds[2 * (Y - 1)]))
+      return DDPO_EINVAL;
+  const int g = size / patch, pp = patch * patch, s3 = size * 3, w3 = W * 3;
+  int rows = 1, y_hi = 0;
+  for (int gy = 0; gy < g; ++gy) {
+    int hi = 0;
+    for (int r = 0; r < patch; ++r) hi = std::max(hi, vbounds[2 * (top + gy * patch + r)] + vbounds[2 * (top + gy * patch + r) + 1]);
+    rows = std::max(rows, hi - vbounds[2 * (top + gy * patch)]);
+    y_hi = std::max(y_hi, hi);
+  }
+  if (cp_lds_bytes(rows, size, W) > CP_LDS_LIMIT) return DDPO_EINVAL;       // the LDS rule: the same domain as the device entry
+  const int y_lo = vbounds[2 * top];
+  std::vector<uint8_t> in_row((size_t)w3), hbuf((size_t)std::max(y_hi - y_lo, 1) * s3);
+  for (int n = 0; n < N; ++n) {
+    for (int y = y_lo; y < y_hi; ++y) {
+      const size_t src = ((size_t)n * H + y) * w3;
+      for (int e = 0; e < w3; ++e)
+        in_row[e] = is_float32 ? (uint8_t)cp_float_to_u8(static_cast<const float*>(images)[src + e]) : static_cast<const uint8_t*>(images)[src + e];
+      for (int xo = 0; xo < size; ++xo)
+        for (int c = 0; c < 3; ++c) {
+          const int X = left + xo;
+          hbuf[(size_t)(y - y_lo) * s3 + xo * 3 + c] =
+              (uint8_t)cp_taps(in_row.data() + hbounds[2 * X] * 3 + c, 3, hcoef + (size_t)X * hksize, hbounds[2 * X + 1]);
+        }
+    }
+    for (int yo = 0; yo < size; ++yo)
+      for (int xo = 0; xo < size; ++xo)
+        for (int c = 0; c < 3; ++c) {
+          const int Y = top + yo;
+          const int b = cp_taps(hbuf.data() + (size_t)(vbounds[2 * Y] - y_lo) * s3 + xo * 3 + c, s3, vcoef + (size_t)Y * vksize, vbounds[2 * Y + 1]);
+          if (resized_out_host) resized_out_host[(((size_t)n * size + yo) * size + xo) * 3 + c] = (uint8_t)b;
+          const size_t row = ((size_t)n * g + yo / patch) * g + xo / patch;
+          out_host[row * ld + c * pp + (yo % patch) * patch + xo % patch] = norm[b * 3 + c];
+        }
+    for (int r = 0; r < g * g; ++r)
+      for (int col = 3 * pp; col < ld; ++col) out_host[((size_t)n * g * g + r) * ld + col] = 0.0f;
+  }
+  return DDPO_OK;
+}

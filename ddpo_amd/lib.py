@@ -6,6 +6,8 @@ There is NO fallback path: if the shared library is missing or a call fails, an 
 """
 import contextlib
 import ctypes
+import functools
+import math
 import os
 import threading
 from ctypes import c_void_p, c_int, c_int32, c_int64, c_uint32, c_float, c_double, c_size_t, POINTER, byref
@@ -160,6 +162,9 @@ _SIGS = {
     "ddpo_jpeg_size_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "ddpo_jpeg_size": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "ddpo_jpeg_size_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    # CLIP image preprocessing into the patch matrix (additive to ABI v14; csrc/clip_preprocess.hip)
+    "ddpo_clip_preprocess": (c_int, [c_void_p] + [c_int] * 10 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "ddpo_clip_preprocess_host": (c_int, [c_void_p] + [c_int] * 10 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1651,6 +1656,173 @@ def jpeg_size_host(images_u8, quality=95):
     out = np.zeros(n, dtype=np.int64)
     _check(load().ddpo_jpeg_size_host(a.ctypes.data_as(c_void_p), n, h, w, quality, out.ctypes.data_as(c_void_p)), "ddpo_jpeg_size_host")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ CLIP image preprocessing
+CLIP_PRECISION_BITS = 22      # CP_PRECISION_BITS of csrc/clip_preprocess_core.h
+CLIP_LDS_LIMIT = 160 * 1024   # CP_LDS_LIMIT
+CLIP_STAGE_ROWS = 8           # CP_STAGE_ROWS
+CLIP_PREPROCESS_RULE = ("the input rows one patch row needs, resampled horizontally to bytes (rows x size x 3), plus 8 staged input rows "
+                        "(W x 3 bytes each) and the 3 KB normalisation table must fit the 160 KB of LDS")
+
+
+def _bicubic(t):
+    a = -0.5
+    t = abs(t)
+    if t < 1.0:
+        return ((a + 2.0) * t - (a + 3.0)) * t * t + 1
+    if t < 2.0:
+        return (((t - 5) * t + 8) * t - 4) * a
+    return 0.0
+
+
+@functools.lru_cache(maxsize=None)
+def clip_preprocess_tables(in_size, out_size):
+    """(coef, bounds, ksize) of one axis of Pillow's 8-bit bicubic resize from `in_size` to `out_size` pixels, restated: coef (out_size, ksize)
+    int32, the weights of output pixel xx as 22-bit fixed point (unused taps 0); bounds (out_size, 2) int32, {first input pixel, tap count}.
+    Float64 scalar arithmetic in Pillow's order — weights at (x + xmin - center + 0.5) * (1 / filterscale), summed left to right, each divided
+    by the sum, rounded half away from zero — so the integers are Pillow's.  An axis that keeps its size is not resampled by Pillow; it gets
+    the identity table here (one tap of 2^22: (p * 2^22 + 2^21) >> 22 == p), which lets the kernel treat every axis alike.  Read-only arrays."""
+    import numpy as np
+    I, O = int(in_size), int(out_size)
+    if I < 1 or O < 1:
+        raise ValueError(f"clip_preprocess_tables: sizes must be positive, got {in_size} -> {out_size}")
+    one = 1 << CLIP_PRECISION_BITS
+    if I == O:
+        ksize = 1
+        coef = np.full((O, 1), one, dtype=np.int32)
+        bounds = np.stack([np.arange(O, dtype=np.int32), np.ones(O, dtype=np.int32)], axis=1)
+    else:
+        scale = I / O
+        fs = max(scale, 1.0)
+        support = 2.0 * fs
+        ksize = int(math.ceil(support)) * 2 + 1
+        ss = 1.0 / fs
+        coef = np.zeros((O, ksize), dtype=np.int32)
+        bounds = np.zeros((O, 2), dtype=np.int32)
+        for xx in range(O):
+            center = (xx + 0.5) * scale
+            xmin = max(int(center - support + 0.5), 0)
+            xmax = min(int(center + support + 0.5), I) - xmin
+            w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+            ww = 0.0
+            for v in w:
+                ww += v
+            for x, v in enumerate(w):
+                k = v / ww if ww != 0.0 else v
+                coef[xx, x] = int(k * one - 0.5) if k < 0 else int(k * one + 0.5)
+            bounds[xx] = (xmin, xmax)
+    coef.setflags(write=False)
+    bounds.setflags(write=False)
+    return coef, bounds, ksize
+
+
+@functools.lru_cache(maxsize=None)
+def clip_norm_table(mean=None, std=None):
+    """256 x 3 float32: entry (b, c) is what models.clip_vision.preprocess makes of byte b in channel c, by its very expression."""
+    import numpy as np
+    if mean is None or std is None:
+        from .models.clip_vision import CLIP_MEAN, CLIP_STD
+        mean, std = CLIP_MEAN, CLIP_STD
+    mean, std = np.asarray(mean, np.float32), np.asarray(std, np.float32)
+    b = np.arange(256, dtype=np.uint8)[:, None].repeat(3, axis=1)
+    f = (b.astype(np.float32) * (1 / 255)).astype(np.float32)
+    t = np.ascontiguousarray(((f - mean) / std).astype(np.float32))
+    t.setflags(write=False)
+    return t
+
+
+def _clip_lds_bytes(rows, size, w):
+    up = lambda px: (px * 3 + 15) // 16 * 16
+    return rows * up(size) + CLIP_STAGE_ROWS * up(w) + 256 * 3 * 4
+
+
+@functools.lru_cache(maxsize=None)
+def clip_preprocess_geometry(h, w, size, patch, k_pad):
+    """Resize and crop geometry exactly as models.clip_vision.preprocess computes it, checked: dict(oh, ow, top, left, rows) — the resized image,
+    the centre-crop origin and the most input rows one patch row spans.  ValueError with the rule that is broken."""
+    h, w, size, patch, k_pad = int(h), int(w), int(size), int(patch), int(k_pad)
+    if h < 1 or w < 1 or size < 1 or patch < 1:
+        raise ValueError(f"clip_preprocess: sizes must be positive, got {h} x {w} images, size {size}, patch {patch}")
+    if size % patch:
+        raise ValueError(f"clip_preprocess: size {size} is not a multiple of patch {patch}")
+    if k_pad < 3 * patch * patch or k_pad % 4:
+        raise ValueError(f"clip_preprocess: k_pad {k_pad} must be a multiple of 4 and at least 3 * patch * patch = {3 * patch * patch}")
+    short, long = (w, h) if w <= h else (h, w)
+    new_short, new_long = size, int(size * long / short)
+    ow, oh = (new_short, new_long) if w <= h else (new_long, new_short)
+    top, left = (oh - size) // 2, (ow - size) // 2
+    _, vb, _ = clip_preprocess_tables(h, oh)
+    rows = 1
+    for y0 in range(top, top + size, patch):
+        rows = max(rows, int((vb[y0:y0 + patch, 0] + vb[y0:y0 + patch, 1]).max() - vb[y0, 0]))
+    if _clip_lds_bytes(rows, size, w) > CLIP_LDS_LIMIT:
+        raise ValueError(f"clip_preprocess: {h} x {w} images to {size} need {rows} rows = {_clip_lds_bytes(rows, size, w)} bytes: {CLIP_PREPROCESS_RULE}")
+    return dict(oh=oh, ow=ow, top=top, left=left, rows=rows)
+
+
+_clip_dev_tables = {}
+
+
+def _clip_device_tables(key, make, device):
+    """int32 / float32 tables as device tensors, uploaded once per (table, device) — a blocking copy, so any stream may read them afterwards."""
+    key = key + (str(device),)
+    ent = _clip_dev_tables.get(key)
+    if ent is None:
+        ent = tuple(torch.from_numpy(a.copy()).to(device) for a in make())
+        _clip_dev_tables[key] = ent
+    return ent
+
+
+def _clip_images_shape(shape):
+    if len(shape) != 4 or shape[3] != 3 or shape[0] < 1:
+        raise ValueError(f"clip_preprocess needs N x H x W x 3 images, got shape {tuple(shape)}")
+    return int(shape[0]), int(shape[1]), int(shape[2])
+
+
+def clip_preprocess(images, size, patch, k_pad, out=None):
+    """models.clip_vision.preprocess + the im2col of the patch embedding in one launch on the current stream (ddpo_clip_preprocess): an
+    N x H x W x 3 CUDA tensor — float32 in [0, 1], truncated as (x * 255).astype(uint8), or uint8 — to the (N * g * g, k_pad) float32 patch
+    matrix, g = size // patch, rows (n, gy, gx), columns (c, ky, kx), pad columns zero.  Equal bit for bit to the host path (Pillow's bicubic
+    resize of the short side to `size`, centre crop, CLIP normalisation).  ValueError names the broken rule (CLIP_PREPROCESS_RULE for LDS)."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype not in (torch.float32, torch.uint8):
+        raise DdpoHipError("clip_preprocess needs a float32 or uint8 CUDA tensor")
+    n, h, w = _clip_images_shape(images.shape)
+    geo = clip_preprocess_geometry(h, w, size, patch, k_pad)
+    g = size // patch
+    hc, hb = _clip_device_tables(("axis", w, geo["ow"]), lambda: clip_preprocess_tables(w, geo["ow"])[:2], images.device)
+    vc, vb = _clip_device_tables(("axis", h, geo["oh"]), lambda: clip_preprocess_tables(h, geo["oh"])[:2], images.device)
+    norm, = _clip_device_tables(("norm",), lambda: (clip_norm_table(),), images.device)
+    if out is None:
+        out = torch.empty(n * g * g, k_pad, dtype=torch.float32, device=images.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (n * g * g, k_pad) or out.device != images.device:
+        raise DdpoHipError(f"clip_preprocess: out must be a float32 ({n * g * g}, {k_pad}) tensor on {images.device}")
+    _check(load().ddpo_clip_preprocess(_p(images), int(images.dtype == torch.float32), n, h, w, geo["oh"], geo["ow"], geo["top"], geo["left"],
+                                       int(size), int(patch), _p(hc), _p(hb), hc.shape[1], _p(vc), _p(vb), vc.shape[1], geo["rows"], _p(norm),
+                                       _p(out), int(k_pad), _stream()), "ddpo_clip_preprocess")
+    return out
+
+
+def clip_preprocess_host(images, size, patch, k_pad, return_resized=False):
+    """The same patch matrix computed serially on the host (ddpo_clip_preprocess_host) for a uint8 or float32 N x H x W x 3 numpy array: the
+    GPU-free reference.  return_resized: also the N x size x size x 3 uint8 image before normalisation (what Pillow's resize + crop gives)."""
+    import numpy as np
+    a = np.ascontiguousarray(images)
+    if a.dtype not in (np.uint8, np.float32):
+        raise ValueError(f"clip_preprocess_host takes uint8 or float32 images, got {a.dtype}")
+    n, h, w = _clip_images_shape(a.shape)
+    geo = clip_preprocess_geometry(h, w, size, patch, k_pad)
+    g = size // patch
+    hc, hb, hk = clip_preprocess_tables(w, geo["ow"])
+    vc, vb, vk = clip_preprocess_tables(h, geo["oh"])
+    norm = clip_norm_table()
+    out = np.full((n * g * g, k_pad), np.nan, dtype=np.float32)
+    resized = np.zeros((n, size, size, 3), dtype=np.uint8)
+    ptr = lambda x: x.ctypes.data_as(c_void_p)
+    _check(load().ddpo_clip_preprocess_host(ptr(a), int(a.dtype == np.float32), n, h, w, geo["oh"], geo["ow"], geo["top"], geo["left"], int(size),
+                                            int(patch), ptr(hc), ptr(hb), hk, ptr(vc), ptr(vb), vk, ptr(norm), ptr(out), int(k_pad), ptr(resized)),
+           "ddpo_clip_preprocess_host")
+    return (out, resized) if return_resized else out
 
 
 def timestep_embedding(ts, dim):

@@ -30,7 +30,7 @@ import torch
 
 from .. import lib as L
 from .clip_text import ClipTextTower, TextConfig, synthetic_text_state
-from .clip_vision import ClipVisionTower, VisionConfig, preprocess
+from .clip_vision import ClipVisionTower, VisionConfig, device_images, preprocess
 from .laion import REPO_ROOT, _load_clip_state, find_weights, synthetic_state_dicts
 
 CHECKPOINT = "openai/clip-vit-large-patch14"
@@ -154,15 +154,40 @@ class ClipScorer:
             out[i:i + m] = self.vision(part)[:m]
         return out
 
-    def __call__(self, images, prompts, return_cosine=False):
-        """images: float32 (N,H,W,3) in [0,1] (host), prompts: N strings -> (N,) float32 scores (host) [, (N,) float32 raw cosines]."""
+    def _embed_patches(self, patches, n):
+        """_embed_images for a patch matrix (lib.clip_preprocess): the same chunks of IMAGE_CHUNK images, cut out of the matrix's rows; a short
+        chunk is padded by repeating the rows of its last image.  Current stream."""
+        gg = self.vcfg.grid * self.vcfg.grid
+        out = torch.empty(n, self.vcfg.proj, dtype=torch.float32, device=self.device)
+        for i in range(0, n, IMAGE_CHUNK):
+            m = min(IMAGE_CHUNK, n - i)
+            part = patches[i * gg:(i + m) * gg]
+            if m < IMAGE_CHUNK:
+                part = torch.cat([part] + [part[-gg:]] * (IMAGE_CHUNK - m))
+            out[i:i + m] = self.vision.forward_patches(part)[:m]
+        return out
+
+    def __call__(self, images, prompts, return_cosine=False, ready=None):
+        """images (N,H,W,3) in [0,1]: a float32 host array (preprocessed on the host, PIL) or a CUDA tensor, float32 or uint8 (preprocessed by
+        `lib.clip_preprocess`, no host trip; the same scores bit for bit), prompts: N strings -> (N,) float32 scores (host) [, (N,) float32 raw
+        cosines].  A CUDA tensor is read on this scorer's stream after `ready` — an event recorded on the producing stream once the images were
+        complete; default: one recorded now on the caller's current stream — and is referenced here until that work has finished."""
         if len(images) != len(prompts):
             raise ValueError(f"{len(images)} images but {len(prompts)} prompts")
-        px = preprocess(images, self.vcfg.image)                               # host, PIL: byte-identical resize
+        on_device = isinstance(images, torch.Tensor)
+        if on_device:
+            images, ready = device_images(images, ready, "ClipScorer")
+        else:
+            px = preprocess(images, self.vcfg.image)                           # host, PIL: byte-identical resize
         with torch.cuda.stream(self.stream), L.fp32_class_datapath():
-            img = self._embed_images(torch.from_numpy(px).to(self.device))
+            if on_device:
+                self.stream.wait_event(ready)
+                img = self._embed_patches(L.clip_preprocess(images, self.vcfg.image, self.vcfg.patch, self.vcfg.k_pad), images.shape[0])
+            else:
+                img = self._embed_images(torch.from_numpy(px).to(self.device))
             txt = torch.stack(self.prompts.lookup(prompts))
             scores = L.cosine_rows(img, txt, scale=math.exp(self.logit_scale)).cpu().numpy()
             cosine = L.cosine_rows(img, txt).cpu().numpy()
         self.stream.synchronize()
+        del images
         return (scores, cosine) if return_cosine else scores

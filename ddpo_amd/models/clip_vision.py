@@ -3,7 +3,9 @@
 Replaces `FlaxCLIPModel.get_image_features` + `CLIPProcessor` of /root/reference/ddpo/training/callbacks.py:60-95 (the reference pmaps it
 on the same devices as the sampler; here it runs on the sampling GPU, on a private HIP stream, next to the sampling of the next batch):
 
-    processor   host, PIL: float [0,1] -> uint8 (truncation) -> bicubic resize of the short side to 224 -> centre crop -> /255 -> normalise
+    processor   float [0,1] -> uint8 (truncation) -> bicubic resize of the short side to 224 -> centre crop -> /255 -> normalise.  Host arrays:
+                `preprocess` (PIL).  Device tensors: `lib.clip_preprocess` (csrc/clip_preprocess.hip), one launch that writes the patch matrix
+                below directly, equal to the host path bit for bit (`forward_patches` takes it)
     patch embed stride-14 14x14 convolution = ONE GEMM over the (N*256, 3*14*14 -> 608) patch matrix; the position embedding rides in
                 the GEMM epilogue as its residual operand
     24 x layer  LayerNorm (bf16 hi/lo planes out) -> q / k / v GEMMs -> flash attention d=64, 257 keys -> out-proj GEMM (+residual)
@@ -65,6 +67,20 @@ def preprocess(images, size=224):
         f = (r.astype(np.float32) * (1 / 255)).astype(np.float32)
         out.append(((f - mean) / std).transpose(2, 0, 1))
     return np.stack(out).astype(np.float32)
+
+
+def device_images(images, ready, who):
+    """What the on-device scorers accept as a device batch: a contiguous N x H x W x 3 CUDA tensor, float32 in [0,1] or uint8.  Returns it with the
+    event its reader has to wait for (`ready`, else one recorded now on the caller's current stream)."""
+    if not images.is_cuda:
+        raise ValueError(f"{who} takes a numpy array or a CUDA tensor")
+    if images.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"{who} takes float32 or uint8 device images, got {images.dtype}")
+    if images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
+        raise ValueError(f"{who} needs a contiguous N x H x W x 3 tensor, got shape {tuple(images.shape)}")
+    if ready is None:
+        ready = torch.cuda.current_stream(images.device).record_event()
+    return images, ready
 
 
 def vision_param_shapes(cfg: VisionConfig):
@@ -170,6 +186,20 @@ class ClipVisionTower:
         # im2col of a stride-p, p x p convolution is a pure re-ordering: rows = patches, columns = (channel, ky, kx), zero-padded to k_pad
         patches = torch.zeros(N * g * g, cfg.k_pad, dtype=torch.float32, device=self.device)
         patches[:, :cfg.k_patch] = pixel_values.reshape(N, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(N * g * g, cfg.k_patch)
+        return self._forward_patches(patches)
+
+    def forward_patches(self, patches):
+        """The tower from the patch-embedding GEMM on: (N * grid * grid, k_pad) fp32 patch matrix — rows (n, gy, gx), columns (channel, ky, kx),
+        pad columns zero; what `forward` builds from pixel values and `lib.clip_preprocess` writes from raw images — -> image_embeds (N, proj)."""
+        with L.fp32_class_datapath():
+            return self._forward_patches(patches)
+
+    def _forward_patches(self, patches):
+        cfg, P = self.cfg, self.params
+        g, C, T = cfg.grid, cfg.hidden, cfg.tokens
+        if patches.dim() != 2 or patches.shape[1] != cfg.k_pad or patches.shape[0] % (g * g) or patches.shape[0] == 0:
+            raise ValueError(f"patches must be (N * {g * g}, {cfg.k_pad}), got {tuple(patches.shape)}")
+        N = patches.shape[0] // (g * g)
         pos_rows, cls_row = self._pos_rows(N)
         pe = L.linear(patches, P["embeddings.patch_embedding.kernel"], residual=pos_rows)            # conv (no bias) + position embedding
         h = torch.empty(N, T, C, dtype=torch.float32, device=self.device)

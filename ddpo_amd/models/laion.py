@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import lib as L
-from .clip_vision import ClipVisionTower, VisionConfig, flax_tree_to_torch_names, preprocess
+from .clip_vision import ClipVisionTower, VisionConfig, device_images, flax_tree_to_torch_names, preprocess
 
 MLP_FILE = "sac+logos+ava1-l14-linearMSE.pth"
 MLP_LAYERS = (0, 2, 4, 6, 7)                  # keys of the published state dict (laion.set_weights :41)
@@ -128,14 +128,28 @@ class AestheticScorer:
     def features(self, pixel_values):
         return self.tower(pixel_values)
 
-    def __call__(self, images):
-        """images: float32 (N,H,W,3) in [0,1] (host) -> (N,) float32 scores (host)."""
+    def _score(self, feats):
+        f = L.l2_normalize_rows(feats)
+        for wp, bp, n in self.mlp:
+            f = L.linear(f[:, :wp.shape[0]].contiguous() if f.shape[1] != wp.shape[0] else f, wp, bp)
+        return f[:, 0].contiguous().cpu().numpy()
+
+    def __call__(self, images, ready=None):
+        """images (N,H,W,3) in [0,1]: a float32 host array (preprocessed on the host, PIL) or a CUDA tensor, float32 or uint8 (preprocessed by
+        `lib.clip_preprocess`, no host trip; the same scores bit for bit) -> (N,) float32 scores (host).
+        A CUDA tensor is read on this scorer's stream after `ready` — an event recorded on the producing stream once the images were complete;
+        default: one recorded now on the caller's current stream — and is referenced here until that work has finished."""
+        if isinstance(images, torch.Tensor):
+            images, ready = device_images(images, ready, "AestheticScorer")
+            with torch.cuda.stream(self.stream), L.fp32_class_datapath():
+                self.stream.wait_event(ready)
+                patches = L.clip_preprocess(images, self.cfg.image, self.cfg.patch, self.cfg.k_pad)
+                scores = self._score(self.tower.forward_patches(patches))
+            self.stream.synchronize()
+            del images
+            return scores
         px = preprocess(images, self.cfg.image)                               # host, PIL: byte-identical resize
         with torch.cuda.stream(self.stream), L.fp32_class_datapath():
-            x = torch.from_numpy(px).to(self.device)
-            f = L.l2_normalize_rows(self.tower(x))
-            for wp, bp, n in self.mlp:
-                f = L.linear(f[:, :wp.shape[0]].contiguous() if f.shape[1] != wp.shape[0] else f, wp, bp)
-            scores = f[:, 0].contiguous().cpu().numpy()
+            scores = self._score(self.tower(torch.from_numpy(px).to(self.device)))
         self.stream.synchronize()
         return scores

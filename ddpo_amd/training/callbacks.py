@@ -6,10 +6,12 @@ Behavioural mirror of the registry / calling convention of /root/reference/ddpo/
 images: float32 (N,H,W,3) in [0,1]; scores: (N,) or (N,1) numpy; info: dict of numpy arrays.
 Callbacks run in a worker thread of the entrypoint (ThreadPoolExecutor, max_workers=2) next to the sampling of the
 following batch, so they must not touch the sampler's HIP stream: the host ones below are pure CPU code and the
-on-device ones (aesthetic, clip_score, jpeg_device, neg_jpeg_device) use their own streams.
+on-device ones (aesthetic, clip_score, jpeg_device, neg_jpeg_device, aesthetic_device, clip_score_device) use their own streams.
 
 In scope (BASELINE.json configs): jpeg, neg_jpeg (+ jpeg_device, neg_jpeg_device: the same rewards counted on the device), aesthetic, llava_bertscore (+ its sibling llava_vqa wire format), and clip_score: the
 prompt-alignment reward that needs no server (CLIPScore on the engine's own CLIP towers; not in the reference, which aligns through LLaVA).
+aesthetic_device / clip_score_device are aesthetic / clip_score with the CLIP preprocessing done on the device too, so the decoded batch never
+leaves HBM (`wants_device_images`).
 The other reward ideas of the reference (rotational / mirror symmetry, thumbnail, BLIP-2 vqa, ...) are not part of
 any benchmark config; add them as plugins with `register`.
 """
@@ -129,6 +131,49 @@ def clip_score_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None
         return scores[:, None], {"cosine": cosine, "synthetic_weights": np.array(scorer.synthetic)}
 
     return _wrapper
+
+
+# ------------------------------------------------------------------------------------------------ the CLIP rewards on device images
+def _is_device_batch(images):
+    import torch
+    return isinstance(images, torch.Tensor)
+
+
+def aesthetic_device_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None):
+    """`aesthetic` without the host trip: the same scores and info, bit for bit.  A CUDA tensor straight from the VAE decoder (`wants_device_images`:
+    the entrypoint then keeps the batch in HBM, see evaluate_callbacks_device) is truncated to bytes, resized, cropped, normalised and laid out as
+    the patch matrix by one kernel (lib.clip_preprocess, csrc/clip_preprocess.hip) on the scorer's private stream; host arrays take `aesthetic`'s
+    own path (PIL).  Weights as for `aesthetic`."""
+    del devices, jit
+    from ..models.laion import AestheticScorer
+    scorer = AestheticScorer(weights_dir=weights_dir, cache=cache, seed=rng)
+
+    def _fn(images, prompts, metadata, ready=None):
+        del prompts, metadata
+        scores = scorer(images, ready=ready) if _is_device_batch(images) else scorer(np.asarray(images, dtype=np.float32))
+        return scores[:, None], {"synthetic_weights": np.array(scorer.synthetic)}
+
+    _fn.wants_device_images = True
+    return _fn
+
+
+def clip_score_device_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None):
+    """`clip_score` without the host trip: the same scores and info (`cosine`, `synthetic_weights`), bit for bit; see aesthetic_device_fn."""
+    del devices, jit
+    from ..models.clip_score import ClipScorer
+    scorer = ClipScorer(weights_dir=weights_dir, cache=cache, seed=rng)
+
+    def _fn(images, prompts, metadata, ready=None):
+        del metadata
+        prompts = [str(p) for p in prompts]
+        if _is_device_batch(images):
+            scores, cosine = scorer(images, prompts, return_cosine=True, ready=ready)
+        else:
+            scores, cosine = scorer(np.asarray(images, dtype=np.float32), prompts, return_cosine=True)
+        return scores[:, None], {"cosine": cosine, "synthetic_weights": np.array(scorer.synthetic)}
+
+    _fn.wants_device_images = True
+    return _fn
 
 
 # ------------------------------------------------------------------------------------------------ LLaVA over HTTP
@@ -252,6 +297,8 @@ callback_fns = {
     "neg_jpeg_device": neg_jpeg_device_fn,
     "aesthetic": aesthetic_fn,
     "clip_score": clip_score_fn,
+    "aesthetic_device": aesthetic_device_fn,
+    "clip_score_device": clip_score_device_fn,
     "llava_bertscore": llava_bertscore,
     "llava_vqa": llava_vqa_satisfaction,
 }

@@ -456,6 +456,25 @@ int ddpo_jpeg_size_workspace_bytes(int N, int H, int W, size_t* out_host);
 int ddpo_jpeg_size(const void* images, int is_float32, int N, int H, int W, int quality, void* workspace, size_t workspace_bytes,
                    int64_t* bytes_out, void* stream);
 int ddpo_jpeg_size_host(const uint8_t* rgb, int N, int H, int W, int quality, int64_t* bytes_out_host);
+/* CLIP image preprocessing into the patch matrix (csrc/clip_preprocess.hip; additive to ABI v14): out[(n, gy, gx)][(c, ky, kx)] =
+ *   norm[byte][c], byte = pixel (gy p + ky, gx p + kx), channel c, of the size x size centre crop of image n after an 8-bit two-pass bicubic resize
+ *   to rh x rw (what Pillow's Image.resize(BICUBIC) returns for an RGB image); columns 3 p p .. ld - 1 are written as zeros.  One launch.
+ *   images: N x H x W x 3 (NHWC, contiguous), uint8 or (is_float32) float32 in [0, 1], truncated as (uint8)(x * 255.0f) (clamped; NaN -> 0).
+ *   Tables (int32; the caller builds them, lib.clip_preprocess_tables; nothing here is computed in double precision): hcoef rw x hksize 22-bit
+ *   fixed-point weights and hbounds rw x 2 {first input column, tap count} for the horizontal pass, vcoef rh x vksize / vbounds rh x 2 for the
+ *   vertical pass.  The horizontal pass is rounded to a byte before the vertical pass; an axis that keeps its size gets the identity table
+ *   (one tap of 2^22).  norm: 256 x 3 float32.  rows: the most input rows one patch row's p output rows span (from the caller's copy of vbounds).
+ *   DDPO_EINVAL: a null pointer, size not a multiple of patch, ld < 3 p p or ld not a multiple of 4, out not 16-byte aligned, a crop window
+ *   (top, left, size) outside rh x rw, and the LDS rule: rows x size x 3 bytes + 8 staged input rows of W x 3 bytes (each rounded up to 16)
+ *   + 3 KB must fit 160 KB.  No workspace and no state: calls on different streams may overlap.  The _host entry is the same arithmetic,
+ *   serially, on host memory (no GPU; it works `rows` out itself and checks the tables); resized_out_host (may be null) receives the
+ *   N x size x size x 3 bytes before normalisation. */
+int ddpo_clip_preprocess(const void* images, int is_float32, int N, int H, int W, int rh, int rw, int top, int left, int size, int patch,
+                         const int32_t* hcoef, const int32_t* hbounds, int hksize, const int32_t* vcoef, const int32_t* vbounds, int vksize,
+                         int rows, const float* norm, float* out, int ld, void* stream);
+int ddpo_clip_preprocess_host(const void* images, int is_float32, int N, int H, int W, int rh, int rw, int top, int left, int size, int patch,
+                              const int32_t* hcoef, const int32_t* hbounds, int hksize, const int32_t* vcoef, const int32_t* vbounds,
+                              int vksize, const float* norm, float* out_host, int ld, uint8_t* resized_out_host);
 int ddpo_timestep_embedding(const int32_t* ts, float* out, int B, int dim, void* stream); /* concat([cos, sin]) */
 int ddpo_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, void* stream);
 int ddpo_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, void* stream);
