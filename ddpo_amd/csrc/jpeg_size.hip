@@ -9,6 +9,9 @@
 //                     the stored coefficients), exclusive scan in scan order -> each block's bit offset, the image's total
 //   jq_emit           one lane per block: its codes OR-ed into the image's big-endian bit buffer at its offset
 //   jq_count          one workgroup per image: 0xFF bytes of the padded stream -> fixed bytes + ceil(bits / 8) + stuffed bytes, int64
+// ddpo_jpeg_encode produces the file as well: the same sequence with jq_pack in the place of jq_count.
+//   jq_pack           one workgroup per image: header, the stream's bytes with a 0x00 after every 0xFF (an exclusive scan of the 0xFF counts gives
+//                     each word its place; a pass's bytes are staged in LDS and stored 16 aligned bytes at a time), EOI, and the same length
 #include "common.h"
 #include "jpeg_size_core.h"
 
@@ -182,6 +185,76 @@ __global__ __launch_bounds__(SCAN_TB) void jq_count(const uint32_t* __restrict__
   }
 }
 
+// One pass packs SCAN_TB words: at most 8 bytes each, staged at the phase (0..15) of their address in the file buffer so that 16-byte pieces of the
+// stage are 16-byte pieces of memory.
+constexpr int PACK_STAGE = SCAN_TB * 8 + 16;
+
+__global__ __launch_bounds__(SCAN_TB) void jq_pack(const uint32_t* __restrict__ bitbuf, size_t words_per_image, const uint32_t* __restrict__ total,
+                                                   int H, int W, int quality, uint8_t* __restrict__ files, size_t stride,
+                                                   int64_t* __restrict__ lengths) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_out[PACK_STAGE];
+  __shared__ uint32_t s_wave[SCAN_TB / 64];
+  __shared__ uint32_t s_carry;
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const uint64_t bits = total[blockIdx.x];
+  const uint64_t nbytes = (bits + 7) >> 3;
+  const uint64_t nw = min((uint64_t)words_per_image, (bits + 31) >> 5);
+  const uint32_t* buf = bitbuf + (size_t)blockIdx.x * words_per_image;
+  uint8_t* row = files + (size_t)blockIdx.x * stride;
+  const uint64_t cap = stride;                                // nothing at or beyond this offset of the row is written
+  for (int i = t; i < JQ_HEADER_BYTES; i += SCAN_TB)
+    if ((uint64_t)i < cap) row[i] = jq_header_byte(i, H, W, quality);
+  if (t == 0) s_carry = 0;
+  __syncthreads();
+  for (uint64_t w0 = 0; w0 < nw; w0 += SCAN_TB) {
+    const uint64_t w = w0 + t;
+    const uint32_t word = w < nw ? buf[w] : 0u;
+    const uint32_t c = w < nw ? (uint32_t)jq_count_ff(word, w, bits) : 0u;
+    uint32_t inc = c;                                         // inclusive scan inside the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t v = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += v;
+    }
+    if (lane == 63) s_wave[wid] = inc;
+    __syncthreads();
+    const uint32_t carry = s_carry;                           // 0xFF bytes before this pass
+    uint32_t before = carry;
+    for (int k = 0; k < wid; ++k) before += s_wave[k];
+    before += inc - c;                                        // 0xFF bytes before this word
+    // the pass's bytes go to [at0, at0 + len) of the file
+    const uint64_t at0 = (uint64_t)JQ_HEADER_BYTES + w0 * 4 + carry;
+    const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(row + at0) & 15);
+    if (w < nw) {
+      uint8_t out[8];
+      uint64_t at;
+      const int n = jq_stuff_word(word, w, bits, before, out, at);
+      for (int k = 0; k < n; ++k) s_out[phase + (uint32_t)(at - at0) + k] = out[k];
+    }
+    __syncthreads();
+    if (t == SCAN_TB - 1) s_carry = before + c;
+    __syncthreads();
+    const uint32_t len = (uint32_t)(min(nbytes, (w0 + SCAN_TB) * 4) - w0 * 4) + (s_carry - carry);
+    // stage index i is file offset at0 - phase + i; the valid ones are [phase, end)
+    const uint32_t end = phase + (uint32_t)min((uint64_t)len, cap > at0 ? cap - at0 : 0);
+    for (uint32_t lo = (uint32_t)t * 16; lo < end; lo += SCAN_TB * 16) {
+      uint8_t* dst = row + at0 + lo - phase;                  // 16-byte aligned
+      if (lo >= phase && lo + 16 <= end) {
+        *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(s_out + lo);
+      } else {
+        for (uint32_t i = max(lo, phase); i < min(lo + 16, end); ++i) dst[i - lo] = s_out[i];
+      }
+    }
+    __syncthreads();                                          // the next pass writes the stage again
+  }
+  if (t == 0) {
+    const uint64_t eoi = (uint64_t)JQ_HEADER_BYTES + nbytes + s_carry;
+    if (eoi < cap) row[eoi] = 0xff;
+    if (eoi + 1 < cap) row[eoi + 1] = 0xd9;
+    lengths[blockIdx.x] = jq_file_bytes(bits, s_carry);
+  }
+}
+
 }  // namespace
 
 extern "C" int ddpo_jpeg_size_workspace_bytes(int N, int H, int W, size_t* out_host) {
@@ -191,33 +264,75 @@ extern "C" int ddpo_jpeg_size_workspace_bytes(int N, int H, int W, size_t* out_h
   return DDPO_OK;
 }
 
-extern "C" int ddpo_jpeg_size(const void* images, int is_float32, int N, int H, int W, int quality, void* workspace, size_t workspace_bytes,
-                              int64_t* bytes_out, void* stream) {
-  JqLayout l;
-  if (!images || !workspace || !bytes_out || quality < 1 || quality > 100 || !jq_layout(N, H, W, l)) return DDPO_EINVAL;
+namespace {
+
+struct JqBuffers {
+  int16_t* coef;
+  uint32_t *acbits, *offs, *total, *bitbuf;
+};
+
+// What ddpo_jpeg_size and ddpo_jpeg_encode share: the argument rules and the launches up to the finished bit buffers.
+int jq_launch_streams(const void* images, int is_float32, int N, int H, int W, int quality, void* workspace, size_t workspace_bytes, hipStream_t s,
+                      JqLayout& l, JqBuffers& b) {
+  if (!images || !workspace || quality < 1 || quality > 100 || !jq_layout(N, H, W, l)) return DDPO_EINVAL;
   if (workspace_bytes < l.bytes || (reinterpret_cast<uintptr_t>(workspace) & 15) || (is_float32 && (reinterpret_cast<uintptr_t>(images) & 3)))
     return DDPO_EINVAL;
   char* ws = static_cast<char*>(workspace);
-  int16_t* coef = reinterpret_cast<int16_t*>(ws + l.coef);
-  uint32_t* acbits = reinterpret_cast<uint32_t*>(ws + l.acbits);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(ws + l.offs);
-  uint32_t* total = reinterpret_cast<uint32_t*>(ws + l.total);
-  uint32_t* bitbuf = reinterpret_cast<uint32_t*>(ws + l.bitbuf);
-  hipStream_t s = as_stream(stream);
+  b.coef = reinterpret_cast<int16_t*>(ws + l.coef);
+  b.acbits = reinterpret_cast<uint32_t*>(ws + l.acbits);
+  b.offs = reinterpret_cast<uint32_t*>(ws + l.offs);
+  b.total = reinterpret_cast<uint32_t*>(ws + l.total);
+  b.bitbuf = reinterpret_cast<uint32_t*>(ws + l.bitbuf);
   const int mw = W / 16, mh = H / 16, nblk = mw * mh * 6;
   const size_t nblk_all = (size_t)nblk * N;
-  if (hipMemsetAsync(bitbuf, 0, l.words_per_image * N * sizeof(uint32_t), s) != hipSuccess) return DDPO_ELAUNCH;
+  if (hipMemsetAsync(b.bitbuf, 0, l.words_per_image * N * sizeof(uint32_t), s) != hipSuccess) return DDPO_ELAUNCH;
   const dim3 tgrid((unsigned)((size_t)N * mh * ((mw + MCUS - 1) / MCUS)));
   if (is_float32)
-    hipLaunchKernelGGL(jq_transform<true>, tgrid, dim3(TB), 0, s, images, H, W, quality, coef, acbits);
+    hipLaunchKernelGGL(jq_transform<true>, tgrid, dim3(TB), 0, s, images, H, W, quality, b.coef, b.acbits);
   else
-    hipLaunchKernelGGL(jq_transform<false>, tgrid, dim3(TB), 0, s, images, H, W, quality, coef, acbits);
+    hipLaunchKernelGGL(jq_transform<false>, tgrid, dim3(TB), 0, s, images, H, W, quality, b.coef, b.acbits);
   DDPO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(jq_scan, dim3(N), dim3(SCAN_TB), 0, s, coef, acbits, nblk, offs, total);
+  hipLaunchKernelGGL(jq_scan, dim3(N), dim3(SCAN_TB), 0, s, b.coef, b.acbits, nblk, b.offs, b.total);
   DDPO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(jq_emit, dim3((unsigned)((nblk_all + 63) / 64)), dim3(64), 0, s, coef, offs, nblk, nblk_all, bitbuf, l.words_per_image);
+  hipLaunchKernelGGL(jq_emit, dim3((unsigned)((nblk_all + 63) / 64)), dim3(64), 0, s, b.coef, b.offs, nblk, nblk_all, b.bitbuf, l.words_per_image);
   DDPO_LAUNCH_CHECK();
-  hipLaunchKernelGGL(jq_count, dim3(N), dim3(SCAN_TB), 0, s, bitbuf, l.words_per_image, total, bytes_out);
+  return DDPO_OK;
+}
+
+// libjpeg's limit on either dimension, and a row that holds at least the smallest file's fixed bytes
+bool jq_encode_args(int H, int W, size_t file_stride) { return H <= 65500 && W <= 65500 && file_stride >= DDPO_JPEG_FIXED_BYTES; }
+
+}  // namespace
+
+extern "C" int ddpo_jpeg_size(const void* images, int is_float32, int N, int H, int W, int quality, void* workspace, size_t workspace_bytes,
+                              int64_t* bytes_out, void* stream) {
+  JqLayout l;
+  JqBuffers b;
+  if (!bytes_out) return DDPO_EINVAL;
+  hipStream_t s = as_stream(stream);
+  const int rc = jq_launch_streams(images, is_float32, N, H, W, quality, workspace, workspace_bytes, s, l, b);
+  if (rc != DDPO_OK) return rc;
+  hipLaunchKernelGGL(jq_count, dim3(N), dim3(SCAN_TB), 0, s, b.bitbuf, l.words_per_image, b.total, bytes_out);
+  DDPO_LAUNCH_CHECK();
+  return DDPO_OK;
+}
+
+extern "C" int ddpo_jpeg_encode_max_bytes(int H, int W, size_t* out_host) {
+  JqLayout l;
+  if (!out_host || !jq_layout(1, H, W, l) || !jq_encode_args(H, W, DDPO_JPEG_FIXED_BYTES)) return DDPO_EINVAL;
+  *out_host = (size_t)jq_file_max_bytes((uint64_t)(H / 16) * (uint64_t)(W / 16) * 6);
+  return DDPO_OK;
+}
+
+extern "C" int ddpo_jpeg_encode(const void* images, int is_float32, int N, int H, int W, int quality, void* workspace, size_t workspace_bytes,
+                                uint8_t* files, size_t file_stride, int64_t* lengths, void* stream) {
+  JqLayout l;
+  JqBuffers b;
+  if (!files || !lengths || !jq_encode_args(H, W, file_stride)) return DDPO_EINVAL;
+  hipStream_t s = as_stream(stream);
+  const int rc = jq_launch_streams(images, is_float32, N, H, W, quality, workspace, workspace_bytes, s, l, b);
+  if (rc != DDPO_OK) return rc;
+  hipLaunchKernelGGL(jq_pack, dim3(N), dim3(SCAN_TB), 0, s, b.bitbuf, l.words_per_image, b.total, H, W, quality, files, file_stride, lengths);
   DDPO_LAUNCH_CHECK();
   return DDPO_OK;
 }
@@ -227,5 +342,15 @@ extern "C" int ddpo_jpeg_size_host(const uint8_t* rgb, int N, int H, int W, int 
   JqLayout l;
   if (!rgb || !bytes_out_host || quality < 1 || quality > 100 || !jq_layout(N, H, W, l)) return DDPO_EINVAL;
   for (int n = 0; n < N; ++n) bytes_out_host[n] = jq_host_image_bytes(rgb + (size_t)n * H * W * 3, H, W, quality);
+  return DDPO_OK;
+}
+
+extern "C" int ddpo_jpeg_encode_host(const uint8_t* rgb, int N, int H, int W, int quality, uint8_t* files_host, size_t file_stride,
+                                     int64_t* lengths_host) {
+  JqLayout l;
+  if (!rgb || !files_host || !lengths_host || quality < 1 || quality > 100 || !jq_layout(N, H, W, l) || !jq_encode_args(H, W, file_stride))
+    return DDPO_EINVAL;
+  for (int n = 0; n < N; ++n)
+    lengths_host[n] = jq_host_image_file(rgb + (size_t)n * H * W * 3, H, W, quality, files_host + (size_t)n * file_stride, file_stride);
   return DDPO_OK;
 }

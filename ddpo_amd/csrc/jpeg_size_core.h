@@ -1,7 +1,9 @@
 // JPEG byte counting: the arithmetic of a baseline 4:2:0 libjpeg encode (standard Huffman tables, one scan, no restart markers), as
 // host + device inline functions.  csrc/jpeg_size.hip runs them from kernels and from the serial host entry (ddpo_jpeg_size_host), so whether
 // the count equals the encoder's is decided by the host entry against a real encoder (tests/test_jpeg_size_cpu.py) and the kernels only have
-// to agree with the host entry.  Plain C++17: tools/native/jpeg_size_host_check.cpp includes this file without a HIP compiler.
+// to agree with the host entry.  The file itself (ddpo_jpeg_encode, ddpo_jpeg_encode_host) adds two functions at the end: the header bytes and the
+// byte-stuffing step, held to the encoder's file the same way (tests/test_jpeg_encode_cpu.py).  Plain C++17: tools/native/jpeg_size_host_check.cpp
+// and jpeg_encode_host_check.cpp include this file without a HIP compiler.
 //
 // Every step is integer and follows the encoder: 16-bit fixed-point RGB -> YCbCr, h2v2 chroma averaging with the alternating 1, 2 bias, level
 // shift, the "islow" forward DCT (CONST_BITS 13, PASS1_BITS 2, output scaled by 8), quantisation sign(c) * floor((|c| + (d >> 1)) / d) with
@@ -262,6 +264,63 @@ JQ_HD int64_t jq_file_bytes(uint64_t total_bits, uint64_t ff_bytes) { return (in
 // words of the bit buffer of one image of `nblk` blocks (+1: the writer's flush may touch the word after the last full one)
 JQ_HD uint64_t jq_bitbuf_words(uint64_t nblk) { return nblk * (JQ_MAX_BLOCK_BITS / 32) + 1; }
 
+// ---------------------------------------------------------------------------------------------------------------- the file
+// Byte i (0 .. JQ_HEADER_BYTES - 1) of everything the encoder writes before the scan data of an H x W image at `quality`:
+//   SOI | APP0 (JFIF 1.01, no units, density 1 x 1) | DQT 0 | DQT 1 | SOF0 | DHT DC0 | DHT AC0 | DHT DC1 | DHT AC1 | SOS
+// A function of the position and nothing else: no table is built at run time, on either side.
+#define JQ_HEADER_BYTES DDPO_JPEG_HEADER_BYTES
+static_assert(JQ_HEADER_BYTES + 2 == JQ_FIXED_BYTES, "header + EOI");
+constexpr uint8_t kJqApp0[18] = {0xff, 0xe0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+constexpr uint8_t kJqSofTail[10] = {3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1};            // 3 components: id, sampling, quantisation table
+constexpr uint8_t kJqSos[14] = {0xff, 0xda, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+
+JQ_HD uint8_t jq_dht_byte(int i, int cls_id, const uint8_t* bits, const uint8_t* vals, int nvals) {
+  if (i < 5) return i == 0 ? 0xff : i == 1 ? 0xc4 : i == 2 ? 0 : i == 3 ? (uint8_t)(19 + nvals) : (uint8_t)cls_id;
+  return i < 21 ? bits[i - 4] : vals[i - 21];                     // bits[1..16], then the symbols
+}
+
+JQ_HD uint8_t jq_header_byte(int i, int H, int W, int quality) {
+  if (i < 2) return i == 0 ? 0xff : 0xd8;
+  if ((i -= 2) < 18) return kJqApp0[i];
+  if ((i -= 18) < 2 * 69) {
+    const int c = i / 69, k = i % 69;
+    if (k < 5) return k == 0 ? 0xff : k == 1 ? 0xdb : k == 2 ? 0 : k == 3 ? 67 : (uint8_t)c;
+    return (uint8_t)(jq_divisor(quality, c, kJqNatural[k - 5]) >> 3);
+  }
+  if ((i -= 2 * 69) < 19) {
+    if (i < 5) return i == 0 ? 0xff : i == 1 ? 0xc0 : i == 2 ? 0 : i == 3 ? 17 : 8;
+    if (i < 9) return (uint8_t)((i < 7 ? H : W) >> ((i & 1) ? 8 : 0));      // i = 5, 6: H high, low; 7, 8: W high, low
+    return kJqSofTail[i - 9];
+  }
+  if ((i -= 19) < 33) return jq_dht_byte(i, 0x00, kJqDcLumBits, kJqDcVals, 12);
+  if ((i -= 33) < 183) return jq_dht_byte(i, 0x10, kJqAcLumBits, kJqAcLumVals, 162);
+  if ((i -= 183) < 33) return jq_dht_byte(i, 0x01, kJqDcChrBits, kJqDcVals, 12);
+  if ((i -= 33) < 183) return jq_dht_byte(i, 0x11, kJqAcChrBits, kJqAcChrVals, 162);
+  return kJqSos[i - 183];
+}
+
+// The file bytes that word `wi` of a bit buffer holding `total_bits` bits contributes, given the 0xFF bytes among the stream bytes before it:
+// its stream bytes in order, each 0xFF followed by a 0x00, the last byte of the stream padded with 1-bits first (jq_count_ff's convention, so a
+// padded byte that becomes 0xFF is stuffed too).  Returns how many (0 for a word past the end of the stream, at most 8) and sets the offset in
+// the file at which they go.
+JQ_HD int jq_stuff_word(uint32_t word, uint64_t wi, uint64_t total_bits, uint64_t ff_before, uint8_t out[8], uint64_t& offset) {
+  const uint64_t nbytes = (total_bits + 7) >> 3;
+  offset = (uint64_t)JQ_HEADER_BYTES + wi * 4 + ff_before;
+  int n = 0;
+  for (int k = 0; k < 4; ++k) {
+    const uint64_t b = wi * 4 + k;
+    if (b >= nbytes) break;
+    uint32_t byte = (word >> (24 - 8 * k)) & 0xffu;
+    if (b == nbytes - 1 && (total_bits & 7)) byte |= (1u << (8 - (int)(total_bits & 7))) - 1u;
+    out[n++] = (uint8_t)byte;
+    if (byte == 0xffu) out[n++] = 0;
+  }
+  return n;
+}
+
+// upper bound of one file: header, EOI, and the longest scan with every byte stuffed
+JQ_HD uint64_t jq_file_max_bytes(uint64_t nblk) { return (uint64_t)JQ_FIXED_BYTES + 2 * ((nblk * JQ_MAX_BLOCK_BITS + 7) >> 3); }
+
 // Quantised coefficients (zig-zag order) of block j (0..5) of the MCU whose 16x16 pixels start at `rgb` (row stride `stride` bytes, 3 bytes / pixel).
 inline void jq_host_mcu_block(const uint8_t* rgb, size_t stride, int j, int quality, int16_t* zz) {
   int data[64], tmp[8], col[8];
@@ -298,11 +357,11 @@ inline void jq_host_mcu_block(const uint8_t* rgb, size_t stride, int j, int qual
   for (int k = 0; k < 64; ++k) zz[k] = (int16_t)data[kJqNatural[k]];
 }
 
-// Serial reference over the functions above: file size of one H x W RGB image (H, W multiples of 16).  `total_bits_out`, `ff_out`: optional.
-inline int64_t jq_host_image_bytes(const uint8_t* rgb, int H, int W, int quality, uint64_t* total_bits_out = nullptr, uint64_t* ff_out = nullptr) {
+// Serial reference over the functions above: the bit buffer of one H x W RGB image (H, W multiples of 16) into `buf`; returns the bits it holds.
+inline uint64_t jq_host_image_stream(const uint8_t* rgb, int H, int W, int quality, std::vector<uint32_t>& buf) {
   const int mw = W / 16, mh = H / 16;
   const uint64_t nblk = (uint64_t)mw * mh * 6, nwords = jq_bitbuf_words(nblk);
-  std::vector<uint32_t> buf(nwords, 0u);
+  buf.assign(nwords, 0u);
   std::vector<int16_t> dc(nblk, 0);
   uint64_t pos = 0;
   int16_t zz[64];
@@ -322,9 +381,37 @@ inline int64_t jq_host_image_bytes(const uint8_t* rgb, int H, int W, int quality
     wr.flush();
     pos += cnt.bits;
   }
+  return pos;
+}
+
+// File size of one image.  `total_bits_out`, `ff_out`: optional.
+inline int64_t jq_host_image_bytes(const uint8_t* rgb, int H, int W, int quality, uint64_t* total_bits_out = nullptr, uint64_t* ff_out = nullptr) {
+  std::vector<uint32_t> buf;
+  const uint64_t pos = jq_host_image_stream(rgb, H, W, quality, buf);
   uint64_t ff = 0;
   for (uint64_t wi = 0; wi * 32 < pos; ++wi) ff += (uint64_t)jq_count_ff(buf[wi], wi, pos);
   if (total_bits_out) *total_bits_out = pos;
   if (ff_out) *ff_out = ff;
+  return jq_file_bytes(pos, ff);
+}
+
+// The file of one image into `row`, of which at most `stride` bytes are written: a longer file leaves its first `stride` bytes.  Returns the
+// file's full length either way; bytes of the row past min(length, stride) are not touched.
+inline int64_t jq_host_image_file(const uint8_t* rgb, int H, int W, int quality, uint8_t* row, size_t stride) {
+  std::vector<uint32_t> buf;
+  const uint64_t pos = jq_host_image_stream(rgb, H, W, quality, buf);
+  for (uint64_t i = 0; i < JQ_HEADER_BYTES && i < stride; ++i) row[i] = jq_header_byte((int)i, H, W, quality);
+  uint64_t ff = 0;
+  for (uint64_t wi = 0; wi * 32 < pos; ++wi) {
+    uint8_t out[8];
+    uint64_t at;
+    const int n = jq_stuff_word(buf[wi], wi, pos, ff, out, at);
+    for (int k = 0; k < n; ++k)
+      if (at + k < stride) row[at + k] = out[k];
+    ff += (uint64_t)jq_count_ff(buf[wi], wi, pos);
+  }
+  const uint64_t eoi = (uint64_t)JQ_HEADER_BYTES + ((pos + 7) >> 3) + ff;
+  if (eoi < stride) row[eoi] = 0xff;
+  if (eoi + 1 < stride) row[eoi + 1] = 0xd9;
   return jq_file_bytes(pos, ff);
 }

@@ -162,6 +162,10 @@ _SIGS = {
     "ddpo_jpeg_size_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "ddpo_jpeg_size": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "ddpo_jpeg_size_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    # ... and the file itself (additive to ABI v14; the same file)
+    "ddpo_jpeg_encode_max_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "ddpo_jpeg_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ddpo_jpeg_encode_host": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     # CLIP image preprocessing into the patch matrix (additive to ABI v14; csrc/clip_preprocess.hip)
     "ddpo_clip_preprocess": (c_int, [c_void_p] + [c_int] * 10 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "ddpo_clip_preprocess_host": (c_int, [c_void_p] + [c_int] * 10 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
@@ -1656,6 +1660,72 @@ def jpeg_size_host(images_u8, quality=95):
     out = np.zeros(n, dtype=np.int64)
     _check(load().ddpo_jpeg_size_host(a.ctypes.data_as(c_void_p), n, h, w, quality, out.ctypes.data_as(c_void_p)), "ddpo_jpeg_size_host")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ JPEG files
+JPEG_HEADER_BYTES = 623       # DDPO_JPEG_HEADER_BYTES: everything a file holds before its scan data
+JPEG_MAX_DIM = 65500          # the largest height or width libjpeg writes
+
+
+def _jpeg_encode_args(shape, quality):
+    n, h, w, quality = _jpeg_size_args(shape, quality)
+    if h > JPEG_MAX_DIM or w > JPEG_MAX_DIM:
+        raise ValueError(f"jpeg_encode: {h} x {w} images: a JPEG file holds at most {JPEG_MAX_DIM} rows and columns")
+    return n, h, w, quality
+
+
+def jpeg_encode_max_bytes(h, w):
+    """Upper bound of the length of one h x w file of jpeg_encode (ddpo_jpeg_encode_max_bytes): a row stride no file exceeds."""
+    nb = c_size_t(0)
+    rc = load().ddpo_jpeg_encode_max_bytes(int(h), int(w), byref(nb))
+    if rc == -1:
+        raise ValueError(f"jpeg_encode: {h} x {w} images: {JPEG_SIZE_RULE}, and at most {JPEG_MAX_DIM}")
+    _check(rc, "ddpo_jpeg_encode_max_bytes")
+    return int(nb.value)
+
+
+def jpeg_encode(images, quality=80, workspace=None, files=None, stride=None):
+    """The bytes PIL's Image.save(buf, "JPEG", quality=q) writes for every image of an N x H x W x 3 CUDA tensor — uint8, or float32 in [0, 1]
+    truncated as (x * 255).astype(uint8) — on the current stream (ddpo_jpeg_encode).  Returns (files, lengths): a uint8 CUDA tensor (N, stride)
+    whose row n starts with file n, and the int64 CUDA lengths, equal to jpeg_size's.  A file longer than `stride` (default H * W * 3 + 625;
+    jpeg_encode_max_bytes(H, W) is never exceeded) leaves its first `stride` bytes and still reports its full length; bytes of a row past the
+    file are not written.  `files`: a contiguous uint8 CUDA tensor (N, stride) to write into.  `workspace`: as for jpeg_size."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype not in (torch.float32, torch.uint8):
+        raise DdpoHipError("jpeg_encode needs a float32 or uint8 CUDA tensor")
+    n, h, w, quality = _jpeg_encode_args(images.shape, quality)
+    if stride is None:
+        stride = int(files.shape[1]) if files is not None and files.dim() == 2 else h * w * 3 + JPEG_FIXED_BYTES
+    if int(stride) != stride or stride < JPEG_FIXED_BYTES:
+        raise ValueError(f"jpeg_encode: the row stride must be an integer >= {JPEG_FIXED_BYTES}, got {stride!r}")
+    stride = int(stride)
+    nb = jpeg_size_workspace_bytes(n, h, w)
+    if workspace is None:
+        workspace = _scratch(nb, images.device, "jpeg_size")
+    if workspace.dtype != torch.uint8 or workspace.numel() < nb or workspace.device != images.device:
+        raise DdpoHipError(f"jpeg_encode: the workspace must be a uint8 tensor of >= {nb} bytes on {images.device}")
+    if files is None:
+        files = torch.empty((n, stride), dtype=torch.uint8, device=images.device)
+    if files.dtype != torch.uint8 or tuple(files.shape) != (n, stride) or not files.is_contiguous() or files.device != images.device:
+        raise DdpoHipError(f"jpeg_encode: `files` must be a contiguous uint8 tensor of shape ({n}, {stride}) on {images.device}")
+    lengths = torch.empty(n, dtype=torch.int64, device=images.device)
+    _check(load().ddpo_jpeg_encode(_p(images), int(images.dtype == torch.float32), n, h, w, quality, _p(workspace), workspace.numel(), _p(files),
+                                   stride, _p(lengths), _stream()), "ddpo_jpeg_encode")
+    return files, lengths
+
+
+def jpeg_encode_host(images_u8, quality=80):
+    """The same files produced serially on the host (ddpo_jpeg_encode_host) for a uint8 N x H x W x 3 numpy array, as a list of bytes: the
+    GPU-free reference."""
+    import numpy as np
+    a = np.ascontiguousarray(images_u8)
+    if a.dtype != np.uint8:
+        raise ValueError("jpeg_encode_host needs uint8 images")
+    n, h, w, quality = _jpeg_encode_args(a.shape, quality)
+    stride = jpeg_encode_max_bytes(h, w)
+    files, lengths = np.empty((n, stride), dtype=np.uint8), np.zeros(n, dtype=np.int64)
+    _check(load().ddpo_jpeg_encode_host(a.ctypes.data_as(c_void_p), n, h, w, quality, files.ctypes.data_as(c_void_p), stride,
+                                        lengths.ctypes.data_as(c_void_p)), "ddpo_jpeg_encode_host")
+    return [files[i, :lengths[i]].tobytes() for i in range(n)]
 
 
 # ------------------------------------------------------------------------------------------------ CLIP image preprocessing

@@ -6,12 +6,14 @@ Behavioural mirror of the registry / calling convention of /root/reference/ddpo/
 images: float32 (N,H,W,3) in [0,1]; scores: (N,) or (N,1) numpy; info: dict of numpy arrays.
 Callbacks run in a worker thread of the entrypoint (ThreadPoolExecutor, max_workers=2) next to the sampling of the
 following batch, so they must not touch the sampler's HIP stream: the host ones below are pure CPU code and the
-on-device ones (aesthetic, clip_score, jpeg_device, neg_jpeg_device, aesthetic_device, clip_score_device) use their own streams.
+on-device ones (aesthetic, clip_score, jpeg_device, neg_jpeg_device, aesthetic_device, clip_score_device, llava_bertscore_device,
+llava_vqa_device) use their own streams.
 
 In scope (BASELINE.json configs): jpeg, neg_jpeg (+ jpeg_device, neg_jpeg_device: the same rewards counted on the device), aesthetic, llava_bertscore (+ its sibling llava_vqa wire format), and clip_score: the
 prompt-alignment reward that needs no server (CLIPScore on the engine's own CLIP towers; not in the reference, which aligns through LLaVA).
 aesthetic_device / clip_score_device are aesthetic / clip_score with the CLIP preprocessing done on the device too, so the decoded batch never
-leaves HBM (`wants_device_images`).
+leaves HBM (`wants_device_images`).  llava_bertscore_device / llava_vqa_device are the LLaVA rewards with the JPEG files they send encoded on the
+device (models/jpeg_encode.py): only the compressed files cross to the host.
 The other reward ideas of the reference (rotational / mirror symmetry, thumbnail, BLIP-2 vqa, ...) are not part of
 any benchmark config; add them as plugins with `register`.
 """
@@ -191,6 +193,58 @@ def _llava_session():
     return sess
 
 
+def _bertscore_requests(sess, url, timeout, batch_size, files, prompts):
+    """The request / reply loop of llava_bertscore over the images' JPEG files (a list of bytes), batched as np.array_split batches the images."""
+    nb = int(np.ceil(len(files) / batch_size))
+    scores, info = [], {"precision": [], "f1": [], "outputs": []}
+    for idx_b, prm_b in zip(np.array_split(np.arange(len(files)), nb), np.array_split(np.asarray(prompts), nb)):
+        payload = {"images": [files[i] for i in idx_b],
+                   "queries": [["Answer concisely: what is going on in this image?"]] * len(idx_b),
+                   "answers": [[f"The image contains {p}"] for p in prm_b]}
+        reply = pickle.loads(sess.post(url, data=pickle.dumps(payload), timeout=timeout).content)
+        scores += np.array(reply["recall"]).squeeze().reshape(-1).tolist()
+        for k in info:
+            info[k] += np.array(reply[k]).squeeze().reshape(-1).tolist()
+    return np.array(scores), {k: np.array(v) for k, v in info.items()}
+
+
+def _vqa_requests(sess, url, timeout, batch_size, files, metadata):
+    """The request / reply loop of llava_vqa over the images' JPEG files (a list of bytes)."""
+    nb = int(np.ceil(len(files) / batch_size))
+    metadata = list(metadata)
+    scores, answers = [], []
+    for idx_b in np.array_split(np.arange(len(files)), nb):
+        metas = [metadata[i] for i in idx_b]
+        payload = {"images": [files[i] for i in idx_b], "queries": [m["questions"] for m in metas]}
+        reply = pickle.loads(sess.post(url, data=pickle.dumps(payload), timeout=timeout).content)
+        for m, outs in zip(metas, reply["outputs"]):
+            assert len(outs) == len(m["answers"])
+            hits = [a in o for a, o in zip(m["answers"], outs)]          # case-sensitive substring test (:357-360)
+            scores.append(float(np.mean(np.array(hits, dtype=int))))
+        answers += reply["outputs"]
+    return np.array(scores), {"answers": np.array(answers)}
+
+
+def _host_jpeg_files(images):
+    return [_to_jpeg_bytes(im) for im in (np.asarray(images) * 255).astype(np.uint8)]
+
+
+def _device_jpeg_files():
+    """images -> JPEG files at quality 80: a CUDA batch through one JpegEncoder (models/jpeg_encode.py, created with the first such batch, on its
+    own stream), a host array through PIL as the host callbacks do."""
+    encoder = []
+
+    def _files(images, ready):
+        if not _is_device_batch(images):
+            return _host_jpeg_files(images)
+        if not encoder:
+            from ..models.jpeg_encode import JpegEncoder
+            encoder.append(JpegEncoder(quality=80, device=images.device))
+        return encoder[0](images, ready=ready)
+
+    return _files
+
+
 def llava_bertscore(devices=None, jit=False, url="http://127.0.0.1:8085", batch_size=16, timeout=120):
     """Alignment reward served by a LLaVA + BERTScore server (reference :465-537).  Wire format: POST of
     pickle.dumps({"images": [jpeg bytes, q=80], "queries": [[str]], "answers": [[str]]}); the reply is a pickled dict
@@ -199,18 +253,7 @@ def llava_bertscore(devices=None, jit=False, url="http://127.0.0.1:8085", batch_
 
     def _fn(images, prompts, metadata):
         del metadata
-        images = (np.asarray(images) * 255).astype(np.uint8)
-        nb = int(np.ceil(len(images) / batch_size))
-        scores, info = [], {"precision": [], "f1": [], "outputs": []}
-        for img_b, prm_b in zip(np.array_split(images, nb), np.array_split(np.asarray(prompts), nb)):
-            payload = {"images": [_to_jpeg_bytes(im) for im in img_b],
-                       "queries": [["Answer concisely: what is going on in this image?"]] * len(img_b),
-                       "answers": [[f"The image contains {p}"] for p in prm_b]}
-            reply = pickle.loads(sess.post(url, data=pickle.dumps(payload), timeout=timeout).content)
-            scores += np.array(reply["recall"]).squeeze().reshape(-1).tolist()
-            for k in info:
-                info[k] += np.array(reply[k]).squeeze().reshape(-1).tolist()
-        return np.array(scores), {k: np.array(v) for k, v in info.items()}
+        return _bertscore_requests(sess, url, timeout, batch_size, _host_jpeg_files(images), prompts)
 
     return _fn
 
@@ -223,21 +266,35 @@ def llava_vqa_satisfaction(devices=None, jit=False, url="http://127.0.0.1:8085",
 
     def _fn(images, prompts, metadata):
         del prompts
-        images = (np.asarray(images) * 255).astype(np.uint8)
-        nb = int(np.ceil(len(images) / batch_size))
-        metadata = list(metadata)
-        scores, answers = [], []
-        for img_b, meta_b in zip(np.array_split(images, nb), np.array_split(np.arange(len(images)), nb)):
-            metas = [metadata[i] for i in meta_b]
-            payload = {"images": [_to_jpeg_bytes(im) for im in img_b], "queries": [m["questions"] for m in metas]}
-            reply = pickle.loads(sess.post(url, data=pickle.dumps(payload), timeout=timeout).content)
-            for m, outs in zip(metas, reply["outputs"]):
-                assert len(outs) == len(m["answers"])
-                hits = [a in o for a, o in zip(m["answers"], outs)]          # case-sensitive substring test (:357-360)
-                scores.append(float(np.mean(np.array(hits, dtype=int))))
-            answers += reply["outputs"]
-        return np.array(scores), {"answers": np.array(answers)}
+        return _vqa_requests(sess, url, timeout, batch_size, _host_jpeg_files(images), metadata)
 
+    return _fn
+
+
+def llava_bertscore_device(devices=None, jit=False, url="http://127.0.0.1:8085", batch_size=16, timeout=120):
+    """`llava_bertscore` without the host trip of the pixels: the same requests, scores and info, byte for byte.  A CUDA tensor straight from the
+    VAE decoder (`wants_device_images`: the entrypoint then keeps the batch in HBM, see evaluate_callbacks_device) is encoded once, on the device,
+    into the files PIL writes at quality 80 (models/jpeg_encode.py, csrc/jpeg_size.hip) and only those cross to the host; host arrays take
+    `llava_bertscore`'s own path (PIL).  Image height and width must be multiples of 16."""
+    sess, files_of = _llava_session(), _device_jpeg_files()
+
+    def _fn(images, prompts, metadata, ready=None):
+        del metadata
+        return _bertscore_requests(sess, url, timeout, batch_size, files_of(images, ready), prompts)
+
+    _fn.wants_device_images = True
+    return _fn
+
+
+def llava_vqa_device(devices=None, jit=False, url="http://127.0.0.1:8085", batch_size=4, timeout=120):
+    """`llava_vqa` without the host trip of the pixels: the same requests, scores and info; see llava_bertscore_device."""
+    sess, files_of = _llava_session(), _device_jpeg_files()
+
+    def _fn(images, prompts, metadata, ready=None):
+        del prompts
+        return _vqa_requests(sess, url, timeout, batch_size, files_of(images, ready), metadata)
+
+    _fn.wants_device_images = True
     return _fn
 
 
@@ -301,4 +358,6 @@ callback_fns = {
     "clip_score_device": clip_score_device_fn,
     "llava_bertscore": llava_bertscore,
     "llava_vqa": llava_vqa_satisfaction,
+    "llava_bertscore_device": llava_bertscore_device,
+    "llava_vqa_device": llava_vqa_device,
 }

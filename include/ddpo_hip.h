@@ -456,6 +456,20 @@ int ddpo_jpeg_size_workspace_bytes(int N, int H, int W, size_t* out_host);
 int ddpo_jpeg_size(const void* images, int is_float32, int N, int H, int W, int quality, void* workspace, size_t workspace_bytes,
                    int64_t* bytes_out, void* stream);
 int ddpo_jpeg_size_host(const uint8_t* rgb, int N, int H, int W, int quality, int64_t* bytes_out_host);
+/* The file itself (csrc/jpeg_size.hip; additive to ABI v14): files[n * file_stride ..] = the bytes of that same baseline JPEG — byte for byte
+ *   what PIL's Image.save(buf, "JPEG", quality=q) writes — and lengths[n] = its length, the value ddpo_jpeg_size returns.  Inputs, rules and
+ *   workspace (ddpo_jpeg_size_workspace_bytes) are ddpo_jpeg_size's; in addition H, W <= 65500 (the format's limit as libjpeg applies it) and
+ *   file_stride >= DDPO_JPEG_FIXED_BYTES, else DDPO_EINVAL.  files: device, N rows of file_stride bytes, no alignment required.
+ *   Prefix rule: a file longer than file_stride leaves its first file_stride bytes in the row, and lengths[n] still reports the full length
+ *   (compare it with file_stride, then repeat with ddpo_jpeg_encode_max_bytes, which no file of that size exceeds:
+ *   625 + 2 * ceil(blocks * 1664 / 8)).  Nothing is written past a row, and bytes of a row beyond min(lengths[n], file_stride) are not written at
+ *   all.  The first DDPO_JPEG_HEADER_BYTES of every file of one (H, W, quality) are the same: everything before the scan data.
+ *   ddpo_jpeg_encode_host: the same arithmetic, serially, on host memory (no GPU). */
+#define DDPO_JPEG_HEADER_BYTES 623
+int ddpo_jpeg_encode_max_bytes(int H, int W, size_t* out_host);
+int ddpo_jpeg_encode(const void* images, int is_float32, int N, int H, int W, int quality, void* workspace, size_t workspace_bytes,
+                     uint8_t* files, size_t file_stride, int64_t* lengths, void* stream);
+int ddpo_jpeg_encode_host(const uint8_t* rgb, int N, int H, int W, int quality, uint8_t* files_host, size_t file_stride, int64_t* lengths_host);
 /* CLIP image preprocessing into the patch matrix (csrc/clip_preprocess.hip; additive to ABI v14): out[(n, gy, gx)][(c, ky, kx)] =
  *   norm[byte][c], byte = pixel (gy p + ky, gx p + kx), channel c, of the size x size centre crop of image n after an 8-bit two-pass bicubic resize
  *   to rh x rw (what Pillow's Image.resize(BICUBIC) returns for an RGB image); columns 3 p p .. ld - 1 are written as zeros.  One launch.
