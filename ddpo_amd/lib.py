@@ -169,6 +169,12 @@ _SIGS = {
     # CLIP image preprocessing into the patch matrix (additive to ABI v14; csrc/clip_preprocess.hip)
     "ddpo_clip_preprocess": (c_int, [c_void_p] + [c_int] * 10 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "ddpo_clip_preprocess_host": (c_int, [c_void_p] + [c_int] * 10 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    # symmetry rewards: exact per-image sums, the four right-angle turns (additive to ABI v14; csrc/symmetry.hip)
+    "ddpo_symmetry_stats_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "ddpo_symmetry_stats": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ddpo_symmetry_stats_host": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p]),
+    "ddpo_rotate4_u8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
+    "ddpo_rotate4_u8_host": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1893,6 +1899,110 @@ def clip_preprocess_host(images, size, patch, k_pad, return_resized=False):
                                             int(patch), ptr(hc), ptr(hb), hk, ptr(vc), ptr(vb), vk, ptr(norm), ptr(out), int(k_pad), ptr(resized)),
            "ddpo_clip_preprocess_host")
     return (out, resized) if return_resized else out
+
+
+# ------------------------------------------------------------------------------------------------ symmetry rewards
+SYMMETRY_MODES = {"mirror": 0, "rot180": 1}
+SYMMETRY_MAX_W = 10880        # SY_MAX_W of csrc/symmetry_core.h
+SYMMETRY_WIDTH_RULE = f"the width must be at most {SYMMETRY_MAX_W} pixels: a pair of rows is staged as bytes in 64 KB of LDS"
+
+
+def _symmetry_mode(mode):
+    if mode not in SYMMETRY_MODES:
+        raise ValueError(f"symmetry_stats: mode must be one of {sorted(SYMMETRY_MODES)}, got {mode!r}")
+    return SYMMETRY_MODES[mode]
+
+
+def _symmetry_images(who, images, is_tensor, square=False):
+    """The rules the symmetry entries share with clip_preprocess, each refused by name: (N, H, W) of a float32 / uint8 contiguous
+    N x H x W x 3 batch that is not empty (and square, for rotate4_u8)."""
+    f32, u8 = (torch.float32, torch.uint8) if is_tensor else ("float32", "uint8")
+    if images.dtype not in (f32, u8):
+        raise ValueError(f"{who}: the dtype must be float32 or uint8, got {images.dtype}")
+    shape = tuple(images.shape)
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError(f"{who} needs N x H x W x 3 images (last dimension 3), got shape {shape}")
+    if shape[0] < 1 or shape[1] < 1 or shape[2] < 1:
+        raise ValueError(f"{who}: empty batch or empty images, got shape {shape}")
+    if not (images.is_contiguous() if is_tensor else images.flags.c_contiguous):
+        raise ValueError(f"{who} needs contiguous images (N x H x W x 3 in memory order)")
+    if square and shape[1] != shape[2]:
+        raise ValueError(f"{who} needs square images (a right-angle turn of a {shape[1]} x {shape[2]} image has another shape)")
+    return int(shape[0]), int(shape[1]), int(shape[2])
+
+
+def symmetry_stats_workspace_bytes(n, h, w, mode):
+    nb = c_size_t(0)
+    rc = load().ddpo_symmetry_stats_workspace_bytes(int(n), int(h), int(w), _symmetry_mode(mode), byref(nb))
+    if rc == -1:
+        raise ValueError(f"symmetry_stats: {n} images of {h} x {w}: sizes must be positive and {SYMMETRY_WIDTH_RULE}")
+    _check(rc, "ddpo_symmetry_stats_workspace_bytes")
+    return int(nb.value)
+
+
+def symmetry_stats(images, mode, workspace=None, out=None):
+    """Four exact sums per image of an N x H x W x 3 CUDA tensor — uint8, or float32 in [0, 1] truncated as (x * 255).astype(uint8) — as an
+    int64 CUDA tensor (N, 4), on the current stream (ddpo_symmetry_stats).  With a a byte and b its partner under `mode` — "mirror":
+    (y, W-1-x, c), "rot180": (H-1-y, W-1-x, c) —: [0] sum of ((a - b) mod 256)^2 mod 256 (what numpy's uint8 arithmetic makes of (a - b) ** 2),
+    [1] sum of a, [2] sum of a^2, [3] sum of a b.  `workspace`: a uint8 CUDA tensor of at least symmetry_stats_workspace_bytes(N, H, W, mode)
+    bytes; default: this stream's scratch.  ValueError names the broken rule."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda:
+        raise DdpoHipError("symmetry_stats needs a CUDA tensor")
+    m = _symmetry_mode(mode)
+    n, h, w = _symmetry_images("symmetry_stats", images, True)
+    nb = symmetry_stats_workspace_bytes(n, h, w, mode)
+    if workspace is None:
+        workspace = _scratch(nb, images.device, "symmetry_stats")
+    if workspace.dtype != torch.uint8 or workspace.numel() < nb or workspace.device != images.device:
+        raise DdpoHipError(f"symmetry_stats: the workspace must be a uint8 tensor of >= {nb} bytes on {images.device}")
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.int64, device=images.device)
+    if out.dtype != torch.int64 or tuple(out.shape) != (n, 4) or not out.is_contiguous() or out.device != images.device:
+        raise DdpoHipError(f"symmetry_stats: out must be a contiguous int64 ({n}, 4) tensor on {images.device}")
+    _check(load().ddpo_symmetry_stats(_p(images), int(images.dtype == torch.float32), n, h, w, m, _p(out), _p(workspace), workspace.numel(),
+                                      _stream()), "ddpo_symmetry_stats")
+    return out
+
+
+def symmetry_stats_host(images, mode):
+    """The same sums computed serially on the host (ddpo_symmetry_stats_host) for a uint8 or float32 N x H x W x 3 numpy array, (N, 4) int64: the
+    GPU-free reference."""
+    import numpy as np
+    a = np.asarray(images)
+    m = _symmetry_mode(mode)
+    n, h, w = _symmetry_images("symmetry_stats_host", a, False)
+    if w > SYMMETRY_MAX_W:
+        raise ValueError(f"symmetry_stats_host: {h} x {w} images: {SYMMETRY_WIDTH_RULE}")
+    out = np.zeros((n, 4), dtype=np.int64)
+    _check(load().ddpo_symmetry_stats_host(a.ctypes.data_as(c_void_p), int(a.dtype == np.float32), n, h, w, m, out.ctypes.data_as(c_void_p)),
+           "ddpo_symmetry_stats_host")
+    return out
+
+
+def rotate4_u8(images, out=None):
+    """The four right-angle turns of a square N x S x S x 3 CUDA batch — uint8, or float32 in [0, 1] truncated as (x * 255).astype(uint8) — as
+    one uint8 CUDA tensor (4N, S, S, 3), on the current stream (ddpo_rotate4_u8): block k N + n is PIL.Image.rotate(90 k) of image n, k = 0..3.
+    ValueError names the broken rule."""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda:
+        raise DdpoHipError("rotate4_u8 needs a CUDA tensor")
+    n, s, _ = _symmetry_images("rotate4_u8", images, True, square=True)
+    if out is None:
+        out = torch.empty((4 * n, s, s, 3), dtype=torch.uint8, device=images.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (4 * n, s, s, 3) or not out.is_contiguous() or out.device != images.device:
+        raise DdpoHipError(f"rotate4_u8: out must be a contiguous uint8 ({4 * n}, {s}, {s}, 3) tensor on {images.device}")
+    _check(load().ddpo_rotate4_u8(_p(images), int(images.dtype == torch.float32), n, s, s, _p(out), _stream()), "ddpo_rotate4_u8")
+    return out
+
+
+def rotate4_u8_host(images):
+    """The same turns made serially on the host (ddpo_rotate4_u8_host) for a uint8 or float32 N x S x S x 3 numpy array: the GPU-free reference."""
+    import numpy as np
+    a = np.asarray(images)
+    n, s, _ = _symmetry_images("rotate4_u8_host", a, False, square=True)
+    out = np.zeros((4 * n, s, s, 3), dtype=np.uint8)
+    _check(load().ddpo_rotate4_u8_host(a.ctypes.data_as(c_void_p), int(a.dtype == np.float32), n, s, s, out.ctypes.data_as(c_void_p)),
+           "ddpo_rotate4_u8_host")
+    return out
 
 
 def timestep_embedding(ts, dim):

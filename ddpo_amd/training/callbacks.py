@@ -6,16 +6,19 @@ Behavioural mirror of the registry / calling convention of /root/reference/ddpo/
 images: float32 (N,H,W,3) in [0,1]; scores: (N,) or (N,1) numpy; info: dict of numpy arrays.
 Callbacks run in a worker thread of the entrypoint (ThreadPoolExecutor, max_workers=2) next to the sampling of the
 following batch, so they must not touch the sampler's HIP stream: the host ones below are pure CPU code and the
-on-device ones (aesthetic, clip_score, jpeg_device, neg_jpeg_device, aesthetic_device, clip_score_device, llava_bertscore_device,
-llava_vqa_device) use their own streams.
+on-device ones (aesthetic, clip_score, rotational and every `*_device` name) use their own streams.
 
 In scope (BASELINE.json configs): jpeg, neg_jpeg (+ jpeg_device, neg_jpeg_device: the same rewards counted on the device), aesthetic, llava_bertscore (+ its sibling llava_vqa wire format), and clip_score: the
 prompt-alignment reward that needs no server (CLIPScore on the engine's own CLIP towers; not in the reference, which aligns through LLaVA).
 aesthetic_device / clip_score_device are aesthetic / clip_score with the CLIP preprocessing done on the device too, so the decoded batch never
 leaves HBM (`wants_device_images`).  llava_bertscore_device / llava_vqa_device are the LLaVA rewards with the JPEG files they send encoded on the
 device (models/jpeg_encode.py): only the compressed files cross to the host.
-The other reward ideas of the reference (rotational / mirror symmetry, thumbnail, BLIP-2 vqa, ...) are not part of
-any benchmark config; add them as plugins with `register`.
+The symmetry family of the reference — mirror, mirror_corr, rotational_corr (pixel rewards; the first and the last in uint8 arithmetic that
+wraps, reproduced to the bit) and rotational (CLIP features of the four right-angle turns) — is here too, each with a `*_device` twin that reads the
+decoded batch where it is (models/symmetry.py, csrc/symmetry.hip): exact integer sums per image instead of PIL copies, turns and CLIP
+preprocessing on the device instead of 4N PIL rotations and resizes.
+The remaining reward ideas of the reference (thumbnail, consistency, diversity, BLIP-2 vqa, arange) are not part of any benchmark config; add
+them as plugins with `register`.
 """
 import io
 import pickle
@@ -173,6 +176,176 @@ def clip_score_device_fn(devices=None, rng=0, cache="cache", jit=True, weights_d
         else:
             scores, cosine = scorer(np.asarray(images, dtype=np.float32), prompts, return_cosine=True)
         return scores[:, None], {"cosine": cosine, "synthetic_weights": np.array(scorer.synthetic)}
+
+    _fn.wants_device_images = True
+    return _fn
+
+
+# ------------------------------------------------------------------------------------------------ symmetry
+# The pixel rewards of the reference subtract and square uint8 arrays, so both operations WRAP modulo 256 before the mean: the reward is not the
+# mean squared error.  The host callbacks below reproduce that number (held to results recorded from the reference,
+# tests/golden/reference_symmetry.json); the device twins get it from an exact integer sum (lib.symmetry_stats, column 0); both report the true
+# mean squared difference beside it (info["mse"]).  Partners are array views: u8[:, :, ::-1] is what PIL's ImageOps.mirror returns and
+# u8[:, ::-1, ::-1] what Image.rotate(180) returns, for any height and width.
+def _truncated_bytes(images):
+    """float (N,H,W,3) in [0,1] -> uint8 by truncation, the whole batch at once"""
+    return (np.asarray(images) * 255).astype(np.uint8)
+
+
+def _partner(u8, mode):
+    return u8[:, :, ::-1] if mode == "mirror" else u8[:, ::-1, ::-1]
+
+
+def _wrapped_and_true_mse(u8, mode):
+    """(mean of the uint8 square of the uint8 difference — each wraps modulo 256 —, mean of the true squared difference), both (N,) float64 and
+    exact: integer sums below 2^53, divided once."""
+    other = _partner(u8, mode)
+    diff = u8 - other                                           # uint8: modulo 256
+    wide = u8.astype(np.int64) - other
+    return (diff * diff).mean(axis=(1, 2, 3)), (wide * wide).sum(axis=(1, 2, 3)) / u8[0].size
+
+
+def _wrapped_mse_fn(mode):
+    def _fn(images, prompts, metadata):
+        del prompts, metadata
+        wrapped, true = _wrapped_and_true_mse(_truncated_bytes(images), mode)
+        return -wrapped, {"mse": true}
+
+    return _fn
+
+
+def mirror_symmetry_fn(devices=None, jit=False):
+    """reward = -mean((image - left-right mirror image) ** 2) over the image's bytes, in uint8 arithmetic that wraps (reference :244-260).
+    Returns (N,) float64; info["mse"] is the same mean without the wrap."""
+    del devices, jit
+    return _wrapped_mse_fn("mirror")
+
+
+def rotational_correlation_fn(devices=None, jit=False):
+    """reward = -mean((image - image turned by 180 degrees) ** 2), in uint8 arithmetic that wraps (reference :216-241: its list of angles holds
+    the one turn, so its average over turns is this one term).  Returns (N,) float64; info["mse"] is the same mean without the wrap."""
+    del devices, jit
+    return _wrapped_mse_fn("rot180")
+
+
+def mirror_correlation_fn(devices=None, jit=False):
+    """reward = -(Pearson correlation of the image's bytes with their left-right mirror image) in float32, as the reference computes it
+    (:263-292).  The mirror image is a permutation of the image, so it has the image's mean and variance: the image is centred once, in float32,
+    and the correlation is sum(centred * mirrored centred) / sum(centred ** 2).  Returns (N,) float32; a constant image gives nan (0 / 0), as
+    there.  Float32 sums: within a few 1e-8 of the exact value."""
+    del devices, jit
+
+    def _fn(images, prompts, metadata):
+        del prompts, metadata
+        x = _truncated_bytes(images).astype(np.float32) / np.float32(255)
+        n = len(x)
+        centred = x - x.reshape(n, -1).mean(axis=1).reshape(n, 1, 1, 1)
+        cross = (centred * _partner(centred, "mirror")).reshape(n, -1).sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return -(cross / (centred * centred).reshape(n, -1).sum(axis=1)), {}
+
+    return _fn
+
+
+def _symmetry_stats_of(mode):
+    from ..models.symmetry import SymmetryStats
+    return SymmetryStats(mode)
+
+
+def _wrapped_mse_device_fn(mode):
+    stats_of = _symmetry_stats_of(mode)
+
+    def _fn(images, prompts, metadata, ready=None):
+        del prompts, metadata
+        n = int(np.prod(images.shape[1:]))
+        stats = stats_of(images, ready=ready)
+        return -(stats[:, 0] / n), {"mse": (2 * stats[:, 2] - 2 * stats[:, 3]) / n}
+
+    _fn.wants_device_images = True
+    return _fn
+
+
+def mirror_symmetry_device_fn(devices=None, jit=False):
+    """`mirror` computed on the device: the same (N,) float64 scores and info["mse"], equal to `mirror`'s exactly — every sum is an integer below
+    2^53 that is divided once, which is what `ndarray.mean` of a uint8 array computes (models/symmetry.py, csrc/symmetry.hip), on a private HIP
+    stream.  Takes host images like every callback, or a CUDA tensor straight from the VAE decoder (`wants_device_images`: the entrypoint then
+    keeps the batch in HBM, see evaluate_callbacks_device)."""
+    del devices, jit
+    return _wrapped_mse_device_fn("mirror")
+
+
+def rotational_correlation_device_fn(devices=None, jit=False):
+    """`rotational_corr` computed on the device: the same scores and info["mse"] exactly; see mirror_symmetry_device_fn."""
+    del devices, jit
+    return _wrapped_mse_device_fn("rot180")
+
+
+def mirror_correlation_device_fn(devices=None, jit=False):
+    """`mirror_corr` from exact sums: with n bytes a and their mirror partners b, correlation = (n sum(a b) - sum(a)^2) / (n sum(a^2) - sum(a)^2)
+    in integer arithmetic, rounded once — the mirror image is a permutation of the image, so both variances are the same.  Returns (N,) float32,
+    nan for a constant image; close to `mirror_corr`'s float32 sums, not bit-equal."""
+    del devices, jit
+    stats_of = _symmetry_stats_of("mirror")
+
+    def _fn(images, prompts, metadata, ready=None):
+        del prompts, metadata
+        n = int(np.prod(images.shape[1:]))
+        scores = []
+        for _, sa, saa, sab in stats_of(images, ready=ready).tolist():            # Python integers: no overflow, no rounding before the division
+            num, den = n * sab - sa * sa, n * saa - sa * sa
+            scores.append(-np.float32(num / den) if den else np.float32("nan"))
+        return np.array(scores, dtype=np.float32), {}
+
+    _fn.wants_device_images = True
+    return _fn
+
+
+def _mean_turn_angle(feats, n_images):
+    """Features (4 N, proj), one block of N rows per turn (0, 90, 180, 270 degrees) -> (N,) float32: minus the mean, over the three turns, of the
+    angle in degrees between an image's features and the turned image's.  Cosines outside [0, 1] are clipped, so an angle is at most 90."""
+    blocks = feats.reshape(-1, n_images, feats.shape[-1])
+    upright, turned = blocks[0], blocks[1:]
+    lengths = np.linalg.norm(upright, axis=-1)[None] * np.linalg.norm(turned, axis=-1)
+    cosines = np.clip((upright[None] * turned).sum(axis=-1) / lengths, 0, 1)
+    degrees = np.arccos(cosines) * 180 / np.pi
+    return -(degrees.sum(axis=0) / len(turned))
+
+
+def _rotational_embedder(embedder, rng, cache, weights_dir):
+    if embedder is not None:
+        return embedder
+    from ..models.symmetry import RotationalEmbedder
+    return RotationalEmbedder(weights_dir=weights_dir, cache=cache, seed=rng)
+
+
+def rotational_symmetry_fn(devices=None, jit=True, embedder=None, rng=0, cache="cache", weights_dir=None):
+    """reward = -(mean angle, in degrees, between the CLIP ViT-L/14 image features of an image and of its turns by 90, 180 and 270 degrees)
+    (reference :166-213), the features on the engine's own kernels (models/symmetry.py:RotationalEmbedder, on a private HIP stream).  Weights as
+    for `clip_score`; missing weights RAISE unless DDPO_ALLOW_SYNTHETIC=1, in which case info['synthetic_weights'] is True.  `embedder`: anything
+    called as embedder(images) -> (4 N, proj) features in the reference's order (tests).  Returns (N,) float32."""
+    del devices, jit
+    emb = _rotational_embedder(embedder, rng, cache, weights_dir)
+
+    def _fn(images, prompts, metadata):
+        del prompts, metadata
+        images = np.asarray(images, dtype=np.float32)
+        return _mean_turn_angle(np.asarray(emb(images)), len(images)), {"synthetic_weights": np.array(getattr(emb, "synthetic", False))}
+
+    return _fn
+
+
+def rotational_symmetry_device_fn(devices=None, jit=True, embedder=None, rng=0, cache="cache", weights_dir=None):
+    """`rotational` without the host trip: the same scores and info, bit for bit.  A square CUDA tensor straight from the VAE decoder
+    (`wants_device_images`) is truncated to bytes and turned by one kernel (lib.rotate4_u8, csrc/symmetry.hip) and preprocessed by another
+    (lib.clip_preprocess) on the embedder's private stream; host arrays take `rotational`'s own path (PIL).  `embedder` is called as
+    embedder(images, ready=ready) for a device batch."""
+    del devices, jit
+    emb = _rotational_embedder(embedder, rng, cache, weights_dir)
+
+    def _fn(images, prompts, metadata, ready=None):
+        del prompts, metadata
+        feats = emb(images, ready=ready) if _is_device_batch(images) else emb(np.asarray(images, dtype=np.float32))
+        return _mean_turn_angle(np.asarray(feats), len(images)), {"synthetic_weights": np.array(getattr(emb, "synthetic", False))}
 
     _fn.wants_device_images = True
     return _fn
@@ -360,4 +533,12 @@ callback_fns = {
     "llava_vqa": llava_vqa_satisfaction,
     "llava_bertscore_device": llava_bertscore_device,
     "llava_vqa_device": llava_vqa_device,
+    "mirror": mirror_symmetry_fn,
+    "mirror_corr": mirror_correlation_fn,
+    "rotational_corr": rotational_correlation_fn,
+    "rotational": rotational_symmetry_fn,
+    "mirror_device": mirror_symmetry_device_fn,
+    "mirror_corr_device": mirror_correlation_device_fn,
+    "rotational_corr_device": rotational_correlation_device_fn,
+    "rotational_device": rotational_symmetry_device_fn,
 }

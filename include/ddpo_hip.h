@@ -489,6 +489,26 @@ int ddpo_clip_preprocess(const void* images, int is_float32, int N, int H, int W
 int ddpo_clip_preprocess_host(const void* images, int is_float32, int N, int H, int W, int rh, int rw, int top, int left, int size, int patch,
                               const int32_t* hcoef, const int32_t* hbounds, int hksize, const int32_t* vcoef, const int32_t* vbounds,
                               int vksize, const float* norm, float* out_host, int ld, uint8_t* resized_out_host);
+/* Symmetry rewards (csrc/symmetry.hip; additive to ABI v14).  images: N x H x W x 3 (NHWC, contiguous), uint8 or (is_float32) float32 in [0, 1],
+ *   truncated as (uint8)(x * 255.0f) (clamped; NaN -> 0), as for ddpo_clip_preprocess.
+ * ddpo_symmetry_stats: stats_out[n][0..3] (int64, device, 8-byte aligned) = four sums over all H W 3 bytes a of image n, b being the partner of a —
+ *   mode 0 (mirror): byte (y, W-1-x, c); mode 1 (rotate 180): byte (H-1-y, W-1-x, c):
+ *     [0] sum of (((a - b) mod 256)^2 mod 256)   what uint8 arithmetic makes of (a - b) ** 2
+ *     [1] sum of a      [2] sum of a^2      [3] sum of a b
+ *   All integer, so exact and independent of the order of summation; the unwrapped sum of (a - b)^2 is 2 [2] - 2 [3].  Two launches on `stream`:
+ *   per-workgroup sums into `workspace` (device, >= ddpo_symmetry_stats_workspace_bytes, 8-byte aligned), then one wave per image adds them.  No
+ *   atomics, nothing to zero, no state outside the arguments: calls on different streams with different workspaces may overlap.
+ *   DDPO_EINVAL: a null pointer, a mode other than 0 / 1, N, H or W < 1, W > 10880 (a row pair is staged in 64 KB of LDS), a small workspace,
+ *   misaligned pointers.
+ * ddpo_rotate4_u8: out (uint8, device, 4N x S x S x 3): block k N + n is image n turned by 90 k degrees counter-clockwise, k = 0..3 — what
+ *   PIL.Image.rotate(90 k) returns for a square image (np.rot90(a, k)).  One launch; every input pixel is read once.  H != W is DDPO_EINVAL.
+ * The _host entries are the same arithmetic, serially, on host memory (no GPU). */
+int ddpo_symmetry_stats_workspace_bytes(int N, int H, int W, int mode, size_t* out_host);
+int ddpo_symmetry_stats(const void* images, int is_float32, int N, int H, int W, int mode, int64_t* stats_out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int ddpo_symmetry_stats_host(const void* images, int is_float32, int N, int H, int W, int mode, int64_t* stats_out_host);
+int ddpo_rotate4_u8(const void* images, int is_float32, int N, int H, int W, uint8_t* out, void* stream);
+int ddpo_rotate4_u8_host(const void* images, int is_float32, int N, int H, int W, uint8_t* out_host);
 int ddpo_timestep_embedding(const int32_t* ts, float* out, int B, int dim, void* stream); /* concat([cos, sin]) */
 int ddpo_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, void* stream);
 int ddpo_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, void* stream);

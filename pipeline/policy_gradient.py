@@ -149,7 +149,7 @@ def main(argv=None):
     # ------------------------------ callbacks -------------------------------#
     callback_fns = {args.filter_field: training.callback_fns[args.filter_field]()}
     executor = futures.ThreadPoolExecutor(max_workers=2)     # rewards run next to the sampling of the following batch
-    # rewards that read the decoder's output where it is (jpeg_device, neg_jpeg_device, aesthetic_device, clip_score_device): the batch stays in HBM, only the inspection PNG's image leaves it
+    # rewards that read the decoder's output where it is (every `*_device` name of training/callbacks.py): the batch stays in HBM, only the inspection PNG's image leaves it
     device_images = all(getattr(fn, "wants_device_images", False) for fn in callback_fns.values())
 
     per_prompt_stats = None
