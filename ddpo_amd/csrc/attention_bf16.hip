@@ -15,6 +15,25 @@
 // is staged), B = P^T.  One workgroup = 4 waves x 32 queries; the 32x32 C fragment of S^T (row = key, col = query = lane&31) is converted
 // in registers to the B operand of the second product: for lane half h the 8 k-slots of MFMA step u are the keys
 // 16u + 4h + {0,1,2,3, 8,9,10,11} (exactly the rows that half holds), and the V^T fragment is read with the same map.
+//
+// d = 40, stacked layout (round 9; DDPO_ATTN_STACK=0 restores the plain one).  On the plain layout d = 40 pays for padding: 40 is padded to 48 in
+// the score reduction (3 passes x 3 k-steps x 2 sub-tiles = 18 MFMAs per 64-key tile, lane half 1 of every third k-step all zeros) and
+// 40 channels + the ones row to 64 rows in each of the V^T hi and lo planes (2 tiles x 2 planes x 4 steps = 16 MFMAs): 34 per tile.  Stacked, the
+// same products take 16 + 12 = 28:
+//   K row (LDS and image), 88 bf16 = 176 B (an odd multiple of 16 B: b128 rows 16 lanes apart in a lane group land on distinct 16-byte slots):
+//       [k_hi(0..39) | k_lo(0..39) | 8 zeros] = 8-element chunks c = 0..10, chunk 10 the zero pad.  No K lo plane: the K part is 11 KiB.
+//   S^T = k_hi q_hi + k_lo q_hi + k_hi q_lo as ONE reduction of 120 in 8 MFMA steps per 32-key sub-tile; qh[0..4] / ql[0..4] = the 8-element
+//   chunks of the bf16 hi / lo of the scaled query; lane half h reads
+//       step s = 0..4:  A = K chunk 2s + h        B = qh[(2s + h) mod 5]     (k_hi q_hi, chunks 0..4;  k_lo q_hi, chunks 5..9)
+//       step s = 5, 6:  A = K chunk 2(s - 5) + h  B = ql[2(s - 5) + h]       (k_hi q_lo, dk 0..31)
+//       step s = 7:     h = 0: A = K chunk 4, B = ql[4];   h = 1: A = chunk 10 (zeros), B = zeros
+//   issued in the order 3, 4, 5, 6, 7, 2, 0, 1 — the small terms first, as on the plain layout; fp32 accumulate (attn_scores_tile, the one
+//   place that fixes the order for all three kernels).
+//   V^T (f16p only): ONE plane of 96 rows at pitch 68: rows 0..39 f16 hi, row 40 ones (the softmax denominator), 41..47 zeros, 48..87 f16 lo,
+//   88..95 zeros; 13056 B, padded to 13 KiB for the LDS-DMA.  O^T = V^T P^T is 3 tiles x 4 steps x ONE MFMA; the hi and the lo row of a channel
+//   accumulate apart (channel dc = 32n + 8g + 4h + i in tile n, register group g; row dc + 48 in the SAME lane at (n + 1, g + 2) or (n + 2, g - 2))
+//   and are added in fp32 before the normalisation (attn_store_o).  The bf16x3 variant splits P as well, so stacking V would save it one tile
+//   in six: it keeps its two V^T planes and takes the stacked K only.
 #include "common.h"
 #include <cstdlib>
 
@@ -55,6 +74,161 @@ __device__ __forceinline__ void split2h(float a, float b, uint32_t& hi, uint32_t
 #define MFMA32H(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 #define ATTN_P_SHIFT 14.0f            /* p = exp2(s - m + 14): the f16 probabilities use the exponent range [2^-14, 2^14] */
 #define ATTN_F16_ONE 0x3C00u
+
+// Geometry of one 64-key tile's K / V^T image = the LDS picture of every kernel below (byte offsets; the staging code, the packer and the
+// MFMA helpers all take theirs from here).  D = 40 with DKP = 80 selects the stacked layout of the header comment: K hi and lo side by
+// side in one row, and — where DVP / 2 still holds the D channels and the ones row, which is the f16p packing (DVP = 96) — V^T hi and lo in
+// one plane of DVP rows, lo at row DVP / 2.
+constexpr bool attn_kstk(int D, int DKP) { return D == 40 && DKP == 2 * D; }      // (d = 8 is padded to DKP = 16: not stacked)
+template <int D, int DKP, int DVP>
+struct AttnImg {
+  static constexpr int KT = 64, LDK = DKP + 8, LDVT = KT + 4;      // keys per tile; bf16 per K row ((DKP+8)*2 bytes = odd multiple of 16 B ->
+                                                                   // conflict-free b128 rows); f16 per V^T row (136 B -> 32 rows hit distinct even banks for ds_read_b64)
+  static constexpr bool KSTK = attn_kstk(D, DKP), VSTK = KSTK && DVP / 2 > D;
+  static constexpr int K_BYTES = KT * LDK * 2, VT_BYTES = DVP * LDVT * 2;
+  static constexpr int KP = KSTK ? K_BYTES : 2 * K_BYTES;                             // K part of an image
+  static constexpr int VP = VSTK ? (VT_BYTES + 1023) / 1024 * 1024 : 2 * VT_BYTES;    // V^T part (stacked: padded to whole KiB for the LDS-DMA)
+  static constexpr int KLO = KSTK ? D * 2 : K_BYTES;                                  // K lo element (key, dk) lies this far behind K hi's
+  static constexpr int VLO = VSTK ? (DVP / 2) * LDVT * 2 : VT_BYTES;                  // V^T lo element (d, key) lies this far behind V^T hi's
+  static constexpr int NDT = DVP / 32;                                                // 32-row tiles of O^T
+  static constexpr int BYTES = KP + VP;                                               // multiple of 16
+  static constexpr int CHUNKS = BYTES / 16;
+};
+
+// Zero a tile image in LDS once (the padding — K columns past the live ones, V^T rows past D — is never written again), then set the ones row
+// of V^T hi.  The caller's next barrier publishes it.
+template <class I, int D, bool ONES>
+__device__ __forceinline__ void attn_image_init(char* smem, int t) {
+  for (int i = t; i < I::CHUNKS; i += 256) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0u, 0u, 0u, 0u);
+  if constexpr (ONES) {
+    __syncthreads();
+    if (t < I::KT) reinterpret_cast<uint16_t*>(smem + I::KP)[D * I::LDVT + t] = (uint16_t)ATTN_F16_ONE;
+  }
+}
+
+// Stage keys kt0 .. kt0 + 63 of one (batch, head) into the image: K row-major as bf16 hi / lo, V transposed as f16 (F16P) or bf16 hi / lo;
+// keys past Nk are written as zeros.  The self-staging kernel and the packer share it: the image IS the LDS picture.
+template <class I, int D, bool F16P>
+__device__ __forceinline__ void attn_stage_tile(char* smem, const float* kb, int ldk, const float* vb, int ldv, int kt0, int Nk, int t) {
+  char* Khi = smem; char* Klo = Khi + I::KLO;
+  uint16_t* vh = reinterpret_cast<uint16_t*>(smem + I::KP);
+  uint16_t* vl = reinterpret_cast<uint16_t*>(smem + I::KP + I::VLO);
+  for (int i = t; i < I::KT * (D / 4); i += 256) {
+    const int key = i / (D / 4), c4 = i - key * (D / 4);
+    float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
+    if (kt0 + key < Nk) {
+      kv = *reinterpret_cast<const float4*>(kb + (int64_t)(kt0 + key) * ldk + c4 * 4);
+      vv = *reinterpret_cast<const float4*>(vb + (int64_t)(kt0 + key) * ldv + c4 * 4);
+    }
+    uint32_t h0, l0, h1, l1;
+    split2(kv.x, kv.y, h0, l0);
+    split2(kv.z, kv.w, h1, l1);
+    *reinterpret_cast<uint2*>(Khi + (key * I::LDK + c4 * 4) * 2) = make_uint2(h0, h1);
+    *reinterpret_cast<uint2*>(Klo + (key * I::LDK + c4 * 4) * 2) = make_uint2(l0, l1);
+    if (F16P) { split2h(vv.x, vv.y, h0, l0); split2h(vv.z, vv.w, h1, l1); }
+    else { split2(vv.x, vv.y, h0, l0); split2(vv.z, vv.w, h1, l1); }
+    const int d0 = c4 * 4;
+    vh[(d0 + 0) * I::LDVT + key] = (uint16_t)(h0 & 0xFFFFu); vh[(d0 + 1) * I::LDVT + key] = (uint16_t)(h0 >> 16);
+    vh[(d0 + 2) * I::LDVT + key] = (uint16_t)(h1 & 0xFFFFu); vh[(d0 + 3) * I::LDVT + key] = (uint16_t)(h1 >> 16);
+    vl[(d0 + 0) * I::LDVT + key] = (uint16_t)(l0 & 0xFFFFu); vl[(d0 + 1) * I::LDVT + key] = (uint16_t)(l0 >> 16);
+    vl[(d0 + 2) * I::LDVT + key] = (uint16_t)(l1 & 0xFFFFu); vl[(d0 + 3) * I::LDVT + key] = (uint16_t)(l1 >> 16);
+  }
+}
+
+// The scaled queries of one 32-query block as B operands of the first product: lane (li, h) holds query li.
+//   plain layout:   f[2s] / f[2s + 1] = bf16 hi / lo of Q[dk = 16s + 8h .. + 8], k-step s
+//   stacked layout: f[s] = the B operand of step s of the header comment's table (qh / ql = the five 8-element chunks of bf16 hi / lo of Q)
+template <int D, int DKP>
+struct AttnQFrag {
+  static constexpr bool STK = attn_kstk(D, DKP);
+  static constexpr int N = STK ? 8 : 2 * (DKP / 16);
+  bf16x8 f[N];
+  __device__ __forceinline__ void load(const float* qp, float scale_log2e, int h) {
+    if constexpr (STK) {
+      uint4 qh[5], ql[5];
+#pragma unroll
+      for (int c = 0; c < 5; ++c) {
+        const float4 a = reinterpret_cast<const float4*>(qp)[2 * c], b = reinterpret_cast<const float4*>(qp)[2 * c + 1];
+        split2(a.x * scale_log2e, a.y * scale_log2e, qh[c].x, ql[c].x);
+        split2(a.z * scale_log2e, a.w * scale_log2e, qh[c].y, ql[c].y);
+        split2(b.x * scale_log2e, b.y * scale_log2e, qh[c].z, ql[c].z);
+        split2(b.z * scale_log2e, b.w * scale_log2e, qh[c].w, ql[c].w);
+      }
+      auto sel = [&](const uint4& a1, const uint4& a0) {       // lane half 1 : lane half 0
+        return __builtin_bit_cast(bf16x8, make_uint4(h ? a1.x : a0.x, h ? a1.y : a0.y, h ? a1.z : a0.z, h ? a1.w : a0.w));
+      };
+      const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+      f[0] = sel(qh[1], qh[0]); f[1] = sel(qh[3], qh[2]); f[2] = sel(qh[0], qh[4]); f[3] = sel(qh[2], qh[1]); f[4] = sel(qh[4], qh[3]);
+      f[5] = sel(ql[1], ql[0]); f[6] = sel(ql[3], ql[2]); f[7] = sel(zero, ql[4]);
+    } else {
+#pragma unroll
+      for (int s = 0; s < DKP / 16; ++s) {
+        uint32_t hi[4], lo[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int dk = 16 * s + 8 * h + 2 * e;
+          const float a = dk < D ? qp[dk] * scale_log2e : 0.f;
+          const float c = dk + 1 < D ? qp[dk + 1] * scale_log2e : 0.f;
+          split2(a, c, hi[e], lo[e]);
+        }
+        f[2 * s] = __builtin_bit_cast(bf16x8, make_uint4(hi[0], hi[1], hi[2], hi[3]));
+        f[2 * s + 1] = __builtin_bit_cast(bf16x8, make_uint4(lo[0], lo[1], lo[2], lo[3]));
+      }
+    }
+  }
+};
+
+// S^T = K Q^T for the two 32-key sub-tiles of one tile, bf16x3: the ONE place that fixes the order of the first product's MFMAs (all three
+// kernels call it, so a variant's bits do not depend on the kernel).  K = the image's K part in LDS.
+//   plain:   per k-step s and sub-tile: k_lo q_hi, k_hi q_lo, k_hi q_hi (small terms first), s ascending
+//   stacked: the eight steps of the header comment's table in the order 3, 4 (k_lo q_hi), 5, 6, 7 (k_hi q_lo), 2 (mixed), 0, 1 (k_hi q_hi):
+//            small terms first again
+template <int D, int DKP, int DVP>
+__device__ __forceinline__ void attn_scores_tile(const char* K, int li, int h, const AttnQFrag<D, DKP>& q, f32x16 (&sacc)[2]) {
+  using I = AttnImg<D, DKP, DVP>;
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sacc[j][r] = 0.f;
+  if constexpr (I::KSTK) {
+    const int off7 = h ? 160 : 64;           // step 7: lane half 0 reads chunk 4 (k_hi 32..39), lane half 1 the zero pad chunk 10
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int s = i < 5 ? i + 3 : (i == 5 ? 2 : i - 6);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int row = (j * 32 + li) * I::LDK * 2;
+        const int off = s < 5 ? 32 * s + 16 * h : (s < 7 ? 32 * (s - 5) + 16 * h : off7);      // chunk 2s + h, 2(s - 5) + h, 4 | 10
+        sacc[j] = MFMA32(*reinterpret_cast<const bf16x8*>(K + row + off), q.f[s], sacc[j]);
+      }
+    }
+  } else {
+    const char* Khi = K; const char* Klo = K + I::KLO;
+#pragma unroll
+    for (int s = 0; s < DKP / 16; ++s) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int off = ((j * 32 + li) * I::LDK + 16 * s + 8 * h) * 2;
+        const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Khi + off);
+        const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Klo + off);
+        sacc[j] = MFMA32(kl, q.f[2 * s], sacc[j]);
+        sacc[j] = MFMA32(kh, q.f[2 * s + 1], sacc[j]);
+        sacc[j] = MFMA32(kh, q.f[2 * s], sacc[j]);
+      }
+    }
+  }
+}
+
+// Keys past Nk in the last tile score -inf (this lane holds keys 32j + (r&3) + 8(r>>2) + 4h of the tile)
+__device__ __forceinline__ void attn_mask_tail(f32x16 (&sacc)[2], int kt0, int Nk, int h) {
+  if (kt0 + 64 > Nk) {                     // only the last tile can hold padded keys (uniform branch)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (kt0 + 32 * j + (r & 3) + 8 * (r >> 2) + 4 * h >= Nk) sacc[j][r] = -INFINITY;
+  }
+}
 
 // Online-softmax step shared by the three kernels below (identical instruction sequence -> identical bits): running maximum, the tile's
 // probabilities as f16 B-operand fragments (step u = 2j + half uses accumulator registers 8 half .. 8 half + 7 of sub-tile j), and — only when
@@ -97,17 +271,21 @@ __device__ __forceinline__ void attn_softmax_tile(const f32x16 (&sacc)[2], float
 // O^T += V^T P^T for one 64-key tile: A fragment of step u = V^T[d = 32n + li][16u + 4h + {0..3, 8..11}] (f16 hi / lo planes in LDS), B = ph[u].
 // Per accumulator the order is fixed (lo then hi, u ascending) — shared by all three kernels; the fragments of step u + 1 are requested before
 // the MFMAs of step u are issued, and the two passes of a step alternate between the accumulators.
-template <int NDT, int LDVT, int QB = 1>
+// VSTK (stacked plane: the lo rows are rows of the same plane, DVP / 2 further down): ONE pass per step over the NDT tiles of that plane; the
+// hi and the lo row of a channel accumulate apart and meet in attn_store_o.
+template <int NDT, int LDVT, int QB = 1, bool VSTK = false>
 __device__ __forceinline__ void attn_pv_tile(const char* Vhi, const char* Vlo, int li, int h, const f16x8 (*ph)[4], f32x16 (*oacc)[NDT]) {
-  f16x8 vh[2][NDT], vl[2][NDT];
+  f16x8 vh[2][NDT], vl[2][VSTK ? 1 : NDT];
   auto fetch = [&](int u, int slot) {
 #pragma unroll
     for (int n = 0; n < NDT; ++n) {
       const int off = ((32 * n + li) * LDVT + 16 * u + 4 * h) * 2;
       const uint2 a0 = *reinterpret_cast<const uint2*>(Vhi + off), a1 = *reinterpret_cast<const uint2*>(Vhi + off + 16);
-      const uint2 c0 = *reinterpret_cast<const uint2*>(Vlo + off), c1 = *reinterpret_cast<const uint2*>(Vlo + off + 16);
       vh[slot][n] = __builtin_bit_cast(f16x8, make_uint4(a0.x, a0.y, a1.x, a1.y));
-      vl[slot][n] = __builtin_bit_cast(f16x8, make_uint4(c0.x, c0.y, c1.x, c1.y));
+      if constexpr (!VSTK) {
+        const uint2 c0 = *reinterpret_cast<const uint2*>(Vlo + off), c1 = *reinterpret_cast<const uint2*>(Vlo + off + 16);
+        vl[slot][n] = __builtin_bit_cast(f16x8, make_uint4(c0.x, c0.y, c1.x, c1.y));
+      }
     }
   };
   fetch(0, 0);
@@ -115,10 +293,12 @@ __device__ __forceinline__ void attn_pv_tile(const char* Vhi, const char* Vlo, i
   for (int u = 0; u < 4; ++u) {
     if (u + 1 < 4) fetch(u + 1, (u + 1) & 1);
     __builtin_amdgcn_sched_barrier(0);       // keep the requests of step u + 1 in front of the MFMAs of step u (the scheduler sinks them otherwise)
+    if constexpr (!VSTK) {
 #pragma unroll
-    for (int qb = 0; qb < QB; ++qb)
+      for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
-      for (int n = 0; n < NDT; ++n) oacc[qb][n] = MFMA32H(vl[u & 1][n], ph[qb][u], oacc[qb][n]);
+        for (int n = 0; n < NDT; ++n) oacc[qb][n] = MFMA32H(vl[u & 1][n], ph[qb][u], oacc[qb][n]);
+    }
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
@@ -196,7 +376,7 @@ __device__ __forceinline__ void attn_pv_tile_x3(const char* Vhi, const char* Vlo
 }
 
 // One tile's softmax + second product for either variant (all three kernels call this, so a variant's bits do not depend on the kernel)
-template <bool F16P, bool ONES, int NDT, int LDVT>
+template <bool F16P, bool ONES, int NDT, int LDVT, bool VSTK>
 __device__ __forceinline__ void attn_tile_tail(const f32x16 (&sacc)[2], float& m_run, float& l_run, f32x16 (&oacc)[NDT], const char* Vhi, const char* Vlo,
                                                int li, int h) {
   float alpha;
@@ -210,7 +390,7 @@ __device__ __forceinline__ void attn_tile_tail(const f32x16 (&sacc)[2], float& m
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[n][r] *= alpha;
     }
-    attn_pv_tile<NDT, LDVT>(Vhi, Vlo, li, h, &ph, &oacc);
+    attn_pv_tile<NDT, LDVT, 1, VSTK>(Vhi, Vlo, li, h, &ph, &oacc);
   } else {
     bf16x8 ph[4], pl[4];
     attn_softmax_tile_x3(sacc, m_run, l_run, ph, pl, alpha, grew);
@@ -234,15 +414,24 @@ struct AttnOut {
   int ld;
   int64_t rows;
 };
-template <int D, int NDT>
+// VSTK: the V^T lo rows were accumulated apart, NDT * 16 rows (= 6 register groups) below their hi rows: row dc + NDT * 16 is in the SAME lane,
+// register group g + 2 of tile n + 1 (g < 2) or g - 2 of tile n + 2.  It is added to the hi row before normalising.
+template <int D, int NDT, bool VSTK = false>
 __device__ __forceinline__ void attn_store_o(const AttnOut out, int64_t row, int col0, const f32x16 (&oacc)[NDT], float inv, int h) {
+  static_assert(!VSTK || (NDT == 3 && D % 8 == 0), "lo rows at +48 = one tile and two register groups further");
 #pragma unroll
   for (int n = 0; n < NDT; ++n) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {            // registers 4g..4g+3 are rows 32n + 8g + 4h + {0,1,2,3} of O^T = 4 consecutive channels
       const int dc = 32 * n + 8 * g + 4 * h;
       if (dc >= D) continue;
-      const float v0 = oacc[n][4 * g] * inv, v1 = oacc[n][4 * g + 1] * inv, v2 = oacc[n][4 * g + 2] * inv, v3 = oacc[n][4 * g + 3] * inv;
+      float v0 = oacc[n][4 * g], v1 = oacc[n][4 * g + 1], v2 = oacc[n][4 * g + 2], v3 = oacc[n][4 * g + 3];
+      if constexpr (VSTK) {
+        if (32 * n + 8 * g >= D) continue;   // the same test as above, decidable per unrolled iteration: no lo row is looked up past the tiles
+        const int n2 = g < 2 ? n + 1 : n + 2, g2 = g < 2 ? g + 2 : g - 2;
+        v0 += oacc[n2][4 * g2]; v1 += oacc[n2][4 * g2 + 1]; v2 += oacc[n2][4 * g2 + 2]; v3 += oacc[n2][4 * g2 + 3];
+      }
+      v0 *= inv; v1 *= inv; v2 *= inv; v3 *= inv;
       if (out.hi) {
         uint32_t h0, l0, h1, l1;
         split2(v0, v1, h0, l0);
@@ -261,20 +450,15 @@ __device__ __forceinline__ void attn_store_o(const AttnOut out, int64_t row, int
 // idle K / V LDS, leaving as 16-byte chunks, ~80 instead of 320 cache-line accesses per wave — produced the same values and the same step time:
 // 3.905 vs 3.906 images/s interleaved on one box, profiles/r05_first_call.log.  Deleted.)
 
-template <int D, int DKP, int DVP, bool F16P>     // head dim, padded to 16 (QK^T reduction) and to 32 (rows of O^T)
-__global__ void __launch_bounds__(256) attn_fwd_bf16_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k, int ldk,
+template <int D, int DKP, int DVP, bool F16P>     // head dim; K row width and V^T rows of the image (AttnImg)
+__global__ void __launch_bounds__(256, (attn_kstk(D, DKP) ? 3 : 1)) attn_fwd_bf16_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k, int ldk,
                                                             const float* __restrict__ v, int ldv, const AttnOut out,
                                                             float* __restrict__ lse, int heads, int Nq, int Nk, float scale_log2e, int qbat) {
-  constexpr int KT = 64;                  // keys per tile
-  constexpr int LDK = DKP + 8;            // bf16 per K row: (DKP+8)*2 bytes = odd multiple of 16 B -> conflict-free b128 rows
-  constexpr int LDVT = KT + 4;            // f16 per V^T row: 136 B -> 32 rows hit distinct even banks for ds_read_b64
-  constexpr int NKS = DKP / 16;           // k-steps of S^T
-  constexpr int NDT = DVP / 32;           // 32-row tiles of O^T
+  using I = AttnImg<D, DKP, DVP>;
+  constexpr int KT = I::KT, LDVT = I::LDVT, NDT = I::NDT;
   constexpr bool ONES = F16P && DVP > D;  // V^T row D = 1: the softmax denominator is row D of O^T
-  constexpr int K_BYTES = KT * LDK * 2, VT_BYTES = DVP * LDVT * 2;
-  __shared__ __attribute__((aligned(16))) char smem[2 * K_BYTES + 2 * VT_BYTES];
-  char* Khi = smem; char* Klo = smem + K_BYTES;
-  char* Vhi = smem + 2 * K_BYTES; char* Vlo = Vhi + VT_BYTES;
+  __shared__ __attribute__((aligned(16))) char smem[I::BYTES];
+  const char* Vhi = smem + I::KP; const char* Vlo = Vhi + I::VLO;
 
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int li = lane & 31, h = lane >> 5;
@@ -282,30 +466,9 @@ __global__ void __launch_bounds__(256) attn_fwd_bf16_kernel(const float* __restr
   const int q0 = blockIdx.x * 128 + wid * 32;
   const int qrow = min(q0 + li, Nq - 1);
 
-  // Q^T fragments (B operand): lane holds Q[q = li][dk = 16s + 8h .. +8], scaled, split
-  bf16x8 qh[NKS], ql[NKS];
-  {
-    const float* qp = q + ((int64_t)(b % qbat) * Nq + qrow) * ldq + hd * D;      // qbat: query batch period (= B unless the queries are shared)
-#pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-      uint32_t hi[4], lo[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int dk = 16 * s + 8 * h + 2 * e;
-        const float a = dk < D ? qp[dk] * scale_log2e : 0.f;
-        const float c = dk + 1 < D ? qp[dk + 1] * scale_log2e : 0.f;
-        split2(a, c, hi[e], lo[e]);
-      }
-      qh[s] = __builtin_bit_cast(bf16x8, make_uint4(hi[0], hi[1], hi[2], hi[3]));
-      ql[s] = __builtin_bit_cast(bf16x8, make_uint4(lo[0], lo[1], lo[2], lo[3]));
-    }
-  }
-  // zero the padding of both LDS images once (K columns D..DKP, V^T rows D..DVP are never written again), then the ones row of V^T hi
-  for (int i = t; i < (2 * K_BYTES + 2 * VT_BYTES) / 16; i += 256) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0u, 0u, 0u, 0u);
-  if constexpr (ONES) {
-    __syncthreads();
-    if (t < KT) reinterpret_cast<uint16_t*>(Vhi)[D * LDVT + t] = (uint16_t)ATTN_F16_ONE;
-  }
+  AttnQFrag<D, DKP> qf;
+  qf.load(q + ((int64_t)(b % qbat) * Nq + qrow) * ldq + hd * D, scale_log2e, h);      // qbat: query batch period (= B unless the queries are shared)
+  attn_image_init<I, D, ONES>(smem, t);
 
   f32x16 oacc[NDT];
 #pragma unroll
@@ -318,134 +481,53 @@ __global__ void __launch_bounds__(256) attn_fwd_bf16_kernel(const float* __restr
 
   for (int kt0 = 0; kt0 < Nk; kt0 += KT) {
     __syncthreads();
-    // stage K (row-major, bf16 hi / lo) and V (transposed, f16 hi / lo)
-    for (int i = t; i < KT * (D / 4); i += 256) {
-      const int key = i / (D / 4), c4 = i - key * (D / 4);
-      float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
-      if (kt0 + key < Nk) {
-        kv = *reinterpret_cast<const float4*>(kb + (int64_t)(kt0 + key) * ldk + c4 * 4);
-        vv = *reinterpret_cast<const float4*>(vb + (int64_t)(kt0 + key) * ldv + c4 * 4);
-      }
-      uint32_t h0, l0, h1, l1;
-      split2(kv.x, kv.y, h0, l0);
-      split2(kv.z, kv.w, h1, l1);
-      *reinterpret_cast<uint2*>(Khi + (key * LDK + c4 * 4) * 2) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(Klo + (key * LDK + c4 * 4) * 2) = make_uint2(l0, l1);
-      if (F16P) { split2h(vv.x, vv.y, h0, l0); split2h(vv.z, vv.w, h1, l1); }
-      else { split2(vv.x, vv.y, h0, l0); split2(vv.z, vv.w, h1, l1); }
-      uint16_t* vh = reinterpret_cast<uint16_t*>(Vhi);
-      uint16_t* vl = reinterpret_cast<uint16_t*>(Vlo);
-      const int d0 = c4 * 4;
-      vh[(d0 + 0) * LDVT + key] = (uint16_t)(h0 & 0xFFFFu); vh[(d0 + 1) * LDVT + key] = (uint16_t)(h0 >> 16);
-      vh[(d0 + 2) * LDVT + key] = (uint16_t)(h1 & 0xFFFFu); vh[(d0 + 3) * LDVT + key] = (uint16_t)(h1 >> 16);
-      vl[(d0 + 0) * LDVT + key] = (uint16_t)(l0 & 0xFFFFu); vl[(d0 + 1) * LDVT + key] = (uint16_t)(l0 >> 16);
-      vl[(d0 + 2) * LDVT + key] = (uint16_t)(l1 & 0xFFFFu); vl[(d0 + 3) * LDVT + key] = (uint16_t)(l1 >> 16);
-    }
+    attn_stage_tile<I, D, F16P>(smem, kb, ldk, vb, ldv, kt0, Nk, t);
     __syncthreads();
-
-    // ---- S^T = K Q^T for the two 32-key sub-tiles
     f32x16 sacc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[j][r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int off = ((j * 32 + li) * LDK + 16 * s + 8 * h) * 2;
-        const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Khi + off);
-        const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Klo + off);
-        sacc[j] = MFMA32(kl, qh[s], sacc[j]);
-        sacc[j] = MFMA32(kh, ql[s], sacc[j]);
-        sacc[j] = MFMA32(kh, qh[s], sacc[j]);
-      }
-    }
-    // ---- online softmax: query = lane column; this lane holds keys 32j + (r&3) + 8(r>>2) + 4h
-    if (kt0 + KT > Nk) {                   // only the last tile can hold padded keys (uniform branch)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kt0 + 32 * j + (r & 3) + 8 * (r >> 2) + 4 * h >= Nk) sacc[j][r] = -INFINITY;
-    }
+    attn_scores_tile<D, DKP, DVP>(smem, li, h, qf, sacc);
+    attn_mask_tail(sacc, kt0, Nk, h);
     // ---- online softmax + O^T += V^T P^T ; A fragment of step u: V^T[d = 32n + li][16u + 4h + {0..3, 8..11}]
-    attn_tile_tail<F16P, ONES, NDT, LDVT>(sacc, m_run, l_run, oacc, Vhi, Vlo, li, h);
+    attn_tile_tail<F16P, ONES, NDT, LDVT, I::VSTK>(sacc, m_run, l_run, oacc, Vhi, Vlo, li, h);
   }
 
   const float l_tot = attn_row_sum<D, NDT, ONES>(oacc, l_run, li);
   const float inv = 1.0f / l_tot;
   if (lse && h == 0 && q0 + li < Nq) lse[(int64_t)bh * Nq + q0 + li] = m_run + log2f(l_tot) - (F16P ? ATTN_P_SHIFT : 0.f);
-  if (q0 + li < Nq) attn_store_o<D, NDT>(out, (int64_t)b * Nq + q0 + li, hd * D, oacc, inv, h);
+  if (q0 + li < Nq) attn_store_o<D, NDT, I::VSTK>(out, (int64_t)b * Nq + q0 + li, hd * D, oacc, inv, h);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Long key sequences (self-attention at 64x64 / 32x32 latents): every 128-query workgroup of the kernel above re-splits
 // and re-transposes the same K / V tiles.  Here a pre-pass does that ONCE per (batch, head): it writes, per 64-key tile,
-// the exact LDS image [K hi | K lo | V^T hi | V^T lo] (padded pitches, zero padding included) to a workspace, and the
+// the exact LDS image [K part | V^T part] (AttnImg: padded pitches, zero padding and the ones row included) to a workspace, and the
 // attention kernel streams images with 16-byte loads one tile ahead of the MFMAs (registers -> ds_write_b128): no
 // conversion, no 2-byte transpose scatter and no exposed global-load latency in the key loop.
 // ------------------------------------------------------------------------------------------------
-template <int D, int DKP, int DVP>
-struct AttnImg {
-  static constexpr int KT = 64, LDK = DKP + 8, LDVT = KT + 4;
-  static constexpr int K_BYTES = KT * LDK * 2, VT_BYTES = DVP * LDVT * 2;
-  static constexpr int BYTES = 2 * K_BYTES + 2 * VT_BYTES;       // multiple of 16
-  static constexpr int CHUNKS = BYTES / 16;
-};
-
 template <int D, int DKP, int DVP, bool F16P>
 __global__ void __launch_bounds__(256) attn_pack_kv_kernel(const float* __restrict__ k, int ldk, const float* __restrict__ v, int ldv,
                                                            uint4* __restrict__ img, int heads, int Nk, int ntiles) {
   using I = AttnImg<D, DKP, DVP>;
   __shared__ __attribute__((aligned(16))) char smem[I::BYTES];
-  char* Khi = smem; char* Klo = smem + I::K_BYTES;
-  char* Vhi = smem + 2 * I::K_BYTES; char* Vlo = Vhi + I::VT_BYTES;
   const int t = threadIdx.x;
   const int tile = blockIdx.x, bh = blockIdx.y, b = bh / heads, hd = bh - b * heads;
-  const int kt0 = tile * I::KT;
-  for (int i = t; i < I::CHUNKS; i += 256) reinterpret_cast<uint4*>(smem)[i] = make_uint4(0u, 0u, 0u, 0u);
+  attn_image_init<I, D, (F16P && DVP > D)>(smem, t);
   __syncthreads();
-  if (F16P && DVP > D && t < I::KT) reinterpret_cast<uint16_t*>(Vhi)[D * I::LDVT + t] = (uint16_t)ATTN_F16_ONE;      // the ones row (softmax denominator)
-  const float* kb = k + (int64_t)b * Nk * ldk + hd * D;
-  const float* vb = v + (int64_t)b * Nk * ldv + hd * D;
-  for (int i = t; i < I::KT * (D / 4); i += 256) {
-    const int key = i / (D / 4), c4 = i - key * (D / 4);
-    if (kt0 + key >= Nk) continue;
-    const float4 kv = *reinterpret_cast<const float4*>(kb + (int64_t)(kt0 + key) * ldk + c4 * 4);
-    const float4 vv = *reinterpret_cast<const float4*>(vb + (int64_t)(kt0 + key) * ldv + c4 * 4);
-    uint32_t h0, l0, h1, l1;
-    split2(kv.x, kv.y, h0, l0);
-    split2(kv.z, kv.w, h1, l1);
-    *reinterpret_cast<uint2*>(Khi + (key * I::LDK + c4 * 4) * 2) = make_uint2(h0, h1);
-    *reinterpret_cast<uint2*>(Klo + (key * I::LDK + c4 * 4) * 2) = make_uint2(l0, l1);
-    if (F16P) { split2h(vv.x, vv.y, h0, l0); split2h(vv.z, vv.w, h1, l1); }
-    else { split2(vv.x, vv.y, h0, l0); split2(vv.z, vv.w, h1, l1); }
-    uint16_t* vh = reinterpret_cast<uint16_t*>(Vhi);
-    uint16_t* vl = reinterpret_cast<uint16_t*>(Vlo);
-    const int d0 = c4 * 4;
-    vh[(d0 + 0) * I::LDVT + key] = (uint16_t)(h0 & 0xFFFFu); vh[(d0 + 1) * I::LDVT + key] = (uint16_t)(h0 >> 16);
-    vh[(d0 + 2) * I::LDVT + key] = (uint16_t)(h1 & 0xFFFFu); vh[(d0 + 3) * I::LDVT + key] = (uint16_t)(h1 >> 16);
-    vl[(d0 + 0) * I::LDVT + key] = (uint16_t)(l0 & 0xFFFFu); vl[(d0 + 1) * I::LDVT + key] = (uint16_t)(l0 >> 16);
-    vl[(d0 + 2) * I::LDVT + key] = (uint16_t)(l1 & 0xFFFFu); vl[(d0 + 3) * I::LDVT + key] = (uint16_t)(l1 >> 16);
-  }
+  attn_stage_tile<I, D, F16P>(smem, k + (int64_t)b * Nk * ldk + hd * D, ldk, v + (int64_t)b * Nk * ldv + hd * D, ldv, tile * I::KT, Nk, t);
   __syncthreads();
   uint4* dst = img + ((int64_t)bh * ntiles + tile) * I::CHUNKS;
   for (int i = t; i < I::CHUNKS; i += 256) dst[i] = reinterpret_cast<const uint4*>(smem)[i];
 }
 
 template <int D, int DKP, int DVP, bool F16P>
-__global__ void __launch_bounds__(256, (DVP <= 32 ? 4 : (DKP <= 48 ? 3 : 2))) attn_fwd_bf16_pk_kernel(const float* __restrict__ q, int ldq, const uint4* __restrict__ img,
+__global__ void __launch_bounds__(256, (DVP <= 32 ? 4 : (DKP <= 48 || attn_kstk(D, DKP) ? 3 : 2))) attn_fwd_bf16_pk_kernel(const float* __restrict__ q, int ldq, const uint4* __restrict__ img,
                                                                const AttnOut out, float* __restrict__ lse, int heads,
                                                                int Nq, int Nk, int ntiles, float scale_log2e, int qbat) {
   using I = AttnImg<D, DKP, DVP>;
-  constexpr int KT = I::KT, LDK = I::LDK, LDVT = I::LDVT;
-  constexpr int NKS = DKP / 16, NDT = DVP / 32;
+  constexpr int KT = I::KT, LDVT = I::LDVT, NDT = I::NDT;
   constexpr bool ONES = F16P && DVP > D;
   constexpr int NCH = (I::CHUNKS + 255) / 256;
   __shared__ __attribute__((aligned(16))) char smem[I::BYTES];
-  const char* Khi = smem; const char* Klo = smem + I::K_BYTES;
-  const char* Vhi = smem + 2 * I::K_BYTES; const char* Vlo = Vhi + I::VT_BYTES;
+  const char* Vhi = smem + I::KP; const char* Vlo = Vhi + I::VLO;
 
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int li = lane & 31, h = lane >> 5;
@@ -453,23 +535,8 @@ __global__ void __launch_bounds__(256, (DVP <= 32 ? 4 : (DKP <= 48 ? 3 : 2))) at
   const int q0 = blockIdx.x * 128 + wid * 32;
   const int qrow = min(q0 + li, Nq - 1);
 
-  bf16x8 qh[NKS], ql[NKS];
-  {
-    const float* qp = q + ((int64_t)(b % qbat) * Nq + qrow) * ldq + hd * D;      // qbat: query batch period (= B unless the queries are shared)
-#pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-      uint32_t hi[4], lo[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int dk = 16 * s + 8 * h + 2 * e;
-        const float a = dk < D ? qp[dk] * scale_log2e : 0.f;
-        const float c = dk + 1 < D ? qp[dk + 1] * scale_log2e : 0.f;
-        split2(a, c, hi[e], lo[e]);
-      }
-      qh[s] = __builtin_bit_cast(bf16x8, make_uint4(hi[0], hi[1], hi[2], hi[3]));
-      ql[s] = __builtin_bit_cast(bf16x8, make_uint4(lo[0], lo[1], lo[2], lo[3]));
-    }
-  }
+  AttnQFrag<D, DKP> qf;
+  qf.load(q + ((int64_t)(b % qbat) * Nq + qrow) * ldq + hd * D, scale_log2e, h);      // qbat: query batch period (= B unless the queries are shared)
 
   f32x16 oacc[NDT];
 #pragma unroll
@@ -505,36 +572,15 @@ __global__ void __launch_bounds__(256, (DVP <= 32 ? 4 : (DKP <= 48 ? 3 : 2))) at
     }
 
     f32x16 sacc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[j][r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int off = ((j * 32 + li) * LDK + 16 * s + 8 * h) * 2;
-        const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Khi + off);
-        const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Klo + off);
-        sacc[j] = MFMA32(kl, qh[s], sacc[j]);
-        sacc[j] = MFMA32(kh, ql[s], sacc[j]);
-        sacc[j] = MFMA32(kh, qh[s], sacc[j]);
-      }
-    }
-    if (kt0 + KT > Nk) {                   // only the last tile can hold padded keys (uniform branch)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kt0 + 32 * j + (r & 3) + 8 * (r >> 2) + 4 * h >= Nk) sacc[j][r] = -INFINITY;
-    }
-    attn_tile_tail<F16P, ONES, NDT, LDVT>(sacc, m_run, l_run, oacc, Vhi, Vlo, li, h);
+    attn_scores_tile<D, DKP, DVP>(smem, li, h, qf, sacc);
+    attn_mask_tail(sacc, kt0, Nk, h);
+    attn_tile_tail<F16P, ONES, NDT, LDVT, I::VSTK>(sacc, m_run, l_run, oacc, Vhi, Vlo, li, h);
   }
 
   const float l_tot = attn_row_sum<D, NDT, ONES>(oacc, l_run, li);
   const float inv = 1.0f / l_tot;
   if (lse && h == 0 && q0 + li < Nq) lse[(int64_t)bh * Nq + q0 + li] = m_run + log2f(l_tot) - (F16P ? ATTN_P_SHIFT : 0.f);
-  if (q0 + li < Nq) attn_store_o<D, NDT>(out, (int64_t)b * Nq + q0 + li, hd * D, oacc, inv, h);
+  if (q0 + li < Nq) attn_store_o<D, NDT, I::VSTK>(out, (int64_t)b * Nq + q0 + li, hd * D, oacc, inv, h);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -557,14 +603,13 @@ typedef unsigned int u32x4_a __attribute__((ext_vector_type(4)));
 // blocks and half as many workgroups stream the images; the score + softmax phases run one block after the other (their K fragments
 // are re-read: both blocks' score accumulators at once do not fit two waves per SIMD).  Per-query arithmetic and order unchanged.
 template <int D, int DKP, int DVP, int QB, bool F16P>
-__global__ void __launch_bounds__(256, (QB == 2 ? 2 : (DVP <= 32 ? 4 : (DKP <= 48 ? 3 : 2)))) attn_fwd_bf16_dma_kernel(const float* __restrict__ q, int ldq, const uint4* __restrict__ img,
+__global__ void __launch_bounds__(256, (QB == 2 ? 2 : (DVP <= 32 ? 4 : (DKP <= 48 || attn_kstk(D, DKP) ? 3 : 2)))) attn_fwd_bf16_dma_kernel(const float* __restrict__ q, int ldq, const uint4* __restrict__ img,
                                                                const AttnOut out, float* __restrict__ lse, int heads,
                                                                int Nq, int Nk, int ntiles, float scale_log2e, int qbat) {
   using I = AttnImg<D, DKP, DVP>;
-  constexpr int KT = I::KT, LDK = I::LDK, LDVT = I::LDVT;
-  constexpr int NKS = DKP / 16, NDT = DVP / 32;
+  constexpr int KT = I::KT, LDVT = I::LDVT, NDT = I::NDT;
   constexpr bool ONES = F16P && DVP > D;
-  constexpr int KP = 2 * I::K_BYTES, VP = 2 * I::VT_BYTES;          // K part (hi | lo) and V^T part (hi | lo) of an image
+  constexpr int KP = I::KP, VP = I::VP;                             // K part and V^T part of an image
   static_assert(KP % 1024 == 0 && VP % 1024 == 0, "LDS-DMA moves whole KiB pieces");
   constexpr int NPK = KP / 1024, NPV = VP / 1024;
   __shared__ __attribute__((aligned(1024))) char smem[2 * KP + VP];  // [K region 0 | K region 1 | V region]
@@ -575,24 +620,11 @@ __global__ void __launch_bounds__(256, (QB == 2 ? 2 : (DVP <= 32 ? 4 : (DKP <= 4
   const int bh = blockIdx.y, b = bh / heads, hd = bh - b * heads;
   const int q0 = blockIdx.x * (128 * QB) + wid * (32 * QB);          // this wave's queries: q0 + 32 * qb + li
 
-  bf16x8 qh[QB][NKS], ql[QB][NKS];
+  AttnQFrag<D, DKP> qf[QB];
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
     const int qrow = min(q0 + 32 * qb + li, Nq - 1);
-    const float* qp = q + ((int64_t)(b % qbat) * Nq + qrow) * ldq + hd * D;      // qbat: query batch period (= B unless the queries are shared)
-#pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-      uint32_t hi[4], lo[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int dk = 16 * s + 8 * h + 2 * e;
-        const float a = dk < D ? qp[dk] * scale_log2e : 0.f;
-        const float c = dk + 1 < D ? qp[dk + 1] * scale_log2e : 0.f;
-        split2(a, c, hi[e], lo[e]);
-      }
-      qh[qb][s] = __builtin_bit_cast(bf16x8, make_uint4(hi[0], hi[1], hi[2], hi[3]));
-      ql[qb][s] = __builtin_bit_cast(bf16x8, make_uint4(lo[0], lo[1], lo[2], lo[3]));
-    }
+    qf[qb].load(q + ((int64_t)(b % qbat) * Nq + qrow) * ldq + hd * D, scale_log2e, h);      // qbat: query batch period (= B unless the queries are shared)
   }
 
   f32x16 oacc[QB][NDT];
@@ -622,8 +654,7 @@ __global__ void __launch_bounds__(256, (QB == 2 ? 2 : (DVP <= 32 ? 4 : (DKP <= 4
   for (int tile = 0; tile < ntiles; ++tile) {
     const int kt0 = tile * KT;
     const uint32_t kreg = (tile & 1) ? KP : 0;
-    const char* Khi = smem + kreg; const char* Klo = Khi + I::K_BYTES;
-    const char* Vhi = smem + 2 * KP; const char* Vlo = Vhi + I::VT_BYTES;
+    const char* Vhi = smem + 2 * KP; const char* Vlo = Vhi + I::VLO;
     // K(tile) has landed (requested a whole tile ago) and my P V reads of the previous tile have returned
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -635,29 +666,8 @@ __global__ void __launch_bounds__(256, (QB == 2 ? 2 : (DVP <= 32 ? 4 : (DKP <= 4
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
       f32x16 sacc[2];
-  #pragma unroll
-      for (int j = 0; j < 2; ++j)
-  #pragma unroll
-        for (int r = 0; r < 16; ++r) sacc[j][r] = 0.f;
-  #pragma unroll
-      for (int s = 0; s < NKS; ++s) {
-  #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int off = ((j * 32 + li) * LDK + 16 * s + 8 * h) * 2;
-          const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Khi + off);
-          const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Klo + off);
-          sacc[j] = MFMA32(kl, qh[qb][s], sacc[j]);
-          sacc[j] = MFMA32(kh, ql[qb][s], sacc[j]);
-          sacc[j] = MFMA32(kh, qh[qb][s], sacc[j]);
-        }
-      }
-      if (kt0 + KT > Nk) {                   // only the last tile can hold padded keys (uniform branch)
-  #pragma unroll
-        for (int j = 0; j < 2; ++j)
-  #pragma unroll
-          for (int r = 0; r < 16; ++r)
-            if (kt0 + 32 * j + (r & 3) + 8 * (r >> 2) + 4 * h >= Nk) sacc[j][r] = -INFINITY;
-      }
+      attn_scores_tile<D, DKP, DVP>(smem + kreg, li, h, qf[qb], sacc);
+      attn_mask_tail(sacc, kt0, Nk, h);
       float alpha;
       bool grew;
       if constexpr (F16P) attn_softmax_tile<ONES>(sacc, m_run[qb], l_run[qb], ph[qb], alpha, grew);
@@ -672,7 +682,7 @@ __global__ void __launch_bounds__(256, (QB == 2 ? 2 : (DVP <= 32 ? 4 : (DKP <= 4
     // V(tile) (and K(tile + 1)) have landed; my K fragment reads have returned
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if constexpr (F16P) attn_pv_tile<NDT, LDVT, QB>(Vhi, Vlo, li, h, ph, oacc);      // one V^T fragment feeds QB query blocks
+    if constexpr (F16P) attn_pv_tile<NDT, LDVT, QB, I::VSTK>(Vhi, Vlo, li, h, ph, oacc);      // one V^T fragment feeds QB query blocks
     else attn_pv_tile_x3<NDT, LDVT, QB>(Vhi, Vlo, li, h, xh, xl, oacc);
   }
 
@@ -682,7 +692,7 @@ __global__ void __launch_bounds__(256, (QB == 2 ? 2 : (DVP <= 32 ? 4 : (DKP <= 4
     const float l_tot = attn_row_sum<D, NDT, ONES>(oacc[qb], l_run[qb], li);
     const float inv = 1.0f / l_tot;
     if (lse && h == 0 && qi < Nq) lse[(int64_t)bh * Nq + qi] = m_run[qb] + log2f(l_tot) - (F16P ? ATTN_P_SHIFT : 0.f);
-    if (qi < Nq) attn_store_o<D, NDT>(out, (int64_t)b * Nq + qi, hd * D, oacc[qb], inv, h);
+    if (qi < Nq) attn_store_o<D, NDT, I::VSTK>(out, (int64_t)b * Nq + qi, hd * D, oacc[qb], inv, h);
   }
 }
 
@@ -707,7 +717,7 @@ static int launch_attn_images(const float* q, int ldq, int qbat, const uint4* im
   // LDS-DMA image streaming wherever the image's K and V^T parts are whole KiB (d = 40, 64): 1.50 -> 1.42 ms on 4096^2, d = 40, batch 16
   // (profiles/r02_probe_attn_dma.log; 1.29 ms with the f16p second product, profiles/r04_probe_attn.log); the register-staged kernel below
   // takes the other head sizes (d = 80) and >= 2 GiB image sets.  (Two query blocks per wave on top measured 1.40 ms at 256 VGPRs with spills — not kept.)
-  if constexpr ((2 * I::K_BYTES) % 1024 == 0 && (2 * I::VT_BYTES) % 1024 == 0) {
+  if constexpr (I::KP % 1024 == 0 && I::VP % 1024 == 0) {
     if ((int64_t)ntiles * I::BYTES < 0x7FFFFFFF) {
       // (measured and not kept, round 4: two query blocks per wave, s_setprio around the MFMA phases, and a software-pipelined one-barrier loop
       // with K and V^T double-buffered — 1.23 / 1.23 / 1.31 ms against 1.22: profiles/r04_probe_attn_qb2_prio.log)
@@ -758,18 +768,29 @@ extern "C" size_t ddpo_attention_fwd_bf16x3_ws_bytes(int B, int heads, int Nk, i
   switch (d) {
     case 8:  return attn_ws<8, 16, 32>(B, heads, Nk);
     case 16: return attn_ws<16, 16, 32>(B, heads, Nk);
-    case 40: return attn_ws<40, 48, 64>(B, heads, Nk);
+    case 40: return attn_ws<40, 48, 64>(B, heads, Nk);      // the plain layout's size: enough for the smaller stacked images of either variant
     case 64: return attn_ws<64, 64, 64>(B, heads, Nk);
     case 80: return attn_ws<80, 80, 96>(B, heads, Nk);
     default: return 0;
   }
 }
 
+// DDPO_ATTN_STACK=0: d = 40 on the plain hi / lo planes (the round-8 kernels) — the interleaved A/B and the tests' comparison.  Read ONCE per
+// process: images packed under one setting are garbage under the other, so it must not change between a pack and its attention.
+static bool attn_stack() {
+  static const bool on = [] {
+    const char* e = getenv("DDPO_ATTN_STACK");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
+// F16P: the enclosing function's variant (the stacked d = 40 image has 96 V^T rows in the f16p packing, the two 64-row planes in bf16x3)
 #define ATTN_BY_D(CALL)                                      \
   switch (d) {                                               \
     case 8:  return CALL(8, 16, 32);                         \
     case 16: return CALL(16, 16, 32);                        \
-    case 40: return CALL(40, 48, 64);                        \
+    case 40: return attn_stack() ? CALL(40, 80, (F16P ? 96 : 64)) : CALL(40, 48, 64); /* stacked (header comment) | DDPO_ATTN_STACK=0 */ \
     case 64: return CALL(64, 64, 64);                        \
     case 80: return CALL(80, 80, 96);                        \
     default: return DDPO_EINVAL; /* other head dims stay on the exact-fp32 kernel */ \
@@ -828,7 +849,8 @@ extern "C" int ddpo_attention_fwd_f16p_po(const float* q, int ldq, const float* 
 
 /* K / V of a (batch, head) set packed ONCE into the per-64-key-tile LDS images the attention kernels stream (any Nk), for callers whose
  * keys / values are constant over many attention calls — the text context of the cross-attention layers over the 50 DDIM steps of a
- * sampling call.  ddpo_attention_kv_images_bytes gives the image size (the same for both variants); ddpo_attention_fwd_{bf16x3,f16p}_images runs
+ * sampling call.  ddpo_attention_kv_images_bytes gives a buffer size that holds either variant's images (d = 40: the plain layout's, which the
+ * stacked images of both variants fit into); ddpo_attention_fwd_{bf16x3,f16p}_images runs
  * the attention from the images of ITS variant's pack function (same kernels as the workspace form: identical results). */
 extern "C" size_t ddpo_attention_kv_images_bytes(int B, int heads, int Nk, int d) {
   if (B <= 0 || heads <= 0 || Nk <= 0) return 0;
