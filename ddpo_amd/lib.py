@@ -1612,6 +1612,21 @@ def cosine_rows(a, b, scale=1.0, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ rewards on device images
+def _cuda_images(who, images, any_dtype=False):
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or not (any_dtype or images.dtype in (torch.float32, torch.uint8)):
+        raise DdpoHipError(f"{who} needs a float32 or uint8 CUDA tensor")
+
+
+def _workspace_or_scratch(who, workspace, nbytes, device, tag):
+    """`workspace` checked — uint8, at least `nbytes`, on `device` — or, when None, this stream's scratch for `tag`"""
+    if workspace is None:
+        workspace = _scratch(nbytes, device, tag)
+    if workspace.dtype != torch.uint8 or workspace.numel() < nbytes or workspace.device != device:
+        raise DdpoHipError(f"{who}: the workspace must be a uint8 tensor of >= {nbytes} bytes on {device}")
+    return workspace
+
+
 # ------------------------------------------------------------------------------------------------ JPEG file size
 JPEG_FIXED_BYTES = 625        # DDPO_JPEG_FIXED_BYTES of include/ddpo_hip.h: the bytes of a file that are not entropy-coded data
 JPEG_SIZE_RULE = "height and width must be multiples of 16 (the 4:2:0 MCU): edge replication and dummy blocks are not built"
@@ -1641,14 +1656,10 @@ def jpeg_size(images, quality=95, workspace=None, out=None):
     """len(PIL JPEG bytes at `quality`) of every image of an N x H x W x 3 CUDA tensor — uint8, or float32 in [0, 1] truncated as
     (x * 255).astype(uint8) — as an int64 CUDA tensor, on the current stream; no file is produced (ddpo_jpeg_size).  H and W must be multiples of 16
     (ValueError).  `workspace`: a uint8 CUDA tensor of at least jpeg_size_workspace_bytes(N, H, W) bytes; default: this stream's scratch."""
-    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype not in (torch.float32, torch.uint8):
-        raise DdpoHipError("jpeg_size needs a float32 or uint8 CUDA tensor")
+    _cuda_images("jpeg_size", images)
     n, h, w, quality = _jpeg_size_args(images.shape, quality)
     nb = jpeg_size_workspace_bytes(n, h, w)
-    if workspace is None:
-        workspace = _scratch(nb, images.device, "jpeg_size")
-    if workspace.dtype != torch.uint8 or workspace.numel() < nb or workspace.device != images.device:
-        raise DdpoHipError(f"jpeg_size: the workspace must be a uint8 tensor of >= {nb} bytes on {images.device}")
+    workspace = _workspace_or_scratch("jpeg_size", workspace, nb, images.device, "jpeg_size")
     if out is None:
         out = torch.empty(n, dtype=torch.int64, device=images.device)
     _check(load().ddpo_jpeg_size(_p(images), int(images.dtype == torch.float32), n, h, w, quality, _p(workspace), workspace.numel(), _p(out),
@@ -1696,8 +1707,7 @@ def jpeg_encode(images, quality=80, workspace=None, files=None, stride=None):
     whose row n starts with file n, and the int64 CUDA lengths, equal to jpeg_size's.  A file longer than `stride` (default H * W * 3 + 625;
     jpeg_encode_max_bytes(H, W) is never exceeded) leaves its first `stride` bytes and still reports its full length; bytes of a row past the
     file are not written.  `files`: a contiguous uint8 CUDA tensor (N, stride) to write into.  `workspace`: as for jpeg_size."""
-    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype not in (torch.float32, torch.uint8):
-        raise DdpoHipError("jpeg_encode needs a float32 or uint8 CUDA tensor")
+    _cuda_images("jpeg_encode", images)
     n, h, w, quality = _jpeg_encode_args(images.shape, quality)
     if stride is None:
         stride = int(files.shape[1]) if files is not None and files.dim() == 2 else h * w * 3 + JPEG_FIXED_BYTES
@@ -1705,10 +1715,7 @@ def jpeg_encode(images, quality=80, workspace=None, files=None, stride=None):
         raise ValueError(f"jpeg_encode: the row stride must be an integer >= {JPEG_FIXED_BYTES}, got {stride!r}")
     stride = int(stride)
     nb = jpeg_size_workspace_bytes(n, h, w)
-    if workspace is None:
-        workspace = _scratch(nb, images.device, "jpeg_size")
-    if workspace.dtype != torch.uint8 or workspace.numel() < nb or workspace.device != images.device:
-        raise DdpoHipError(f"jpeg_encode: the workspace must be a uint8 tensor of >= {nb} bytes on {images.device}")
+    workspace = _workspace_or_scratch("jpeg_encode", workspace, nb, images.device, "jpeg_size")
     if files is None:
         files = torch.empty((n, stride), dtype=torch.uint8, device=images.device)
     if files.dtype != torch.uint8 or tuple(files.shape) != (n, stride) or not files.is_contiguous() or files.device != images.device:
@@ -1861,8 +1868,7 @@ def clip_preprocess(images, size, patch, k_pad, out=None):
     N x H x W x 3 CUDA tensor — float32 in [0, 1], truncated as (x * 255).astype(uint8), or uint8 — to the (N * g * g, k_pad) float32 patch
     matrix, g = size // patch, rows (n, gy, gx), columns (c, ky, kx), pad columns zero.  Equal bit for bit to the host path (Pillow's bicubic
     resize of the short side to `size`, centre crop, CLIP normalisation).  ValueError names the broken rule (CLIP_PREPROCESS_RULE for LDS)."""
-    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype not in (torch.float32, torch.uint8):
-        raise DdpoHipError("clip_preprocess needs a float32 or uint8 CUDA tensor")
+    _cuda_images("clip_preprocess", images)
     n, h, w = _clip_images_shape(images.shape)
     geo = clip_preprocess_geometry(h, w, size, patch, k_pad)
     g = size // patch
@@ -1946,15 +1952,11 @@ def symmetry_stats(images, mode, workspace=None, out=None):
     (y, W-1-x, c), "rot180": (H-1-y, W-1-x, c) —: [0] sum of ((a - b) mod 256)^2 mod 256 (what numpy's uint8 arithmetic makes of (a - b) ** 2),
     [1] sum of a, [2] sum of a^2, [3] sum of a b.  `workspace`: a uint8 CUDA tensor of at least symmetry_stats_workspace_bytes(N, H, W, mode)
     bytes; default: this stream's scratch.  ValueError names the broken rule."""
-    if not isinstance(images, torch.Tensor) or not images.is_cuda:
-        raise DdpoHipError("symmetry_stats needs a CUDA tensor")
+    _cuda_images("symmetry_stats", images, any_dtype=True)          # _symmetry_images names the dtype rule
     m = _symmetry_mode(mode)
     n, h, w = _symmetry_images("symmetry_stats", images, True)
     nb = symmetry_stats_workspace_bytes(n, h, w, mode)
-    if workspace is None:
-        workspace = _scratch(nb, images.device, "symmetry_stats")
-    if workspace.dtype != torch.uint8 or workspace.numel() < nb or workspace.device != images.device:
-        raise DdpoHipError(f"symmetry_stats: the workspace must be a uint8 tensor of >= {nb} bytes on {images.device}")
+    workspace = _workspace_or_scratch("symmetry_stats", workspace, nb, images.device, "symmetry_stats")
     if out is None:
         out = torch.empty((n, 4), dtype=torch.int64, device=images.device)
     if out.dtype != torch.int64 or tuple(out.shape) != (n, 4) or not out.is_contiguous() or out.device != images.device:
@@ -1983,8 +1985,7 @@ def rotate4_u8(images, out=None):
     """The four right-angle turns of a square N x S x S x 3 CUDA batch — uint8, or float32 in [0, 1] truncated as (x * 255).astype(uint8) — as
     one uint8 CUDA tensor (4N, S, S, 3), on the current stream (ddpo_rotate4_u8): block k N + n is PIL.Image.rotate(90 k) of image n, k = 0..3.
     ValueError names the broken rule."""
-    if not isinstance(images, torch.Tensor) or not images.is_cuda:
-        raise DdpoHipError("rotate4_u8 needs a CUDA tensor")
+    _cuda_images("rotate4_u8", images, any_dtype=True)          # _symmetry_images names the dtype rule
     n, s, _ = _symmetry_images("rotate4_u8", images, True, square=True)
     if out is None:
         out = torch.empty((4 * n, s, s, 3), dtype=torch.uint8, device=images.device)

@@ -2,10 +2,9 @@
 transformers' `CLIPModel(...).logits_per_image`.  Image side: models/clip_vision.py (the tower of the aesthetic reward).  Text side:
 models/clip_text.py.  Cosine: `ddpo_cosine_rows` (one launch instead of two normalisations and a batched dot product).
 
-Like the aesthetic scorer it runs on a private HIP stream: the reward callback is evaluated by a worker thread while the main thread samples
-the next batch, and the two must not share a stream or scratch space.
+A `DeviceScorer` (models/device_scorer.py) like the aesthetic scorer: it runs on a private HIP stream.
 
-Weights: the ONE checkpoint the aesthetic reward already uses, looked up the same way (`laion.find_weights`): `<weights_dir>/clip/` with
+Weights: the ONE checkpoint the aesthetic reward already uses, looked up the same way (`laion.load_clip_checkpoint`): `<weights_dir>/clip/` with
 `weights_dir` = the argument, else $DDPO_AESTHETIC_WEIGHTS, then an HF cache snapshot of `openai/clip-vit-large-patch14`.  It carries both
 towers, `text_projection` and `logit_scale`.  The tokenizer is transformers' `CLIPTokenizer` read from the same directory (`vocab.json` +
 `merges.txt`).  Missing weights — or real weights without their vocabulary — raise before any GPU work, unless DDPO_ALLOW_SYNTHETIC=1 asks for
@@ -30,10 +29,10 @@ import torch
 
 from .. import lib as L
 from .clip_text import ClipTextTower, TextConfig, synthetic_text_state
-from .clip_vision import ClipVisionTower, VisionConfig, device_images, preprocess
-from .laion import REPO_ROOT, _load_clip_state, find_weights, synthetic_state_dicts
+from .clip_vision import ClipVisionTower, VisionConfig, preprocess
+from .device_scorer import DeviceScorer, device_images
+from .laion import load_clip_checkpoint
 
-CHECKPOINT = "openai/clip-vit-large-patch14"
 TEXT_CHUNK = 8            # prompts per text-tower launch sequence (616 rows)
 IMAGE_CHUNK = 4           # images per image-tower launch sequence (1028 rows at ViT-L/14)
 SYNTHETIC_LOGIT_SCALE = math.log(1 / 0.07)      # CLIP's initial value; the trained checkpoint holds ln(100)
@@ -81,37 +80,25 @@ def load_clip_tokenizer(clip_dir):
     return CLIPTokenizer.from_pretrained(clip_dir)
 
 
-class ClipScorer:
+class ClipScorer(DeviceScorer):
     def __init__(self, weights_dir=None, cache="cache", seed=0, device="cuda", config="vit-l/14", clip_state=None, tokenizer=None,
                  logit_scale=None, cache_size=4096):
         """`clip_state` (+ optionally `tokenizer`, `logit_scale`): a state dict handed in directly (tests); otherwise files are looked up (see
         the module docstring).  `logit_scale` overrides the checkpoint's (the log of the factor, as the checkpoint stores it)."""
-        self.device = torch.device(device)
         self.vcfg, self.tcfg = VisionConfig.named(config), TextConfig.named(config)
         if self.vcfg.proj != self.tcfg.proj:
             raise ValueError(f"image and text projections differ: {self.vcfg.proj} vs {self.tcfg.proj}")
         self.synthetic = False
         if clip_state is None:
-            clip_dir, _ = find_weights(weights_dir, cache)
-            clip_state = _load_clip_state(clip_dir) if clip_dir else None
-            if clip_state is not None and tokenizer is None:
+            clip_state, clip_dir, _, self.synthetic = load_clip_checkpoint("clip_score", self.vcfg, weights_dir, cache, seed)
+            if self.synthetic:            # scored through the byte-level stand-in tokenizer below
+                clip_state.update(synthetic_text_state(self.tcfg, seed))
+                clip_state["logit_scale"] = torch.tensor(SYNTHETIC_LOGIT_SCALE)
+            elif tokenizer is None:
                 tokenizer = load_clip_tokenizer(clip_dir)
                 if tokenizer is None:
                     raise FileNotFoundError(f"clip_score reward: the CLIP checkpoint in '{clip_dir}' has no tokenizer files (vocab.json, merges.txt); "
                                             f"real weights are never scored through the byte-level stand-in tokenizer")
-            if clip_state is None:
-                from ..utils.serialization import allow_synthetic
-                if not allow_synthetic():
-                    raise FileNotFoundError(
-                        f"clip_score reward: the CLIP ViT-L/14 checkpoint ({CHECKPOINT}) not found (looked for `clip/` in weights_dir / "
-                        f"$DDPO_AESTHETIC_WEIGHTS, then for a snapshot in '{os.path.join(REPO_ROOT, cache)}' and the HF cache; nothing is downloaded).  "
-                        f"Set DDPO_ALLOW_SYNTHETIC=1 to score with seeded RANDOM-INIT towers (benchmarks / tests only)")
-                print("[ models/clip_score ] WARNING: DDPO_ALLOW_SYNTHETIC=1 and no CLIP checkpoint on disk — scoring with seeded random-init "
-                      "CLIP towers and a byte-level tokenizer; rewards are meaningless")
-                clip_state, _ = synthetic_state_dicts(self.vcfg, self.vcfg.proj, seed)
-                clip_state.update(synthetic_text_state(self.tcfg, seed))
-                clip_state["logit_scale"] = torch.tensor(SYNTHETIC_LOGIT_SCALE)
-                self.synthetic = True
         if tokenizer is None:
             from .text import ByteTokenizer
             tokenizer = ByteTokenizer()
@@ -121,13 +108,12 @@ class ClipScorer:
                 raise KeyError("the CLIP state dict holds no `logit_scale`")
             logit_scale = float(torch.as_tensor(clip_state["logit_scale"]).double())
         self.logit_scale = float(logit_scale)
-        self.stream = torch.cuda.Stream(self.device)          # (after the weight lookup: a missing-weights refusal needs no GPU)
-        with torch.cuda.stream(self.stream):
+        super().__init__(device)      # (after the weight lookup: a missing-weights refusal needs no GPU)
+        with self.on_stream():
             self.vision = ClipVisionTower(self.vcfg, self.device)
             self.vision.load_state_dict(clip_state)
             self.text = ClipTextTower(self.tcfg, self.device)
             self.text.load_state_dict(clip_state)
-        self.stream.synchronize()
         self.prompts = PromptCache(self._embed_prompts, cache_size)
 
     def tokenize(self, prompts):
@@ -178,16 +164,13 @@ class ClipScorer:
         if on_device:
             images, ready = device_images(images, ready, "ClipScorer")
         else:
-            px = preprocess(images, self.vcfg.image)                           # host, PIL: byte-identical resize
-        with torch.cuda.stream(self.stream), L.fp32_class_datapath():
+            px, ready = preprocess(np.asarray(images, dtype=np.float32), self.vcfg.image), None      # host, PIL: byte-identical resize
+        with self.on_stream(ready), L.fp32_class_datapath():
             if on_device:
-                self.stream.wait_event(ready)
                 img = self._embed_patches(L.clip_preprocess(images, self.vcfg.image, self.vcfg.patch, self.vcfg.k_pad), images.shape[0])
             else:
                 img = self._embed_images(torch.from_numpy(px).to(self.device))
             txt = torch.stack(self.prompts.lookup(prompts))
             scores = L.cosine_rows(img, txt, scale=math.exp(self.logit_scale)).cpu().numpy()
             cosine = L.cosine_rows(img, txt).cpu().numpy()
-        self.stream.synchronize()
-        del images
         return (scores, cosine) if return_cosine else scores

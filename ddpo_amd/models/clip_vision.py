@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from .. import lib as L
+from .device_scorer import truncate_u8
 from .unet import ParamStore
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
@@ -55,8 +56,7 @@ def preprocess(images, size=224):
     mean, std = np.asarray(CLIP_MEAN, np.float32), np.asarray(CLIP_STD, np.float32)
     out = []
     for x in images:
-        x = np.asarray(x)
-        u8 = (x * 255).astype(np.uint8) if np.issubdtype(x.dtype, np.floating) else x
+        u8 = truncate_u8(x)
         h, w = u8.shape[:2]
         short, long = (w, h) if w <= h else (h, w)
         new_short, new_long = size, int(size * long / short)
@@ -67,20 +67,6 @@ def preprocess(images, size=224):
         f = (r.astype(np.float32) * (1 / 255)).astype(np.float32)
         out.append(((f - mean) / std).transpose(2, 0, 1))
     return np.stack(out).astype(np.float32)
-
-
-def device_images(images, ready, who):
-    """What the on-device scorers accept as a device batch: a contiguous N x H x W x 3 CUDA tensor, float32 in [0,1] or uint8.  Returns it with the
-    event its reader has to wait for (`ready`, else one recorded now on the caller's current stream)."""
-    if not images.is_cuda:
-        raise ValueError(f"{who} takes a numpy array or a CUDA tensor")
-    if images.dtype not in (torch.float32, torch.uint8):
-        raise ValueError(f"{who} takes float32 or uint8 device images, got {images.dtype}")
-    if images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
-        raise ValueError(f"{who} needs a contiguous N x H x W x 3 tensor, got shape {tuple(images.shape)}")
-    if ready is None:
-        ready = torch.cuda.current_stream(images.device).record_event()
-    return images, ready
 
 
 def vision_param_shapes(cfg: VisionConfig):

@@ -2,17 +2,16 @@
 byte for byte, without the images leaving the device — only the compressed files cross to the host.  What the LLaVA rewards send to their
 server (training/callbacks.py: llava_bertscore_device, llava_vqa_device).
 
-Like JpegSizer it runs on a private HIP stream with a workspace and a file buffer of its own: the reward callback is evaluated by a worker
-thread while the main thread samples the next batch, and the two must not share a stream or scratch space.  The kernels keep no state outside
-the workspace, so any number of encoders may run at once.
+A `DeviceScorer` (models/device_scorer.py) like JpegSizer: private HIP stream, a workspace and a file buffer of its own.
 """
-import numpy as np
 import torch
 
 from .. import lib as L
+from .device_scorer import DeviceScorer
+from .jpeg_size import jpeg_images
 
 
-class JpegEncoder:
+class JpegEncoder(DeviceScorer):
     def __init__(self, quality=80, device="cuda", stride=None):
         """`stride`: bytes of a row of the file buffer; default H * W * 3 + 625, which only a pathological image exceeds.  A batch with a longer
         file is encoded once more with rows of lib.jpeg_encode_max_bytes (`retries` counts those)."""
@@ -20,24 +19,18 @@ class JpegEncoder:
             raise ValueError(f"quality must be an integer in 1..100, got {quality!r}")
         if stride is not None and (int(stride) != stride or stride < L.JPEG_FIXED_BYTES):
             raise ValueError(f"stride must be an integer >= {L.JPEG_FIXED_BYTES}, got {stride!r}")
+        super().__init__(device)
         self.quality = int(quality)
-        self.device = torch.device(device)
-        self.stream = torch.cuda.Stream(self.device)
         self.stride = None if stride is None else int(stride)
         self.workspace = None
         self.files = None
         self.retries = 0
 
     def _workspace(self, n, h, w):
-        nb = L.jpeg_size_workspace_bytes(n, h, w)              # ValueError names the multiple-of-16 rule
-        if self.workspace is None or self.workspace.numel() < nb:
-            self.workspace = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        return self.workspace
+        return self._buffer("workspace", L.jpeg_size_workspace_bytes(n, h, w))              # ValueError names the multiple-of-16 rule
 
     def _files(self, n, stride):
-        if self.files is None or self.files.numel() < n * stride:
-            self.files = torch.empty(n * stride, dtype=torch.uint8, device=self.device)
-        return self.files[:n * stride].view(n, stride)
+        return self._buffer("files", n * stride)[:n * stride].view(n, stride)
 
     def _encode(self, dev_images, stride):
         """-> (files on the device, lengths on the host), on the current (this encoder's) stream"""
@@ -50,36 +43,16 @@ class JpegEncoder:
         tensor (float32 in [0,1] or uint8; no host trip).  Returns the N files as a list of bytes.
         A CUDA tensor is read on this encoder's stream after `ready` — an event recorded on the producing stream once the images were complete;
         default: one recorded now on the caller's current stream — and is referenced here until that work has finished."""
-        if isinstance(images, torch.Tensor):
-            if not images.is_cuda:
-                raise ValueError("JpegEncoder takes a numpy array or a CUDA tensor")
-            if not images.is_contiguous():
-                raise ValueError("JpegEncoder needs a contiguous N x H x W x 3 tensor")
-            if ready is None:
-                ready = torch.cuda.current_stream(images.device).record_event()
-            dev_images = images
-        else:
-            a = np.asarray(images)
-            if np.issubdtype(a.dtype, np.floating):
-                assert np.abs(a).max() <= 1.0
-                a = (a * 255).astype(np.uint8)                  # the reference's truncation (callbacks.encode_jpeg)
-            if a.dtype != np.uint8:
-                raise ValueError(f"JpegEncoder takes float or uint8 images, got {a.dtype}")
-            dev_images, ready = None, None
-        shape = images.shape if dev_images is not None else a.shape
-        n, h, w, _ = L._jpeg_encode_args(shape, self.quality)
-        with torch.cuda.stream(self.stream):
-            if dev_images is None:
-                dev_images = torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-            else:
-                self.stream.wait_event(ready)
+        images, ready = jpeg_images(images, ready, "JpegEncoder")
+        n, h, w, _ = L._jpeg_encode_args(images.shape, self.quality)
+        with self.on_stream(ready):
+            if not isinstance(images, torch.Tensor):
+                images = torch.from_numpy(images).to(self.device)
             stride = self.stride if self.stride is not None else h * w * 3 + L.JPEG_FIXED_BYTES
-            files, lengths = self._encode(dev_images, stride)
+            files, lengths = self._encode(images, stride)
             if int(lengths.max()) > stride:                     # rows held prefixes only: once more with rows no file exceeds
                 self.retries += 1
-                files, lengths = self._encode(dev_images, L.jpeg_encode_max_bytes(h, w))
+                files, lengths = self._encode(images, L.jpeg_encode_max_bytes(h, w))
             host = files[:, :int(lengths.max())].cpu()          # narrowed to the longest file: the padding of the rows stays on the device
-        self.stream.synchronize()
-        del dev_images
         host = host.numpy()
         return [host[i, :int(lengths[i])].tobytes() for i in range(n)]

@@ -3,8 +3,7 @@
 
 Mirror of /root/reference/ddpo/models/laion.py:7-51 (the dropouts are inert at inference; `set_weights` :38-51 transposes the
 published `.pth`'s torch (out,in) matrices into Dense kernels — the engine's (in,out) layout) and of the scoring path of
-/root/reference/ddpo/training/callbacks.py:60-95.  Runs on a private HIP stream: the reward callback is evaluated by a worker thread
-while the main thread samples the next batch (pipeline/policy_gradient.py), and the two must not share a stream or scratch space.
+/root/reference/ddpo/training/callbacks.py:60-95.  A `DeviceScorer` (models/device_scorer.py): it runs on a private HIP stream.
 
 Weights (nothing can be downloaded here):
   CLIP   `<weights_dir>/clip/` or an HF cache snapshot of `openai/clip-vit-large-patch14` (torch or Flax files)
@@ -18,8 +17,10 @@ import numpy as np
 import torch
 
 from .. import lib as L
-from .clip_vision import ClipVisionTower, VisionConfig, device_images, flax_tree_to_torch_names, preprocess
+from .clip_vision import ClipVisionTower, VisionConfig, flax_tree_to_torch_names, preprocess
+from .device_scorer import DeviceScorer, device_images
 
+CHECKPOINT = "openai/clip-vit-large-patch14"
 MLP_FILE = "sac+logos+ava1-l14-linearMSE.pth"
 MLP_LAYERS = (0, 2, 4, 6, 7)                  # keys of the published state dict (laion.set_weights :41)
 MLP_DIMS = (1024, 128, 64, 16, 1)
@@ -85,33 +86,38 @@ def find_weights(weights_dir=None, cache="cache"):
     return clip_dir, mlp
 
 
-class AestheticScorer:
+def load_clip_checkpoint(reward, cfg, weights_dir=None, cache="cache", seed=0, with_mlp=False):
+    """The weights of a CLIP reward, for every scorer that holds a tower: (clip_state, clip_dir, mlp_state, synthetic).  The checkpoint is looked
+    up by `find_weights` — with `with_mlp`, the aesthetic MLP file beside it (else mlp_state is None) — and nothing is downloaded.  Whatever is
+    missing is named in a FileNotFoundError, unless DDPO_ALLOW_SYNTHETIC=1 asks for the seeded random-init `synthetic_state_dicts(cfg, cfg.proj,
+    seed)` instead (benchmarks / tests): `synthetic` is then True and clip_dir None.  No GPU is touched."""
+    clip_dir, mlp_path = find_weights(weights_dir, cache)
+    clip_state = _load_clip_state(clip_dir) if clip_dir else None
+    missing = [name for name, absent in ((f"the CLIP ViT-L/14 checkpoint ({CHECKPOINT})", clip_state is None),
+                                         (MLP_FILE, with_mlp and mlp_path is None)) if absent]
+    if not missing:
+        return clip_state, clip_dir, torch.load(mlp_path, map_location="cpu", weights_only=True) if with_mlp else None, False
+    from ..utils.serialization import allow_synthetic
+    if not allow_synthetic():
+        raise FileNotFoundError(
+            f"{reward} reward: {' and '.join(missing)} not found (looked for `clip/` and the MLP file in weights_dir / $DDPO_AESTHETIC_WEIGHTS, "
+            f"then in '{os.path.join(REPO_ROOT, cache)}' and the HF cache; nothing is downloaded).  Set DDPO_ALLOW_SYNTHETIC=1 to score with "
+            f"seeded RANDOM-INIT weights (benchmarks / tests only)")
+    print(f"[ models/laion ] WARNING: DDPO_ALLOW_SYNTHETIC=1 and {' and '.join(missing)} not on disk — the {reward} reward is scored with "
+          f"seeded random-init weights; rewards are meaningless")
+    clip_state, mlp_state = synthetic_state_dicts(cfg, cfg.proj, seed)
+    return clip_state, None, mlp_state if with_mlp else None, True
+
+
+class AestheticScorer(DeviceScorer):
     def __init__(self, weights_dir=None, cache="cache", seed=0, device="cuda", config="vit-l/14", clip_state=None, mlp_state=None):
         """`clip_state` / `mlp_state`: state dicts handed in directly (tests); otherwise files are looked up (see module docstring)."""
-        self.device = torch.device(device)
         self.cfg = VisionConfig.named(config)
         self.synthetic = False
         if clip_state is None or mlp_state is None:
-            clip_dir, mlp_path = find_weights(weights_dir, cache)
-            loaded = _load_clip_state(clip_dir) if clip_dir else None
-            if loaded is None or mlp_path is None:
-                from ..utils.serialization import allow_synthetic
-                if not allow_synthetic():
-                    missing = [n for n, ok in (("the CLIP ViT-L/14 checkpoint (openai/clip-vit-large-patch14)", loaded is not None),
-                                               (MLP_FILE, mlp_path is not None)) if not ok]
-                    raise FileNotFoundError(
-                        f"aesthetic reward: {' and '.join(missing)} not found (looked in weights_dir / $DDPO_AESTHETIC_WEIGHTS, the HF cache and "
-                        f"'{os.path.join(REPO_ROOT, cache)}'; nothing is downloaded).  Set DDPO_ALLOW_SYNTHETIC=1 to score with a seeded "
-                        f"RANDOM-INIT model (benchmarks / tests only)")
-                print("[ models/laion ] WARNING: DDPO_ALLOW_SYNTHETIC=1 and no aesthetic-predictor weights on disk — scoring with a seeded "
-                      "random-init CLIP ViT-L/14 + MLP; rewards are meaningless")
-                clip_state, mlp_state = synthetic_state_dicts(self.cfg, self.cfg.proj, seed)
-                self.synthetic = True
-            else:
-                clip_state = loaded
-                mlp_state = torch.load(mlp_path, map_location="cpu", weights_only=True)
-        self.stream = torch.cuda.Stream(self.device)          # (after the weight lookup: a missing-weights refusal needs no GPU)
-        with torch.cuda.stream(self.stream):
+            clip_state, _, mlp_state, self.synthetic = load_clip_checkpoint("aesthetic", self.cfg, weights_dir, cache, seed, with_mlp=True)
+        super().__init__(device)      # (after the weight lookup: a missing-weights refusal needs no GPU)
+        with self.on_stream():
             self.tower = ClipVisionTower(self.cfg, self.device)
             self.tower.load_state_dict(clip_state)
             # MLP in the engine's (in, out) layout; the 1-wide last layer is zero-padded to 4 columns (vector epilogue of the GEMM)
@@ -123,7 +129,6 @@ class AestheticScorer:
                 wp = torch.zeros(w.shape[0], n4); wp[:, :w.shape[1]] = w
                 bp = torch.zeros(n4); bp[:b.numel()] = b
                 self.mlp.append((wp.to(self.device), bp.to(self.device), w.shape[1]))
-        self.stream.synchronize()
 
     def features(self, pixel_values):
         return self.tower(pixel_values)
@@ -141,15 +146,9 @@ class AestheticScorer:
         default: one recorded now on the caller's current stream — and is referenced here until that work has finished."""
         if isinstance(images, torch.Tensor):
             images, ready = device_images(images, ready, "AestheticScorer")
-            with torch.cuda.stream(self.stream), L.fp32_class_datapath():
-                self.stream.wait_event(ready)
+            with self.on_stream(ready), L.fp32_class_datapath():
                 patches = L.clip_preprocess(images, self.cfg.image, self.cfg.patch, self.cfg.k_pad)
-                scores = self._score(self.tower.forward_patches(patches))
-            self.stream.synchronize()
-            del images
-            return scores
-        px = preprocess(images, self.cfg.image)                               # host, PIL: byte-identical resize
-        with torch.cuda.stream(self.stream), L.fp32_class_datapath():
-            scores = self._score(self.tower(torch.from_numpy(px).to(self.device)))
-        self.stream.synchronize()
-        return scores
+                return self._score(self.tower.forward_patches(patches))
+        px = preprocess(np.asarray(images, dtype=np.float32), self.cfg.image)     # host, PIL: byte-identical resize
+        with self.on_stream(), L.fp32_class_datapath():
+            return self._score(self.tower(torch.from_numpy(px).to(self.device)))

@@ -27,12 +27,34 @@ import random
 import numpy as np
 from PIL import Image
 
+from ..models.device_scorer import truncate_u8
+
 
 def register(name):
     def deco(factory):
         callback_fns[name] = factory
         return factory
     return deco
+
+
+# ------------------------------------------------------------------------------------------------ host / device twins
+# A reward with a `*_device` twin is ONE body(images, prompts, metadata, ready=None) over a scorer that takes a host array or a CUDA tensor
+# (models/device_scorer.py); `_callback` makes either registry entry of it.
+def _callback(body, device):
+    """`device`: the body itself, flagged `wants_device_images` — the entrypoint then keeps the decoder's batch in HBM and hands it over with the
+    event that says it is complete (evaluate_callbacks_device); host arrays are taken too.  Otherwise the plain three-argument callback."""
+    if device:
+        body.wants_device_images = True
+        return body
+    return lambda images, prompts, metadata: body(images, prompts, metadata)
+
+
+def _negated(fn):
+    def _fn(*args, **kwargs):
+        scores, info = fn(*args, **kwargs)
+        return -scores, info
+
+    return _callback(_fn, device=True) if getattr(fn, "wants_device_images", False) else _fn
 
 
 # ------------------------------------------------------------------------------------------------ jpeg compressibility
@@ -42,9 +64,8 @@ def encode_jpeg(x, quality=95):
     x = np.asarray(x)
     if np.issubdtype(x.dtype, np.floating):
         assert np.abs(x).max() <= 1.0
-        x = (x * 255).astype(np.uint8)
     buf = io.BytesIO()
-    Image.fromarray(x).save(buf, "JPEG", quality=quality)
+    Image.fromarray(truncate_u8(x)).save(buf, "JPEG", quality=quality)
     return np.frombuffer(buf.getvalue(), dtype=np.uint8)
 
 
@@ -62,13 +83,7 @@ def jpeg_fn(devices=None, jit=False):
 
 def neg_jpeg_fn(*a, **kw):
     """reward = +(JPEG size in kB): incompressibility (reference :156-163)."""
-    inner = jpeg_fn(*a, **kw)
-
-    def _fn(*args, **kwargs):
-        scores, info = inner(*args, **kwargs)
-        return -scores, info
-
-    return _fn
+    return _negated(jpeg_fn(*a, **kw))
 
 
 def jpeg_device_fn(devices=None, jit=False, quality=95):
@@ -84,23 +99,26 @@ def jpeg_device_fn(devices=None, jit=False, quality=95):
         del prompts, metadata
         return -(sizer(images, ready=ready) / 1000.0)[:, None], {}
 
-    _fn.wants_device_images = True
-    return _fn
+    return _callback(_fn, device=True)
 
 
 def neg_jpeg_device_fn(*a, **kw):
     """`neg_jpeg` computed on the device: +(JPEG size in kB), see jpeg_device_fn."""
-    inner = jpeg_device_fn(*a, **kw)
-
-    def _fn(*args, **kwargs):
-        scores, info = inner(*args, **kwargs)
-        return -scores, info
-
-    _fn.wants_device_images = True
-    return _fn
+    return _negated(jpeg_device_fn(*a, **kw))
 
 
 # ------------------------------------------------------------------------------------------------ LAION aesthetic
+def _aesthetic(device, rng, cache, weights_dir):
+    from ..models.laion import AestheticScorer
+    scorer = AestheticScorer(weights_dir=weights_dir, cache=cache, seed=rng)
+
+    def _fn(images, prompts, metadata, ready=None):
+        del prompts, metadata
+        return scorer(images, ready=ready)[:, None], {"synthetic_weights": np.array(scorer.synthetic)}
+
+    return _callback(_fn, device)
+
+
 def aesthetic_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None):
     """CLIP ViT-L/14 image features -> L2-normalise -> LAION aesthetic MLP (reference :60-95, ddpo/models/laion.py), on the engine's
     own kernels (models/clip_vision.py, models/laion.py), on a private HIP stream.  Weights: `weights_dir` or $DDPO_AESTHETIC_WEIGHTS
@@ -108,40 +126,7 @@ def aesthetic_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None)
     `.pth`; nothing is downloaded.  Missing weights RAISE — an `a_*` run must not silently optimise a random reward — unless
     DDPO_ALLOW_SYNTHETIC=1, in which case info['synthetic_weights'] is True."""
     del devices, jit
-    from ..models.laion import AestheticScorer
-    scorer = AestheticScorer(weights_dir=weights_dir, cache=cache, seed=rng)
-
-    def _wrapper(images, prompts, metadata):
-        del prompts, metadata
-        scores = scorer(np.asarray(images, dtype=np.float32))
-        return scores[:, None], {"synthetic_weights": np.array(scorer.synthetic)}
-
-    return _wrapper
-
-
-# ------------------------------------------------------------------------------------------------ CLIPScore prompt alignment
-def clip_score_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None):
-    """reward = exp(logit_scale) * cos(CLIP image embedding, CLIP text embedding of the prompt) — the diagonal of transformers'
-    `CLIPModel.logits_per_image` — on the engine's own kernels (models/clip_score.py), on a private HIP stream.  Weights: the
-    `openai/clip-vit-large-patch14` checkpoint, looked up exactly like the aesthetic reward's (`weights_dir` or $DDPO_AESTHETIC_WEIGHTS
-    `/clip`, else the HF cache); nothing is downloaded.  Missing weights RAISE unless DDPO_ALLOW_SYNTHETIC=1, in which case
-    info['synthetic_weights'] is True.  Uses `prompts` (one string per image); `metadata` is ignored.  info['cosine'] is the raw cosine."""
-    del devices, jit
-    from ..models.clip_score import ClipScorer
-    scorer = ClipScorer(weights_dir=weights_dir, cache=cache, seed=rng)
-
-    def _wrapper(images, prompts, metadata):
-        del metadata
-        scores, cosine = scorer(np.asarray(images, dtype=np.float32), [str(p) for p in prompts], return_cosine=True)
-        return scores[:, None], {"cosine": cosine, "synthetic_weights": np.array(scorer.synthetic)}
-
-    return _wrapper
-
-
-# ------------------------------------------------------------------------------------------------ the CLIP rewards on device images
-def _is_device_batch(images):
-    import torch
-    return isinstance(images, torch.Tensor)
+    return _aesthetic(False, rng, cache, weights_dir)
 
 
 def aesthetic_device_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None):
@@ -150,35 +135,36 @@ def aesthetic_device_fn(devices=None, rng=0, cache="cache", jit=True, weights_di
     the patch matrix by one kernel (lib.clip_preprocess, csrc/clip_preprocess.hip) on the scorer's private stream; host arrays take `aesthetic`'s
     own path (PIL).  Weights as for `aesthetic`."""
     del devices, jit
-    from ..models.laion import AestheticScorer
-    scorer = AestheticScorer(weights_dir=weights_dir, cache=cache, seed=rng)
-
-    def _fn(images, prompts, metadata, ready=None):
-        del prompts, metadata
-        scores = scorer(images, ready=ready) if _is_device_batch(images) else scorer(np.asarray(images, dtype=np.float32))
-        return scores[:, None], {"synthetic_weights": np.array(scorer.synthetic)}
-
-    _fn.wants_device_images = True
-    return _fn
+    return _aesthetic(True, rng, cache, weights_dir)
 
 
-def clip_score_device_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None):
-    """`clip_score` without the host trip: the same scores and info (`cosine`, `synthetic_weights`), bit for bit; see aesthetic_device_fn."""
-    del devices, jit
+# ------------------------------------------------------------------------------------------------ CLIPScore prompt alignment
+def _clip_score(device, rng, cache, weights_dir):
     from ..models.clip_score import ClipScorer
     scorer = ClipScorer(weights_dir=weights_dir, cache=cache, seed=rng)
 
     def _fn(images, prompts, metadata, ready=None):
         del metadata
-        prompts = [str(p) for p in prompts]
-        if _is_device_batch(images):
-            scores, cosine = scorer(images, prompts, return_cosine=True, ready=ready)
-        else:
-            scores, cosine = scorer(np.asarray(images, dtype=np.float32), prompts, return_cosine=True)
+        scores, cosine = scorer(images, [str(p) for p in prompts], return_cosine=True, ready=ready)
         return scores[:, None], {"cosine": cosine, "synthetic_weights": np.array(scorer.synthetic)}
 
-    _fn.wants_device_images = True
-    return _fn
+    return _callback(_fn, device)
+
+
+def clip_score_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None):
+    """reward = exp(logit_scale) * cos(CLIP image embedding, CLIP text embedding of the prompt) — the diagonal of transformers'
+    `CLIPModel.logits_per_image` — on the engine's own kernels (models/clip_score.py), on a private HIP stream.  Weights: the
+    `openai/clip-vit-large-patch14` checkpoint, looked up exactly like the aesthetic reward's (`weights_dir` or $DDPO_AESTHETIC_WEIGHTS
+    `/clip`, else the HF cache); nothing is downloaded.  Missing weights RAISE unless DDPO_ALLOW_SYNTHETIC=1, in which case
+    info['synthetic_weights'] is True.  Uses `prompts` (one string per image); `metadata` is ignored.  info['cosine'] is the raw cosine."""
+    del devices, jit
+    return _clip_score(False, rng, cache, weights_dir)
+
+
+def clip_score_device_fn(devices=None, rng=0, cache="cache", jit=True, weights_dir=None):
+    """`clip_score` without the host trip: the same scores and info (`cosine`, `synthetic_weights`), bit for bit; see aesthetic_device_fn."""
+    del devices, jit
+    return _clip_score(True, rng, cache, weights_dir)
 
 
 # ------------------------------------------------------------------------------------------------ symmetry
@@ -186,12 +172,7 @@ def clip_score_device_fn(devices=None, rng=0, cache="cache", jit=True, weights_d
 # mean squared error.  The host callbacks below reproduce that number (held to results recorded from the reference,
 # tests/golden/reference_symmetry.json); the device twins get it from an exact integer sum (lib.symmetry_stats, column 0); both report the true
 # mean squared difference beside it (info["mse"]).  Partners are array views: u8[:, :, ::-1] is what PIL's ImageOps.mirror returns and
-# u8[:, ::-1, ::-1] what Image.rotate(180) returns, for any height and width.
-def _truncated_bytes(images):
-    """float (N,H,W,3) in [0,1] -> uint8 by truncation, the whole batch at once"""
-    return (np.asarray(images) * 255).astype(np.uint8)
-
-
+# u8[:, ::-1, ::-1] what Image.rotate(180) returns, for any height and width.  These pairs keep two bodies: numpy there, SymmetryStats here.
 def _partner(u8, mode):
     return u8[:, :, ::-1] if mode == "mirror" else u8[:, ::-1, ::-1]
 
@@ -208,7 +189,7 @@ def _wrapped_and_true_mse(u8, mode):
 def _wrapped_mse_fn(mode):
     def _fn(images, prompts, metadata):
         del prompts, metadata
-        wrapped, true = _wrapped_and_true_mse(_truncated_bytes(images), mode)
+        wrapped, true = _wrapped_and_true_mse(truncate_u8(images), mode)
         return -wrapped, {"mse": true}
 
     return _fn
@@ -237,7 +218,7 @@ def mirror_correlation_fn(devices=None, jit=False):
 
     def _fn(images, prompts, metadata):
         del prompts, metadata
-        x = _truncated_bytes(images).astype(np.float32) / np.float32(255)
+        x = truncate_u8(images).astype(np.float32) / np.float32(255)
         n = len(x)
         centred = x - x.reshape(n, -1).mean(axis=1).reshape(n, 1, 1, 1)
         cross = (centred * _partner(centred, "mirror")).reshape(n, -1).sum(axis=1)
@@ -261,8 +242,7 @@ def _wrapped_mse_device_fn(mode):
         stats = stats_of(images, ready=ready)
         return -(stats[:, 0] / n), {"mse": (2 * stats[:, 2] - 2 * stats[:, 3]) / n}
 
-    _fn.wants_device_images = True
-    return _fn
+    return _callback(_fn, device=True)
 
 
 def mirror_symmetry_device_fn(devices=None, jit=False):
@@ -296,8 +276,7 @@ def mirror_correlation_device_fn(devices=None, jit=False):
             scores.append(-np.float32(num / den) if den else np.float32("nan"))
         return np.array(scores, dtype=np.float32), {}
 
-    _fn.wants_device_images = True
-    return _fn
+    return _callback(_fn, device=True)
 
 
 def _mean_turn_angle(feats, n_images):
@@ -311,11 +290,18 @@ def _mean_turn_angle(feats, n_images):
     return -(degrees.sum(axis=0) / len(turned))
 
 
-def _rotational_embedder(embedder, rng, cache, weights_dir):
-    if embedder is not None:
-        return embedder
-    from ..models.symmetry import RotationalEmbedder
-    return RotationalEmbedder(weights_dir=weights_dir, cache=cache, seed=rng)
+def _rotational(device, embedder, rng, cache, weights_dir):
+    emb = embedder
+    if emb is None:
+        from ..models.symmetry import RotationalEmbedder
+        emb = RotationalEmbedder(weights_dir=weights_dir, cache=cache, seed=rng)
+
+    def _fn(images, prompts, metadata, ready=None):
+        del prompts, metadata
+        feats = emb(images) if ready is None else emb(images, ready=ready)
+        return _mean_turn_angle(np.asarray(feats), len(images)), {"synthetic_weights": np.array(getattr(emb, "synthetic", False))}
+
+    return _callback(_fn, device)
 
 
 def rotational_symmetry_fn(devices=None, jit=True, embedder=None, rng=0, cache="cache", weights_dir=None):
@@ -324,31 +310,16 @@ def rotational_symmetry_fn(devices=None, jit=True, embedder=None, rng=0, cache="
     for `clip_score`; missing weights RAISE unless DDPO_ALLOW_SYNTHETIC=1, in which case info['synthetic_weights'] is True.  `embedder`: anything
     called as embedder(images) -> (4 N, proj) features in the reference's order (tests).  Returns (N,) float32."""
     del devices, jit
-    emb = _rotational_embedder(embedder, rng, cache, weights_dir)
-
-    def _fn(images, prompts, metadata):
-        del prompts, metadata
-        images = np.asarray(images, dtype=np.float32)
-        return _mean_turn_angle(np.asarray(emb(images)), len(images)), {"synthetic_weights": np.array(getattr(emb, "synthetic", False))}
-
-    return _fn
+    return _rotational(False, embedder, rng, cache, weights_dir)
 
 
 def rotational_symmetry_device_fn(devices=None, jit=True, embedder=None, rng=0, cache="cache", weights_dir=None):
     """`rotational` without the host trip: the same scores and info, bit for bit.  A square CUDA tensor straight from the VAE decoder
     (`wants_device_images`) is truncated to bytes and turned by one kernel (lib.rotate4_u8, csrc/symmetry.hip) and preprocessed by another
     (lib.clip_preprocess) on the embedder's private stream; host arrays take `rotational`'s own path (PIL).  `embedder` is called as
-    embedder(images, ready=ready) for a device batch."""
+    embedder(images, ready=ready) when the caller hands an event over."""
     del devices, jit
-    emb = _rotational_embedder(embedder, rng, cache, weights_dir)
-
-    def _fn(images, prompts, metadata, ready=None):
-        del prompts, metadata
-        feats = emb(images, ready=ready) if _is_device_batch(images) else emb(np.asarray(images, dtype=np.float32))
-        return _mean_turn_angle(np.asarray(feats), len(images)), {"synthetic_weights": np.array(getattr(emb, "synthetic", False))}
-
-    _fn.wants_device_images = True
-    return _fn
+    return _rotational(True, embedder, rng, cache, weights_dir)
 
 
 # ------------------------------------------------------------------------------------------------ LLaVA over HTTP
@@ -366,8 +337,9 @@ def _llava_session():
     return sess
 
 
-def _bertscore_requests(sess, url, timeout, batch_size, files, prompts):
+def _bertscore_requests(sess, url, timeout, batch_size, files, prompts, metadata):
     """The request / reply loop of llava_bertscore over the images' JPEG files (a list of bytes), batched as np.array_split batches the images."""
+    del metadata
     nb = int(np.ceil(len(files) / batch_size))
     scores, info = [], {"precision": [], "f1": [], "outputs": []}
     for idx_b, prm_b in zip(np.array_split(np.arange(len(files)), nb), np.array_split(np.asarray(prompts), nb)):
@@ -381,8 +353,9 @@ def _bertscore_requests(sess, url, timeout, batch_size, files, prompts):
     return np.array(scores), {k: np.array(v) for k, v in info.items()}
 
 
-def _vqa_requests(sess, url, timeout, batch_size, files, metadata):
+def _vqa_requests(sess, url, timeout, batch_size, files, prompts, metadata):
     """The request / reply loop of llava_vqa over the images' JPEG files (a list of bytes)."""
+    del prompts
     nb = int(np.ceil(len(files) / batch_size))
     metadata = list(metadata)
     scores, answers = [], []
@@ -398,16 +371,22 @@ def _vqa_requests(sess, url, timeout, batch_size, files, metadata):
     return np.array(scores), {"answers": np.array(answers)}
 
 
-def _host_jpeg_files(images):
-    return [_to_jpeg_bytes(im) for im in (np.asarray(images) * 255).astype(np.uint8)]
+def _is_device_batch(images):
+    import torch
+    return isinstance(images, torch.Tensor)
+
+
+def _host_jpeg_files(images, ready=None):
+    del ready
+    return [_to_jpeg_bytes(im) for im in truncate_u8(images)]
 
 
 def _device_jpeg_files():
     """images -> JPEG files at quality 80: a CUDA batch through one JpegEncoder (models/jpeg_encode.py, created with the first such batch, on its
-    own stream), a host array through PIL as the host callbacks do."""
+    device and on a stream of its own), a host array through PIL as the host callbacks do."""
     encoder = []
 
-    def _files(images, ready):
+    def _files(images, ready=None):
         if not _is_device_batch(images):
             return _host_jpeg_files(images)
         if not encoder:
@@ -418,30 +397,28 @@ def _device_jpeg_files():
     return _files
 
 
+def _llava(device, requests_of, url, batch_size, timeout):
+    """The LLaVA pairs differ in where the files come from only: PIL, or for a CUDA batch the encoder above."""
+    sess, files_of = _llava_session(), _device_jpeg_files() if device else _host_jpeg_files
+
+    def _fn(images, prompts, metadata, ready=None):
+        return requests_of(sess, url, timeout, batch_size, files_of(images, ready), prompts, metadata)
+
+    return _callback(_fn, device)
+
+
 def llava_bertscore(devices=None, jit=False, url="http://127.0.0.1:8085", batch_size=16, timeout=120):
     """Alignment reward served by a LLaVA + BERTScore server (reference :465-537).  Wire format: POST of
     pickle.dumps({"images": [jpeg bytes, q=80], "queries": [[str]], "answers": [[str]]}); the reply is a pickled dict
     with "recall" (the reward), "precision", "f1", "outputs".  Batches of 16; 1000 retries on HTTP 500."""
-    sess = _llava_session()
-
-    def _fn(images, prompts, metadata):
-        del metadata
-        return _bertscore_requests(sess, url, timeout, batch_size, _host_jpeg_files(images), prompts)
-
-    return _fn
+    return _llava(False, _bertscore_requests, url, batch_size, timeout)
 
 
 def llava_vqa_satisfaction(devices=None, jit=False, url="http://127.0.0.1:8085", batch_size=4, timeout=120):
     """VQA reward (reference :402-462): request {"images", "queries"} (questions from the prompt metadata), reply
     {"outputs"}; the score of an image is the fraction of answers that contain the expected answer string
     (case-sensitive); info = {"answers": the server's outputs}."""
-    sess = _llava_session()
-
-    def _fn(images, prompts, metadata):
-        del prompts
-        return _vqa_requests(sess, url, timeout, batch_size, _host_jpeg_files(images), metadata)
-
-    return _fn
+    return _llava(False, _vqa_requests, url, batch_size, timeout)
 
 
 def llava_bertscore_device(devices=None, jit=False, url="http://127.0.0.1:8085", batch_size=16, timeout=120):
@@ -449,26 +426,12 @@ def llava_bertscore_device(devices=None, jit=False, url="http://127.0.0.1:8085",
     VAE decoder (`wants_device_images`: the entrypoint then keeps the batch in HBM, see evaluate_callbacks_device) is encoded once, on the device,
     into the files PIL writes at quality 80 (models/jpeg_encode.py, csrc/jpeg_size.hip) and only those cross to the host; host arrays take
     `llava_bertscore`'s own path (PIL).  Image height and width must be multiples of 16."""
-    sess, files_of = _llava_session(), _device_jpeg_files()
-
-    def _fn(images, prompts, metadata, ready=None):
-        del metadata
-        return _bertscore_requests(sess, url, timeout, batch_size, files_of(images, ready), prompts)
-
-    _fn.wants_device_images = True
-    return _fn
+    return _llava(True, _bertscore_requests, url, batch_size, timeout)
 
 
 def llava_vqa_device(devices=None, jit=False, url="http://127.0.0.1:8085", batch_size=4, timeout=120):
     """`llava_vqa` without the host trip of the pixels: the same requests, scores and info; see llava_bertscore_device."""
-    sess, files_of = _llava_session(), _device_jpeg_files()
-
-    def _fn(images, prompts, metadata, ready=None):
-        del prompts
-        return _vqa_requests(sess, url, timeout, batch_size, files_of(images, ready), metadata)
-
-    _fn.wants_device_images = True
-    return _fn
+    return _llava(True, _vqa_requests, url, batch_size, timeout)
 
 
 # ------------------------------------------------------------------------------------------------ registry
