@@ -69,28 +69,7 @@ __global__ __launch_bounds__(CP_TB) void clip_preprocess_kernel(const CpArgs a) 
   for (int r0 = 0; r0 < nrows; r0 += CP_STAGE_ROWS) {
     const int nr = min(CP_STAGE_ROWS, nrows - r0);
     const size_t row0 = ((size_t)n * a.H + (size_t)(y_lo + r0)) * w3;      // element index of the first staged row
-    if (VEC) {                                                              // W % 4 == 0 and an aligned base: rows start on 16 B (float) / 4 B (uint8)
-      const int q = w3 >> 2;
-      for (int i = t; i < nr * q; i += CP_TB) {
-        const int r = i / q, e = (i - r * q) * 4;
-        const size_t src = row0 + (size_t)r * w3 + e;
-        uint32_t pk;
-        if (F32) {
-          const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(a.images) + src);
-          pk = (uint32_t)cp_float_to_u8(v.x) | ((uint32_t)cp_float_to_u8(v.y) << 8) | ((uint32_t)cp_float_to_u8(v.z) << 16) |
-               ((uint32_t)cp_float_to_u8(v.w) << 24);
-        } else {
-          pk = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(a.images) + src);
-        }
-        *reinterpret_cast<uint32_t*>(s_in + r * srow + e) = pk;
-      }
-    } else {
-      for (int i = t; i < nr * w3; i += CP_TB) {
-        const int r = i / w3, e = i - r * w3;
-        const size_t src = row0 + (size_t)r * w3 + e;
-        s_in[r * srow + e] = F32 ? (uint8_t)cp_float_to_u8(static_cast<const float*>(a.images)[src]) : static_cast<const uint8_t*>(a.images)[src];
-      }
-    }
+    cp_stage_rows<F32, VEC, CP_TB>(a.images, row0, nr, w3, s_in, srow, t);
     __syncthreads();
     for (int i = t; i < nr * s3; i += CP_TB) {
       const int r = i / s3, rem = i - r * s3, xo = rem / 3, c = rem - xo * 3;

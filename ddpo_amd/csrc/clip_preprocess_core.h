@@ -1,7 +1,8 @@
 // CLIP image preprocessing: the per-pixel integer arithmetic of an 8-bit two-pass bicubic resize (what Pillow's Image.resize does to an RGB
 // image) as host + device inline functions.  csrc/clip_preprocess.hip runs them from its kernel and from the serial host entry
 // (ddpo_clip_preprocess_host), so whether the bytes equal Pillow's is decided by the host entry against Pillow itself
-// (tests/test_clip_preprocess_cpu.py) and the kernel only has to agree with the host entry.  Plain C++17: no HIP header is needed.
+// (tests/test_clip_preprocess_cpu.py) and the kernel only has to agree with the host entry.  csrc/resize_u8.hip runs the same functions to
+// output the resized bytes themselves.  Plain C++17 but for the kernels' row staging at the bottom (under __HIPCC__): no HIP header is needed.
 //
 // Everything here is integer once the pixel is a byte: the coefficient tables arrive as 22-bit fixed-point int32 (built by the caller in double
 // precision, lib.clip_preprocess_tables), a pass is acc = 2^21 + sum(pixel * coeff), result = clamp(acc >> 22, 0, 255), and the horizontal
@@ -45,3 +46,34 @@ CP_HD size_t cp_row_bytes(int pixels) { return ((size_t)pixels * 3 + 15) & ~(siz
 CP_HD size_t cp_lds_bytes(int rows, int size, int W) {
   return (size_t)rows * cp_row_bytes(size) + (size_t)CP_STAGE_ROWS * cp_row_bytes(W) + 256 * 3 * sizeof(float);
 }
+
+#if defined(__HIPCC__)
+// Kernel side: `nr` rows of w3 = W x 3 elements, starting at element `row0` of `images`, into s_in[r * srow + e] as bytes — float32 truncated by
+// cp_float_to_u8 — by the TB threads of a workgroup (thread t).  VEC: W % 4 == 0 and an aligned base, so rows start on 16 B (float) / 4 B (uint8)
+// and four elements move at a time.  The caller synchronises.
+template <bool F32, bool VEC, int TB>
+__device__ inline void cp_stage_rows(const void* images, size_t row0, int nr, int w3, uint8_t* s_in, int srow, int t) {
+  if (VEC) {
+    const int q = w3 >> 2;
+    for (int i = t; i < nr * q; i += TB) {
+      const int r = i / q, e = (i - r * q) * 4;
+      const size_t src = row0 + (size_t)r * w3 + e;
+      uint32_t pk;
+      if (F32) {
+        const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(images) + src);
+        pk = (uint32_t)cp_float_to_u8(v.x) | ((uint32_t)cp_float_to_u8(v.y) << 8) | ((uint32_t)cp_float_to_u8(v.z) << 16) |
+             ((uint32_t)cp_float_to_u8(v.w) << 24);
+      } else {
+        pk = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(images) + src);
+      }
+      *reinterpret_cast<uint32_t*>(s_in + r * srow + e) = pk;
+    }
+  } else {
+    for (int i = t; i < nr * w3; i += TB) {
+      const int r = i / w3, e = i - r * w3;
+      const size_t src = row0 + (size_t)r * w3 + e;
+      s_in[r * srow + e] = F32 ? (uint8_t)cp_float_to_u8(static_cast<const float*>(images)[src]) : static_cast<const uint8_t*>(images)[src];
+    }
+  }
+}
+#endif

@@ -175,6 +175,9 @@ _SIGS = {
     "ddpo_symmetry_stats_host": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p]),
     "ddpo_rotate4_u8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
     "ddpo_rotate4_u8_host": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p]),
+    # 8-bit bicubic resize to bytes (additive to ABI v14; csrc/resize_u8.hip)
+    "ddpo_resize_u8": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ddpo_resize_u8_host": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1905,6 +1908,79 @@ def clip_preprocess_host(images, size, patch, k_pad, return_resized=False):
                                             int(patch), ptr(hc), ptr(hb), hk, ptr(vc), ptr(vb), vk, ptr(norm), ptr(out), int(k_pad), ptr(resized)),
            "ddpo_clip_preprocess_host")
     return (out, resized) if return_resized else out
+
+
+# ------------------------------------------------------------------------------------------------ 8-bit bicubic resize to bytes
+RESIZE_U8_BAND = 2            # output rows of one workgroup (measured: DESIGN.md 2e); 1 where 2 break the LDS rule
+RESIZE_U8_RULE = ("the input rows one band of output rows needs (2 output rows, or 1 where 2 do not fit), resampled horizontally to bytes "
+                  "(rows x ow x 3), plus 8 staged input rows (W x 3 bytes each) must fit the 160 KB of LDS")
+
+
+def _resize_lds_bytes(rows, ow, w):
+    up = lambda px: (px * 3 + 15) // 16 * 16
+    return rows * up(ow) + CLIP_STAGE_ROWS * up(w)
+
+
+@functools.lru_cache(maxsize=None)
+def resize_u8_geometry(h, w, oh, ow):
+    """dict(band, rows) of a resize of h x w images to oh x ow: the output rows one workgroup makes — RESIZE_U8_BAND, halved while the LDS rule
+    is broken — and the most input rows such a band spans (by 16: 16 (band - 1) + 64).  ValueError with the rule that is broken."""
+    h, w, oh, ow = int(h), int(w), int(oh), int(ow)
+    if h < 1 or w < 1 or oh < 1 or ow < 1:
+        raise ValueError(f"resize_u8: sizes must be positive, got {h} x {w} images to {oh} x {ow}")
+    if oh > 1 << 15 or ow > 1 << 15 or h > 1 << 24 or w > 1 << 24:
+        raise ValueError(f"resize_u8: {h} x {w} images to {oh} x {ow}: at most 2^24 input and 2^15 output pixels a side")
+    _, vb, _ = clip_preprocess_tables(h, oh)
+    band = RESIZE_U8_BAND
+    while True:
+        rows = max(int((vb[y0:y0 + band, 0] + vb[y0:y0 + band, 1]).max() - vb[y0, 0]) for y0 in range(0, oh, band))
+        if _resize_lds_bytes(rows, ow, w) <= CLIP_LDS_LIMIT:
+            return dict(band=band, rows=max(rows, 1))
+        if band == 1:
+            raise ValueError(f"resize_u8: {h} x {w} images to {oh} x {ow} need {rows} rows = {_resize_lds_bytes(rows, ow, w)} bytes: {RESIZE_U8_RULE}")
+        band //= 2
+
+
+def _resize_target(who, oh, ow):
+    if int(oh) != oh or int(ow) != ow or oh < 1 or ow < 1:
+        raise ValueError(f"{who}: the output height and width must be positive integers, got {oh} x {ow}")
+    return int(oh), int(ow)
+
+
+def resize_u8(images, oh, ow, out=None):
+    """PIL.Image.resize((ow, oh), BICUBIC) of every image of an N x H x W x 3 CUDA batch — uint8, or float32 in [0, 1] truncated as
+    (x * 255).astype(uint8) — as one uint8 CUDA tensor (N, oh, ow, 3), in one launch on the current stream (ddpo_resize_u8): Pillow's bytes
+    exactly, up-scales included.  ValueError names the broken rule (RESIZE_U8_RULE for LDS)."""
+    _cuda_images("resize_u8", images, any_dtype=True)          # _symmetry_images names the dtype rule
+    n, h, w = _symmetry_images("resize_u8", images, True)
+    oh, ow = _resize_target("resize_u8", oh, ow)
+    geo = resize_u8_geometry(h, w, oh, ow)
+    hc, hb = _clip_device_tables(("axis", w, ow), lambda: clip_preprocess_tables(w, ow)[:2], images.device)
+    vc, vb = _clip_device_tables(("axis", h, oh), lambda: clip_preprocess_tables(h, oh)[:2], images.device)
+    if out is None:
+        out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=images.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, oh, ow, 3) or not out.is_contiguous() or out.device != images.device:
+        raise DdpoHipError(f"resize_u8: out must be a contiguous uint8 ({n}, {oh}, {ow}, 3) tensor on {images.device}")
+    _check(load().ddpo_resize_u8(_p(images), int(images.dtype == torch.float32), n, h, w, oh, ow, _p(hc), _p(hb), hc.shape[1], _p(vc), _p(vb),
+                                 vc.shape[1], geo["band"], geo["rows"], _p(out), _stream()), "ddpo_resize_u8")
+    return out
+
+
+def resize_u8_host(images, oh, ow):
+    """The same bytes computed serially on the host (ddpo_resize_u8_host) for a uint8 or float32 N x H x W x 3 numpy array: the GPU-free
+    reference, held to Pillow itself."""
+    import numpy as np
+    a = np.asarray(images)
+    n, h, w = _symmetry_images("resize_u8_host", a, False)
+    oh, ow = _resize_target("resize_u8_host", oh, ow)
+    geo = resize_u8_geometry(h, w, oh, ow)
+    hc, hb, hk = clip_preprocess_tables(w, ow)
+    vc, vb, vk = clip_preprocess_tables(h, oh)
+    out = np.zeros((n, oh, ow, 3), dtype=np.uint8)
+    ptr = lambda x: x.ctypes.data_as(c_void_p)
+    _check(load().ddpo_resize_u8_host(ptr(a), int(a.dtype == np.float32), n, h, w, oh, ow, ptr(hc), ptr(hb), hk, ptr(vc), ptr(vb), vk, geo["band"],
+                                      ptr(out)), "ddpo_resize_u8_host")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ symmetry rewards

@@ -6,7 +6,7 @@ Behavioural mirror of the registry / calling convention of /root/reference/ddpo/
 images: float32 (N,H,W,3) in [0,1]; scores: (N,) or (N,1) numpy; info: dict of numpy arrays.
 Callbacks run in a worker thread of the entrypoint (ThreadPoolExecutor, max_workers=2) next to the sampling of the
 following batch, so they must not touch the sampler's HIP stream: the host ones below are pure CPU code and the
-on-device ones (aesthetic, clip_score, rotational and every `*_device` name) use their own streams.
+on-device ones (aesthetic, clip_score, rotational, thumbnail and every `*_device` name) use their own streams.
 
 In scope (BASELINE.json configs): jpeg, neg_jpeg (+ jpeg_device, neg_jpeg_device: the same rewards counted on the device), aesthetic, llava_bertscore (+ its sibling llava_vqa wire format), and clip_score: the
 prompt-alignment reward that needs no server (CLIPScore on the engine's own CLIP towers; not in the reference, which aligns through LLaVA).
@@ -17,7 +17,9 @@ The symmetry family of the reference — mirror, mirror_corr, rotational_corr (p
 wraps, reproduced to the bit) and rotational (CLIP features of the four right-angle turns) — is here too, each with a `*_device` twin that reads the
 decoded batch where it is (models/symmetry.py, csrc/symmetry.hip): exact integer sums per image instead of PIL copies, turns and CLIP
 preprocessing on the device instead of 4N PIL rotations and resizes.
-The remaining reward ideas of the reference (thumbnail, consistency, diversity, BLIP-2 vqa, arange) are not part of any benchmark config; add
+thumbnail (scale invariance: CLIP features of an image against those of its thumbnails at 1/4, 1/8 and 1/16) has its `thumbnail_device` twin as
+well: the thumbnails are made by an 8-bit bicubic resize kernel that outputs Pillow's bytes (models/thumbnail.py, csrc/resize_u8.hip).
+The remaining reward ideas of the reference (consistency, diversity, BLIP-2 vqa, arange) are not part of any benchmark config; add
 them as plugins with `register`.
 """
 import io
@@ -280,8 +282,9 @@ def mirror_correlation_device_fn(devices=None, jit=False):
 
 
 def _mean_turn_angle(feats, n_images):
-    """Features (4 N, proj), one block of N rows per turn (0, 90, 180, 270 degrees) -> (N,) float32: minus the mean, over the three turns, of the
-    angle in degrees between an image's features and the turned image's.  Cosines outside [0, 1] are clipped, so an angle is at most 90."""
+    """Features (B N, proj), block 0 the N images as they are and every further block the same images changed one way (`rotational`: turned by
+    90, 180, 270 degrees; `thumbnail`: shrunk by 4, 8, 16) -> (N,) float32: minus the mean, over the B - 1 changes, of the angle in degrees
+    between an image's features and the changed image's.  Cosines outside [0, 1] are clipped, so an angle is at most 90."""
     blocks = feats.reshape(-1, n_images, feats.shape[-1])
     upright, turned = blocks[0], blocks[1:]
     lengths = np.linalg.norm(upright, axis=-1)[None] * np.linalg.norm(turned, axis=-1)
@@ -290,18 +293,22 @@ def _mean_turn_angle(feats, n_images):
     return -(degrees.sum(axis=0) / len(turned))
 
 
-def _rotational(device, embedder, rng, cache, weights_dir):
-    emb = embedder
-    if emb is None:
-        from ..models.symmetry import RotationalEmbedder
-        emb = RotationalEmbedder(weights_dir=weights_dir, cache=cache, seed=rng)
-
+def _mean_angle_callback(device, emb):
+    """The one body of `rotational` and `thumbnail`, host and device: `emb` makes the blocks of features, _mean_turn_angle the score."""
     def _fn(images, prompts, metadata, ready=None):
         del prompts, metadata
         feats = emb(images) if ready is None else emb(images, ready=ready)
         return _mean_turn_angle(np.asarray(feats), len(images)), {"synthetic_weights": np.array(getattr(emb, "synthetic", False))}
 
     return _callback(_fn, device)
+
+
+def _rotational(device, embedder, rng, cache, weights_dir):
+    emb = embedder
+    if emb is None:
+        from ..models.symmetry import RotationalEmbedder
+        emb = RotationalEmbedder(weights_dir=weights_dir, cache=cache, seed=rng)
+    return _mean_angle_callback(device, emb)
 
 
 def rotational_symmetry_fn(devices=None, jit=True, embedder=None, rng=0, cache="cache", weights_dir=None):
@@ -320,6 +327,34 @@ def rotational_symmetry_device_fn(devices=None, jit=True, embedder=None, rng=0, 
     embedder(images, ready=ready) when the caller hands an event over."""
     del devices, jit
     return _rotational(True, embedder, rng, cache, weights_dir)
+
+
+# ------------------------------------------------------------------------------------------------ thumbnail
+def _thumbnail(device, embedder, rng, cache, weights_dir):
+    emb = embedder
+    if emb is None:
+        from ..models.thumbnail import ThumbnailEmbedder
+        emb = ThumbnailEmbedder(weights_dir=weights_dir, cache=cache, seed=rng)
+    return _mean_angle_callback(device, emb)
+
+
+def thumbnail_fn(devices=None, jit=True, embedder=None, rng=0, cache="cache", weights_dir=None):
+    """reward = -(mean angle, in degrees, between the CLIP ViT-L/14 image features of an image and of its thumbnails, shrunk by 4, 8 and 16 with
+    Pillow's bicubic resize, each from the original) (reference :295-344): scale invariance.  The features are computed on the engine's own
+    kernels (models/thumbnail.py:ThumbnailEmbedder, on a private HIP stream).  Weights as for `clip_score`; missing weights RAISE unless
+    DDPO_ALLOW_SYNTHETIC=1, in which case info['synthetic_weights'] is True.  `embedder`: anything called as embedder(images) -> (4 N, proj)
+    features in the reference's order (tests).  Height and width must be at least 16.  Returns (N,) float32."""
+    del devices, jit
+    return _thumbnail(False, embedder, rng, cache, weights_dir)
+
+
+def thumbnail_device_fn(devices=None, jit=True, embedder=None, rng=0, cache="cache", weights_dir=None):
+    """`thumbnail` without the host trip: the same scores and info, bit for bit.  A CUDA tensor straight from the VAE decoder
+    (`wants_device_images`) is truncated to bytes and shrunk by three launches of one kernel (lib.resize_u8, csrc/resize_u8.hip), and the
+    originals and the thumbnails are preprocessed by another (lib.clip_preprocess) on the embedder's private stream; host arrays take
+    `thumbnail`'s own path (PIL).  `embedder` is called as embedder(images, ready=ready) when the caller hands an event over."""
+    del devices, jit
+    return _thumbnail(True, embedder, rng, cache, weights_dir)
 
 
 # ------------------------------------------------------------------------------------------------ LLaVA over HTTP
@@ -504,4 +539,6 @@ callback_fns = {
     "mirror_corr_device": mirror_correlation_device_fn,
     "rotational_corr_device": rotational_correlation_device_fn,
     "rotational_device": rotational_symmetry_device_fn,
+    "thumbnail": thumbnail_fn,
+    "thumbnail_device": thumbnail_device_fn,
 }

@@ -509,6 +509,18 @@ int ddpo_symmetry_stats(const void* images, int is_float32, int N, int H, int W,
 int ddpo_symmetry_stats_host(const void* images, int is_float32, int N, int H, int W, int mode, int64_t* stats_out_host);
 int ddpo_rotate4_u8(const void* images, int is_float32, int N, int H, int W, uint8_t* out, void* stream);
 int ddpo_rotate4_u8_host(const void* images, int is_float32, int N, int H, int W, uint8_t* out_host);
+/* 8-bit bicubic resize to bytes (csrc/resize_u8.hip; additive to ABI v14): out (uint8, N x oh x ow x 3) = what Pillow's Image.resize((ow, oh),
+ *   BICUBIC) returns for each RGB image of the batch — horizontal pass rounded to a byte, then the vertical pass.  One launch, one workgroup per
+ *   (image, band of `band` output rows).  images and tables as for ddpo_clip_preprocess: hcoef ow x hksize / hbounds ow x 2 for the horizontal
+ *   pass, vcoef oh x vksize / vbounds oh x 2 for the vertical pass; an axis that keeps its size gets the identity table; up-scales are in the
+ *   domain.  rows: the most input rows one band spans (from the caller's copy of vbounds).  out needs no alignment.
+ *   DDPO_EINVAL: a null pointer, a size < 1, oh or ow > 32768, band < 1, rows outside 1..H, and the LDS rule: rows x ow x 3 bytes + 8 staged
+ *   input rows of W x 3 bytes (each rounded up to 16) must fit 160 KB.  No workspace and no state: calls on different streams may overlap.
+ *   The _host entry is the same arithmetic, serially, on host memory (no GPU; it works `rows` out itself from `band` and checks the tables). */
+int ddpo_resize_u8(const void* images, int is_float32, int N, int H, int W, int oh, int ow, const int32_t* hcoef, const int32_t* hbounds, int hksize,
+                   const int32_t* vcoef, const int32_t* vbounds, int vksize, int band, int rows, uint8_t* out, void* stream);
+int ddpo_resize_u8_host(const void* images, int is_float32, int N, int H, int W, int oh, int ow, const int32_t* hcoef, const int32_t* hbounds,
+                        int hksize, const int32_t* vcoef, const int32_t* vbounds, int vksize, int band, uint8_t* out_host);
 int ddpo_timestep_embedding(const int32_t* ts, float* out, int B, int dim, void* stream); /* concat([cos, sin]) */
 int ddpo_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW, void* stream);
 int ddpo_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, void* stream);
