@@ -150,9 +150,9 @@ static int launch_attn(const float* q, int ldq, int qbat, const float* k, int ld
   return DDPO_OK;
 }
 
-/* batch b reads the queries of batch b % q_batches (q_batches == B: the plain function) */
-extern "C" int ddpo_attention_fwd_shared_q(const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
-                                           float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
+/* batch b reads the queries of batch b % q_batches */
+extern "C" int ddpo_attention_fwd(const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
+                                  float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
   if (!q || !k || !v || !o || B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0) return DDPO_EINVAL;
   if ((ldq & 3) || (ldk & 3) || (ldv & 3) || (ldo & 3)) return DDPO_EINVAL;
   if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
@@ -170,9 +170,4 @@ extern "C" int ddpo_attention_fwd_shared_q(const float* q, int ldq, int q_batche
     case 160: return launch_attn<160, 160, 32>(q, ldq, q_batches, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, scale, st);
     default:  return DDPO_EINVAL;
   }
-}
-
-extern "C" int ddpo_attention_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
-                                  float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
-  return ddpo_attention_fwd_shared_q(q, ldq, B, k, ldk, v, ldv, o, ldo, lse, B, heads, Nq, Nk, d, scale, stream);
 }

@@ -1,6 +1,6 @@
 // Flash attention forward on the 16-bit MFMA datapath, in two arithmetic variants of the second product (template flag F16P; the first product
-// is the same in both).  F16P = false is the `bf16x3` datapath's operator (ddpo_attention_fwd_bf16x3*): P and V split into bf16 hi + lo, three
-// passes, ~1e-6 on the output.  F16P = true is the `f16mx` datapath's (ddpo_attention_fwd_f16p*, round 4): described below, ~1e-5.
+// is the same in both).  F16P = false is the `bf16x3` datapath's operator (f16p == 0 of the entry points): P and V split into bf16 hi + lo, three
+// passes, ~1e-6 on the output.  F16P = true is the `f16mx` datapath's (f16p != 0, round 4): described below, ~1e-5.
 //   S^T (keys x queries) = K Q^T : bf16x3 — K and the pre-scaled Q split into bf16 hi + lo, three MFMA passes (a_lo*b_hi + a_hi*b_lo + a_hi*b_hi,
 //                                  fp32 accumulate, ~1e-5 relative: the scores are exponentiated, they keep the full split)
 //   O^T (d x queries)    = V^T P^T: since round 4 the probabilities are ONE f16 term and V is split into f16 hi + lo — two passes of
@@ -404,7 +404,7 @@ __device__ __forceinline__ void attn_tile_tail(const f32x16 (&sacc)[2], float& m
   }
 }
 
-// Where the normalised output rows go.  hi == nullptr: fp32 (rows, ld).  hi != nullptr (ABI v12, ddpo_attention_fwd_*_po): the bf16 hi / lo planes
+// Where the normalised output rows go.  hi == nullptr: fp32 (rows, ld).  hi != nullptr (o_hi of the entry points): the bf16 hi / lo planes
 // of the SAME fp32 values (the split the fp32-fed GEMM loader applies) — the operand format of the plane-fed to_out projection, so that layer
 // never reads an fp32 tensor; ld = plane row stride in elements (0: k-blocked planes (C / 32, rows, 32)), rows = B * Nq.
 struct AttnOut {
@@ -763,7 +763,7 @@ static size_t attn_ws(int B, int heads, int Nk) {
   return attn_img_bytes<D, DKP, DVP>(B, heads, Nk);
 }
 
-extern "C" size_t ddpo_attention_fwd_bf16x3_ws_bytes(int B, int heads, int Nk, int d) {
+extern "C" size_t ddpo_attention_fwd_x16_ws_bytes(int B, int heads, int Nk, int d) {
   if (B <= 0 || heads <= 0 || Nk <= 0) return 0;
   switch (d) {
     case 8:  return attn_ws<8, 16, 32>(B, heads, Nk);
@@ -818,40 +818,26 @@ static int attention_fwd_impl(const float* q, int ldq, int qbat, const float* k,
   ATTN_BY_D(CALL)
 #undef CALL
 }
-extern "C" int ddpo_attention_fwd_bf16x3(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
-                                         float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* ws, size_t ws_bytes,
-                                         void* stream) {
-  return attention_fwd_impl<false>(q, ldq, B, k, ldk, v, ldv, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale, ws,
-                                   ws_bytes, stream);
+/* The output form of the two forward entry points: o_hi == NULL: fp32 rows (o, ldo); o_hi != NULL: o must be NULL and the output leaves as bf16
+ * hi / lo planes (o_hi / o_lo, row stride ld_planes elements; 0 = k-blocked (heads * d / 32, B * Nq, 32)) of exactly the fp32 values the row
+ * form writes — no fp32 tensor is written.  attn_out_ok refuses the rest (neither form, planes without o_lo, alignment). */
+static AttnOut attn_out(float* o, int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, int64_t rows) {
+  return o_hi ? AttnOut{o, o_hi, o_lo, ld_planes, rows} : AttnOut{o, nullptr, nullptr, ldo, rows};
 }
-extern "C" int ddpo_attention_fwd_f16p(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
-                                       float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* ws, size_t ws_bytes,
-                                       void* stream) {
-  return attention_fwd_impl<true>(q, ldq, B, k, ldk, v, ldv, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale, ws,
-                                  ws_bytes, stream);
-}
-/* Plane-emitting forms (ABI v12): the output leaves as bf16 hi / lo planes (o_hi / o_lo, row stride ld_planes elements; 0 = k-blocked
- * (heads * d / 32, B * Nq, 32)) of exactly the fp32 values the functions above write — no fp32 tensor is written. */
-extern "C" int ddpo_attention_fwd_bf16x3_po(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, uint16_t* o_hi,
-                                            uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale,
-                                            void* ws, size_t ws_bytes, void* stream) {
-  if (!o_hi) return DDPO_EINVAL;
-  return attention_fwd_impl<false>(q, ldq, B, k, ldk, v, ldv, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale,
-                                   ws, ws_bytes, stream);
-}
-extern "C" int ddpo_attention_fwd_f16p_po(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, uint16_t* o_hi,
-                                          uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale,
-                                          void* ws, size_t ws_bytes, void* stream) {
-  if (!o_hi) return DDPO_EINVAL;
-  return attention_fwd_impl<true>(q, ldq, B, k, ldk, v, ldv, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d, scale,
-                                  ws, ws_bytes, stream);
+/* batch b reads the queries of batch b % q_batches (include/ddpo_hip.h) */
+extern "C" int ddpo_attention_fwd_x16(int f16p, const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv,
+                                      float* o, int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads,
+                                      int Nq, int Nk, int d, float scale, void* ws, size_t ws_bytes, void* stream) {
+  const AttnOut out = attn_out(o, ldo, o_hi, o_lo, ld_planes, (int64_t)B * Nq);
+  return !f16p ? attention_fwd_impl<false>(q, ldq, q_batches, k, ldk, v, ldv, out, lse, B, heads, Nq, Nk, d, scale, ws, ws_bytes, stream)
+               : attention_fwd_impl<true>(q, ldq, q_batches, k, ldk, v, ldv, out, lse, B, heads, Nq, Nk, d, scale, ws, ws_bytes, stream);
 }
 
 /* K / V of a (batch, head) set packed ONCE into the per-64-key-tile LDS images the attention kernels stream (any Nk), for callers whose
  * keys / values are constant over many attention calls — the text context of the cross-attention layers over the 50 DDIM steps of a
  * sampling call.  ddpo_attention_kv_images_bytes gives a buffer size that holds either variant's images (d = 40: the plain layout's, which the
- * stacked images of both variants fit into); ddpo_attention_fwd_{bf16x3,f16p}_images runs
- * the attention from the images of ITS variant's pack function (same kernels as the workspace form: identical results). */
+ * stacked images of both variants fit into); ddpo_attention_fwd_images runs the attention from the images packed with the SAME f16p (same
+ * kernels as the workspace form: identical results). */
 extern "C" size_t ddpo_attention_kv_images_bytes(int B, int heads, int Nk, int d) {
   if (B <= 0 || heads <= 0 || Nk <= 0) return 0;
   switch (d) {
@@ -877,13 +863,10 @@ static int pack_kv_impl(const float* k, int ldk, const float* v, int ldv, void* 
   ATTN_BY_D(CALL)
 #undef CALL
 }
-extern "C" int ddpo_attention_pack_kv_bf16x3(const float* k, int ldk, const float* v, int ldv, void* images, size_t images_bytes, int B, int heads,
-                                             int Nk, int d, void* stream) {
-  return pack_kv_impl<false>(k, ldk, v, ldv, images, images_bytes, B, heads, Nk, d, stream);
-}
-extern "C" int ddpo_attention_pack_kv_f16p(const float* k, int ldk, const float* v, int ldv, void* images, size_t images_bytes, int B, int heads,
-                                           int Nk, int d, void* stream) {
-  return pack_kv_impl<true>(k, ldk, v, ldv, images, images_bytes, B, heads, Nk, d, stream);
+extern "C" int ddpo_attention_pack_kv(int f16p, const float* k, int ldk, const float* v, int ldv, void* images, size_t images_bytes, int B,
+                                      int heads, int Nk, int d, void* stream) {
+  return !f16p ? pack_kv_impl<false>(k, ldk, v, ldv, images, images_bytes, B, heads, Nk, d, stream)
+               : pack_kv_impl<true>(k, ldk, v, ldv, images, images_bytes, B, heads, Nk, d, stream);
 }
 
 template <bool F16P>
@@ -901,52 +884,10 @@ static int attention_images_impl(const float* q, int ldq, int qbat, const void* 
   ATTN_BY_D(CALL)
 #undef CALL
 }
-extern "C" int ddpo_attention_fwd_bf16x3_images(const float* q, int ldq, const void* images, size_t images_bytes, float* o, int ldo, float* lse,
-                                                int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
-  return attention_images_impl<false>(q, ldq, B, images, images_bytes, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d,
-                                      scale, stream);
-}
-extern "C" int ddpo_attention_fwd_f16p_images(const float* q, int ldq, const void* images, size_t images_bytes, float* o, int ldo, float* lse,
-                                              int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
-  return attention_images_impl<true>(q, ldq, B, images, images_bytes, AttnOut{o, nullptr, nullptr, ldo, (int64_t)B * Nq}, lse, B, heads, Nq, Nk, d,
-                                     scale, stream);
-}
-extern "C" int ddpo_attention_fwd_bf16x3_images_po(const float* q, int ldq, const void* images, size_t images_bytes, uint16_t* o_hi, uint16_t* o_lo,
-                                                   int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
-  if (!o_hi) return DDPO_EINVAL;
-  return attention_images_impl<false>(q, ldq, B, images, images_bytes, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk,
-                                      d, scale, stream);
-}
-extern "C" int ddpo_attention_fwd_f16p_images_po(const float* q, int ldq, const void* images, size_t images_bytes, uint16_t* o_hi, uint16_t* o_lo,
-                                                 int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream) {
-  if (!o_hi) return DDPO_EINVAL;
-  return attention_images_impl<true>(q, ldq, B, images, images_bytes, AttnOut{nullptr, o_hi, o_lo, ld_planes, (int64_t)B * Nq}, lse, B, heads, Nq, Nk,
-                                     d, scale, stream);
-}
-
-/* Shared-query forms (include/ddpo_hip.h): batch b reads the queries of batch b % q_batches; everything else as the functions above. */
-static bool shared_q_out(float* o, int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, int64_t rows, AttnOut& out) {
-  if (o_hi) {
-    if (o) return false;
-    out = AttnOut{nullptr, o_hi, o_lo, ld_planes, rows};
-  } else {
-    out = AttnOut{o, nullptr, nullptr, ldo, rows};
-  }
-  return true;
-}
-extern "C" int ddpo_attention_fwd_x16_shared_q(int f16p, const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv,
-                                               float* o, int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads,
-                                               int Nq, int Nk, int d, float scale, void* ws, size_t ws_bytes, void* stream) {
-  AttnOut out;
-  if (!shared_q_out(o, ldo, o_hi, o_lo, ld_planes, (int64_t)B * Nq, out)) return DDPO_EINVAL;
-  return f16p ? attention_fwd_impl<true>(q, ldq, q_batches, k, ldk, v, ldv, out, lse, B, heads, Nq, Nk, d, scale, ws, ws_bytes, stream)
-              : attention_fwd_impl<false>(q, ldq, q_batches, k, ldk, v, ldv, out, lse, B, heads, Nq, Nk, d, scale, ws, ws_bytes, stream);
-}
-extern "C" int ddpo_attention_fwd_images_shared_q(int f16p, const float* q, int ldq, int q_batches, const void* images, size_t images_bytes,
-                                                  float* o, int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads,
-                                                  int Nq, int Nk, int d, float scale, void* stream) {
-  AttnOut out;
-  if (!shared_q_out(o, ldo, o_hi, o_lo, ld_planes, (int64_t)B * Nq, out)) return DDPO_EINVAL;
-  return f16p ? attention_images_impl<true>(q, ldq, q_batches, images, images_bytes, out, lse, B, heads, Nq, Nk, d, scale, stream)
-              : attention_images_impl<false>(q, ldq, q_batches, images, images_bytes, out, lse, B, heads, Nq, Nk, d, scale, stream);
+extern "C" int ddpo_attention_fwd_images(int f16p, const float* q, int ldq, int q_batches, const void* images, size_t images_bytes, float* o,
+                                         int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk,
+                                         int d, float scale, void* stream) {
+  const AttnOut out = attn_out(o, ldo, o_hi, o_lo, ld_planes, (int64_t)B * Nq);
+  return !f16p ? attention_images_impl<false>(q, ldq, q_batches, images, images_bytes, out, lse, B, heads, Nq, Nk, d, scale, stream)
+               : attention_images_impl<true>(q, ldq, q_batches, images, images_bytes, out, lse, B, heads, Nq, Nk, d, scale, stream);
 }

@@ -415,7 +415,7 @@ static int launch_bwd_bf16(const float* q, int ldq, const float* k, int ldk, con
 }
 
 // ================================================================================================
-// The `bf16x3` datapath's backward (ddpo_attention_bwd_bf16x3): EVERY product on three bf16 passes (all operands hi + lo), no scaling — the
+// The `bf16x3` datapath's backward (ddpo_attention_bwd_x16, f16p == 0): EVERY product on three bf16 passes (all operands hi + lo), no scaling — the
 // round-1..3 kernels, kept as the reference-accuracy variant (84 + 60 MFMAs per 64 x 32 block pair).
 // ================================================================================================
 namespace x3 {
@@ -720,39 +720,26 @@ static int launch_bwd_bf16(const float* q, int ldq, const float* k, int ldk, con
 
 }  // namespace x3
 
-extern "C" int ddpo_attention_bwd_bf16x3(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
-                                         const float* d_o, const float* lse, float* dvec, float* dq, float* dk, float* dv, int B,
-                                         int heads, int Nq, int Nk, int d, float scale, void* stream) {
+/* f16p == 0: the bf16x3 datapath's backward (namespace x3); else the f16mx datapath's (see the head of this file), whose dvec is
+ * B * heads * (Nq + 1) floats. */
+extern "C" int ddpo_attention_bwd_x16(int f16p, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
+                                      const float* d_o, const float* lse, float* dvec, float* dq, float* dk, float* dv, int B,
+                                      int heads, int Nq, int Nk, int d, float scale, void* stream) {
   if (!q || !k || !v || !o || !d_o || !lse || !dvec || !dq || !dk || !dv) return DDPO_EINVAL;
   if (B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0 || (ldq & 3) || (ldk & 3) || (ldv & 3) || (long)B * heads > 65535) return DDPO_EINVAL;
   hipStream_t st = as_stream(stream);
-#define BWDB(DD, DK, DV) return x3::launch_bwd_bf16<DD, DK, DV>(q, ldq, k, ldk, v, ldv, o, d_o, lse, dvec, dq, dk, dv, B, heads, Nq, Nk, scale, st)
-  switch (d) {
-    case 8: BWDB(8, 16, 32);
-    case 16: BWDB(16, 16, 32);
-    case 40: BWDB(40, 48, 64);
-    case 64: BWDB(64, 64, 64);
-    case 80: BWDB(80, 80, 96);
-    default: return DDPO_EINVAL;
+#define BWDB(DD, DK, DV) launch_bwd_bf16<DD, DK, DV>(q, ldq, k, ldk, v, ldv, o, d_o, lse, dvec, dq, dk, dv, B, heads, Nq, Nk, scale, st)
+#define BWD_BY_D(NS)                         \
+  switch (d) {                               \
+    case 8: return NS BWDB(8, 16, 32);       \
+    case 16: return NS BWDB(16, 16, 32);     \
+    case 40: return NS BWDB(40, 48, 64);     \
+    case 64: return NS BWDB(64, 64, 64);     \
+    case 80: return NS BWDB(80, 80, 96);     \
+    default: return DDPO_EINVAL;             \
   }
-#undef BWDB
-}
-
-/* The f16mx datapath's backward (see the head of this file); dvec: B * heads * (Nq + 1) floats. */
-extern "C" int ddpo_attention_bwd_f16p(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
-                                       const float* d_o, const float* lse, float* dvec, float* dq, float* dk, float* dv, int B,
-                                       int heads, int Nq, int Nk, int d, float scale, void* stream) {
-  if (!q || !k || !v || !o || !d_o || !lse || !dvec || !dq || !dk || !dv) return DDPO_EINVAL;
-  if (B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0 || (ldq & 3) || (ldk & 3) || (ldv & 3) || (long)B * heads > 65535) return DDPO_EINVAL;
-  hipStream_t st = as_stream(stream);
-#define BWDB(DD, DK, DV) return launch_bwd_bf16<DD, DK, DV>(q, ldq, k, ldk, v, ldv, o, d_o, lse, dvec, dq, dk, dv, B, heads, Nq, Nk, scale, st)
-  switch (d) {
-    case 8: BWDB(8, 16, 32);
-    case 16: BWDB(16, 16, 32);
-    case 40: BWDB(40, 48, 64);
-    case 64: BWDB(64, 64, 64);
-    case 80: BWDB(80, 80, 96);
-    default: return DDPO_EINVAL;
-  }
+  if (!f16p) BWD_BY_D(x3::)
+  BWD_BY_D()
+#undef BWD_BY_D
 #undef BWDB
 }

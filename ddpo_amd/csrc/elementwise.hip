@@ -5,7 +5,7 @@
 #include "common.h"
 #include <math.h>
 
-extern "C" int ddpo_abi_version(void) { return 14; }
+extern "C" int ddpo_abi_version(void) { return 15; }
 extern "C" size_t ddpo_sizeof_gemm_desc(void) { return sizeof(ddpo_gemm_desc); }
 extern "C" size_t ddpo_sizeof_ddim_consts(void) { return sizeof(ddpo_ddim_consts); }
 
@@ -437,11 +437,11 @@ __global__ void ppo_info_kernel(const float* __restrict__ per_sample, const floa
   }
 }
 
-extern "C" int ddpo_ddim_logprob_ppo_fwd_bwd_grouped(const float* eps_c, const float* eps_u, const float* x, const float* x_next,
-                                                     const int32_t* ts, const float* old_logp, const float* advantages,
-                                                     float guidance_scale, float clip_range, int train_cfg,
-                                                     const ddpo_ddim_consts* c, float* d_eps_c, float* d_eps_u, float* per_sample,
-                                                     float* info, int B, int group, int chw, void* stream) {
+extern "C" int ddpo_ddim_logprob_ppo_fwd_bwd(const float* eps_c, const float* eps_u, const float* x, const float* x_next,
+                                             const int32_t* ts, const float* old_logp, const float* advantages,
+                                             float guidance_scale, float clip_range, int train_cfg,
+                                             const ddpo_ddim_consts* c, float* d_eps_c, float* d_eps_u, float* per_sample,
+                                             float* info, int B, int group, int chw, void* stream) {
   if (!eps_c || !x || !x_next || !ts || !old_logp || !advantages || !c || !d_eps_c || !per_sample || !info) return DDPO_EINVAL;
   if (train_cfg && (!eps_u || !d_eps_u)) return DDPO_EINVAL;
   if (B <= 0 || group <= 0 || B % group || chw <= 0 || (chw & 3)) return DDPO_EINVAL;
@@ -463,15 +463,6 @@ extern "C" int ddpo_ddim_logprob_ppo_fwd_bwd_grouped(const float* eps_c, const f
   hipLaunchKernelGGL(ppo_info_kernel, dim3(B / group), dim3(64), 0, as_stream(stream), per_sample, old_logp, info, group);
   DDPO_LAUNCH_CHECK();
   return DDPO_OK;
-}
-
-extern "C" int ddpo_ddim_logprob_ppo_fwd_bwd(const float* eps_c, const float* eps_u, const float* x, const float* x_next,
-                                             const int32_t* ts, const float* old_logp, const float* advantages,
-                                             float guidance_scale, float clip_range, int train_cfg,
-                                             const ddpo_ddim_consts* c, float* d_eps_c, float* d_eps_u, float* per_sample,
-                                             float* info, int B, int chw, void* stream) {
-  return ddpo_ddim_logprob_ppo_fwd_bwd_grouped(eps_c, eps_u, x, x_next, ts, old_logp, advantages, guidance_scale, clip_range,
-                                               train_cfg, c, d_eps_c, d_eps_u, per_sample, info, B, B, chw, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

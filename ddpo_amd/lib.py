@@ -46,7 +46,7 @@ class GemmDesc(ctypes.Structure):
                 ("w_scale", c_void_p), ("planes_fmt", c_int), ("colsum", c_void_p), ("aux_out", c_void_p), ("res_rows", c_int)]
 
 
-ABI_VERSION = 14         # must equal ddpo_abi_version() of the loaded library (include/ddpo_hip.h)
+ABI_VERSION = 15         # must equal ddpo_abi_version() of the loaded library (include/ddpo_hip.h)
 
 _SIGS = {
     "ddpo_abi_version": (c_int, []),
@@ -60,10 +60,7 @@ _SIGS = {
                                    c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ddpo_ddim_logprob_ppo_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_float, c_float, c_int, POINTER(DdimConsts), c_void_p, c_void_p,
-                                              c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "ddpo_ddim_logprob_ppo_fwd_bwd_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                      c_float, c_float, c_int, POINTER(DdimConsts), c_void_p, c_void_p,
-                                                      c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+                                              c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ddpo_rwr_noisy_latents": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int,
                                        c_void_p]),
     "ddpo_rwr_mse_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
@@ -95,38 +92,20 @@ _SIGS = {
     # folded nearest-2x up-sampler (additive to ABI v14)
     "ddpo_fold_up2x_weights": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "ddpo_conv_up2x_folded_fwd": (c_int, [POINTER(GemmDesc), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    "ddpo_attention_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+    # attention forwards: q_batches after ldq; the 16-bit forms take f16p first and both output forms (o, ldo | o_hi, o_lo, ld_planes)
+    "ddpo_attention_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                    c_int, c_int, c_int, c_float, c_void_p]),
+    "ddpo_attention_fwd_x16_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ddpo_attention_fwd_x16": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                       c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
     "ddpo_attention_kv_images_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "ddpo_attention_pack_kv_bf16x3": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
-    "ddpo_attention_fwd_bf16x3_images": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                                 c_float, c_void_p]),
-    "ddpo_attention_fwd_bf16x3": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
-                                          c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
-    "ddpo_attention_fwd_bf16x3_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "ddpo_attention_fwd_f16p": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
-                                        c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
-    "ddpo_attention_pack_kv_f16p": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
-    "ddpo_attention_fwd_f16p_images": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                               c_float, c_void_p]),
-    # ABI v12: plane-emitting attention forwards (o_hi, o_lo, ld_planes replace o, ldo)
-    **{f"ddpo_attention_fwd_{v}_po": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
-                                              c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]) for v in ("bf16x3", "f16p")},
-    **{f"ddpo_attention_fwd_{v}_images_po": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
-                                                     c_int, c_int, c_float, c_void_p]) for v in ("bf16x3", "f16p")},
-    # shared-query attention forwards (additive to ABI v14): q_batches after ldq; the 16-bit forms take f16p first and both output forms
-    "ddpo_attention_fwd_shared_q": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
-                                            c_int, c_int, c_int, c_float, c_void_p]),
-    "ddpo_attention_fwd_x16_shared_q": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                                c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
-    "ddpo_attention_fwd_images_shared_q": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                                   c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "ddpo_attention_bwd_f16p": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "ddpo_attention_pack_kv": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
+    "ddpo_attention_fwd_images": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                          c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ddpo_attention_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "ddpo_attention_bwd_bf16x3": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "ddpo_attention_bwd_x16": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ddpo_groupnorm_stats_floats": (c_size_t, [c_int, c_int, c_int]),
     "ddpo_groupnorm_bwd_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "ddpo_groupnorm_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
@@ -638,23 +617,14 @@ def ddim_logprob_ppo_fwd_bwd(eps_c, eps_u, x, x_next, ts, old_logp, advantages, 
         d_u = torch.empty_like(eps_c) if train_cfg else None
         per_sample = torch.empty(B, 4, dtype=torch.float32, device=x.device)
         info = None
-    if group is None:
-        if info is None:
-            info = torch.empty(3, dtype=torch.float32, device=x.device)
-        _check(load().ddpo_ddim_logprob_ppo_fwd_bwd(_p(eps_c), _p(eps_u), _p(x), _p(x_next), _p(ts), _p(old_logp), _p(advantages),
-                                                    float(guidance_scale), float(clip_range), int(bool(train_cfg)), byref(consts),
-                                                    _p(d_c), _p(d_u), _p(per_sample), _p(info), B, chw, _stream()),
-               "ddpo_ddim_logprob_ppo_fwd_bwd")
-    else:
-        if group <= 0 or B % group:
-            raise ValueError(f"batch of {B} rows is not a whole number of micro-batches of {group}")
-        if info is None:
-            info = torch.empty(B // group, 3, dtype=torch.float32, device=x.device)
-        _check(load().ddpo_ddim_logprob_ppo_fwd_bwd_grouped(_p(eps_c), _p(eps_u), _p(x), _p(x_next), _p(ts), _p(old_logp),
-                                                            _p(advantages), float(guidance_scale), float(clip_range),
-                                                            int(bool(train_cfg)), byref(consts), _p(d_c), _p(d_u), _p(per_sample),
-                                                            _p(info), B, int(group), chw, _stream()),
-               "ddpo_ddim_logprob_ppo_fwd_bwd_grouped")
+    if group is not None and (group <= 0 or B % group):
+        raise ValueError(f"batch of {B} rows is not a whole number of micro-batches of {group}")
+    if info is None:
+        info = torch.empty(*((3,) if group is None else (B // group, 3)), dtype=torch.float32, device=x.device)
+    _check(load().ddpo_ddim_logprob_ppo_fwd_bwd(_p(eps_c), _p(eps_u), _p(x), _p(x_next), _p(ts), _p(old_logp), _p(advantages),
+                                                float(guidance_scale), float(clip_range), int(bool(train_cfg)), byref(consts),
+                                                _p(d_c), _p(d_u), _p(per_sample), _p(info), B, B if group is None else int(group), chw, _stream()),
+           "ddpo_ddim_logprob_ppo_fwd_bwd")
     return d_c, d_u, per_sample, info
 
 
@@ -1310,8 +1280,8 @@ def attention(q, k, v, B, heads, Nq, Nk, d, scale=None, out=None, ldq=None, ldk=
 
 
 def _attention_shared_q(q, q_batches, k, v, images, B, heads, Nq, Nk, d, sc, out, ldq, ldk, ldv, ldo, return_lse, planes_out):
-    """The one routing of attention() / attention_from_images() (images: K / V come packed) to the kernels, through the shared-query entry points
-    (q_batches = B is the plain function: the C side forwards its plain entry points to the same code)."""
+    """The one routing of attention() / attention_from_images() (images: K / V come packed) to the three forward entry points (q_batches = B:
+    every batch has its own queries)."""
     C = heads * d
     x16 = current_datapath() != "fp32" and d in (8, 16, 40, 64, 80)
     if planes_out and (not attention_planes_ok(d) or out is not None or return_lse):
@@ -1322,17 +1292,17 @@ def _attention_shared_q(q, q_batches, k, v, images, B, heads, Nq, Nk, d, sc, out
     lse = torch.empty(B * heads * Nq, dtype=torch.float32, device=q.device) if return_lse else None
     o_args = (None, 0, _p(opl.hi), _p(opl.lo), opl.ld) if opl is not None else (_p(out), int(ldo or C), None, None, 0)
     if images is not None:
-        _check(load().ddpo_attention_fwd_images_shared_q(int(_mx()), _pr(q, ldq), int(ldq or C), int(q_batches), _p(images), images.numel(), *o_args,
-                                                         _p(lse), B, heads, Nq, Nk, d, sc, _stream()), "ddpo_attention_fwd_images_shared_q")
+        _check(load().ddpo_attention_fwd_images(int(_mx()), _pr(q, ldq), int(ldq or C), int(q_batches), _p(images), images.numel(), *o_args,
+                                                _p(lse), B, heads, Nq, Nk, d, sc, _stream()), "ddpo_attention_fwd_images")
     elif x16:
-        nb = int(load().ddpo_attention_fwd_bf16x3_ws_bytes(B, heads, Nk, d))      # 0 for short key sequences
+        nb = int(load().ddpo_attention_fwd_x16_ws_bytes(B, heads, Nk, d))      # 0 for short key sequences
         ws = _scratch(nb, q.device, "attn_kv") if nb else None
-        _check(load().ddpo_attention_fwd_x16_shared_q(int(_mx()), _pr(q, ldq), int(ldq or C), int(q_batches), _pr(k, ldk), int(ldk or C), _pr(v, ldv),
-                                                      int(ldv or C), *o_args, _p(lse), B, heads, Nq, Nk, d, sc, _p(ws), nb, _stream()),
-               "ddpo_attention_fwd_x16_shared_q")
+        _check(load().ddpo_attention_fwd_x16(int(_mx()), _pr(q, ldq), int(ldq or C), int(q_batches), _pr(k, ldk), int(ldk or C), _pr(v, ldv),
+                                             int(ldv or C), *o_args, _p(lse), B, heads, Nq, Nk, d, sc, _p(ws), nb, _stream()),
+               "ddpo_attention_fwd_x16")
     else:
-        _check(load().ddpo_attention_fwd_shared_q(_pr(q, ldq), int(ldq or C), int(q_batches), _pr(k, ldk), int(ldk or C), _pr(v, ldv), int(ldv or C),
-                                                  _p(out), int(ldo or C), _p(lse), B, heads, Nq, Nk, d, sc, _stream()), "ddpo_attention_fwd_shared_q")
+        _check(load().ddpo_attention_fwd(_pr(q, ldq), int(ldq or C), int(q_batches), _pr(k, ldk), int(ldk or C), _pr(v, ldv), int(ldv or C),
+                                         _p(out), int(ldo or C), _p(lse), B, heads, Nq, Nk, d, sc, _stream()), "ddpo_attention_fwd")
     res = opl if opl is not None else out
     return (res, lse) if return_lse else res
 
@@ -1364,8 +1334,8 @@ def attention_kv_images(k, v, B, heads, Nk, d, out=None, ldk=None, ldv=None):
     nb = int(load().ddpo_attention_kv_images_bytes(B, heads, Nk, d))
     if out is None or out.numel() < nb:
         out = torch.empty(nb, dtype=torch.uint8, device=k.device)
-    fn, name = (load().ddpo_attention_pack_kv_f16p, "ddpo_attention_pack_kv_f16p") if _mx() else (load().ddpo_attention_pack_kv_bf16x3, "ddpo_attention_pack_kv_bf16x3")
-    _check(fn(_p(k), int(ldk or C), _p(v), int(ldv or C), _p(out), out.numel(), B, heads, Nk, d, _stream()), name)
+    _check(load().ddpo_attention_pack_kv(int(_mx()), _p(k), int(ldk or C), _p(v), int(ldv or C), _p(out), out.numel(), B, heads, Nk, d, _stream()),
+           "ddpo_attention_pack_kv")
     out._ddpo_kv_fmt = kv_images_fmt()       # the two packings have the same size and incompatible contents: the images carry their format
     return out
 
@@ -1403,11 +1373,12 @@ def attention_bwd(q, k, v, o, d_o, lse, B, heads, Nq, Nk, d, scale=None):
     dk = torch.empty(B * Nk, C, dtype=torch.float32, device=q.device)
     dv = torch.empty(B * Nk, C, dtype=torch.float32, device=q.device)
     dvec = torch.empty(B * heads * (Nq + 1), dtype=torch.float32, device=q.device)        # rowsum(dO * O) + one max-|dO| word per (batch, head) slab
-    fn, name = load().ddpo_attention_bwd, "ddpo_attention_bwd"
+    args = (_p(q), C, _p(k), C, _p(v), C, _p(o), _p(d_o), _p(lse), _p(dvec), _p(dq), _p(dk), _p(dv),
+            B, heads, Nq, Nk, d, float(scale if scale is not None else d ** -0.5), _stream())
     if current_datapath() != "fp32" and d in (8, 16, 40, 64, 80):
-        fn, name = (load().ddpo_attention_bwd_f16p, "ddpo_attention_bwd_f16p") if _mx() else (load().ddpo_attention_bwd_bf16x3, "ddpo_attention_bwd_bf16x3")
-    _check(fn(_p(q), C, _p(k), C, _p(v), C, _p(o), _p(d_o), _p(lse), _p(dvec), _p(dq), _p(dk), _p(dv),
-              B, heads, Nq, Nk, d, float(scale if scale is not None else d ** -0.5), _stream()), name)
+        _check(load().ddpo_attention_bwd_x16(int(_mx()), *args), "ddpo_attention_bwd_x16")
+    else:
+        _check(load().ddpo_attention_bwd(*args), "ddpo_attention_bwd")
     return dq, dk, dv
 
 

@@ -234,7 +234,7 @@ def train_steps_fused(state: AccumulatingTrainState, batches, noise_scheduler_st
     /root/reference/pipeline/policy_gradient.py:407-441 updates only at the last timestep of a mini-batch); summing inside
     one launch is the same arithmetic up to fp32 summation order, with 4x..16x more rows per GEMM (a micro-batch of 2
     samples x CFG is a U-Net batch of 4 — too small to fill 256 CUs).  Each micro-batch keeps its own mean loss
-    (`ddpo_ddim_logprob_ppo_fwd_bwd_grouped`) and its own info row, and n_acc advances by k.
+    (`ddpo_ddim_logprob_ppo_fwd_bwd` with `group`) and its own info row, and n_acc advances by k.
 
     batches: list of k dicts as for `train_step`, all with the same shapes.  `do_opt_update` applies after the LAST one.
     Returns (state, [info_0, ..., info_{k-1}])."""

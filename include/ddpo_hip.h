@@ -69,24 +69,18 @@ int ddpo_ddim_step_fwd(const float* eps_u, const float* eps_c, const float* x, c
 
 /* Scoring-mode step + PPO-clip loss + its gradient w.r.t. the two U-Net outputs:
  * ddpo/training/policy_gradient.py:95-125 (forward), jax.grad of it (:138-139) down to d eps_c / d eps_u.
- * per_sample: (B,4) = {log_prob, ratio, max(unclipped,clipped), clipped?}; info: 3 floats
- * {approx_kl, clipfrac, loss} (:132-134).  If train_cfg == 0, eps_u/d_eps_u may be NULL. */
+ * per_sample: (B,4) = {log_prob, ratio, max(unclipped,clipped), clipped?}; info: {approx_kl, clipfrac, loss} (:132-134).
+ * If train_cfg == 0, eps_u/d_eps_u may be NULL.
+ * The B rows are B/group micro-batches scored at once: rows [j*group, (j+1)*group) form micro-batch j (group >= 1, B % group == 0,
+ * DDPO_EINVAL otherwise; group == B: one batch, info is 3 floats).  Each micro-batch's loss is the mean over ITS `group` rows, so the
+ * gradients written are exactly those B/group separate calls would write (AccumulatingTrainState sums them anyway,
+ * ddpo/training/policy_gradient.py:32-48), and info is (B/group, 3): one {approx_kl, clipfrac, loss} per micro-batch. */
 int ddpo_ddim_logprob_ppo_fwd_bwd(const float* eps_c, const float* eps_u, const float* x,
                                   const float* x_next, const int32_t* ts, const float* old_logp,
                                   const float* advantages, float guidance_scale, float clip_range,
                                   int train_cfg, const ddpo_ddim_consts* c, float* d_eps_c,
-                                  float* d_eps_u, float* per_sample, float* info, int B, int chw,
-                                  void* stream);
-/* The same over k micro-batches at once: rows [j*group, (j+1)*group) form micro-batch j (B % group == 0).  Each
- * micro-batch's loss is the mean over ITS `group` rows, so the gradients written are exactly those k separate calls
- * would write (AccumulatingTrainState sums them anyway, ddpo/training/policy_gradient.py:32-48), and
- * info is (B/group, 3): one {approx_kl, clipfrac, loss} per micro-batch.  group == B is the call above. */
-int ddpo_ddim_logprob_ppo_fwd_bwd_grouped(const float* eps_c, const float* eps_u, const float* x,
-                                          const float* x_next, const int32_t* ts, const float* old_logp,
-                                          const float* advantages, float guidance_scale, float clip_range,
-                                          int train_cfg, const ddpo_ddim_consts* c, float* d_eps_c,
-                                          float* d_eps_u, float* per_sample, float* info, int B, int group,
-                                          int chw, void* stream);
+                                  float* d_eps_u, float* per_sample, float* info, int B, int group,
+                                  int chw, void* stream);
 
 /* ---- optimizer: optax.chain(clip_by_global_norm, adamw(mu_dtype=bf16)) + AccumulatingTrainState ----
  * pipeline/policy_gradient.py:130-150; ddpo/training/policy_gradient.py:32-48. */
@@ -325,101 +319,70 @@ int ddpo_gemm_conv_wgrad_bf16x3_planes(const ddpo_gemm_desc* d, const uint16_t* 
 int ddpo_pack_weights_bf16(const float* w, int K, int N, int Kp, uint16_t* fwd_hi, uint16_t* fwd_lo,
                            uint16_t* bwd_hi, uint16_t* bwd_lo, void* stream);
 
-/* Fused multi-head attention, softmax(q k^T * scale) v, flash-style on fp32 MFMA (16x16x4).
- * q:(B,Nq,·) k,v:(B,Nk,·) o:(B,Nq,·): head h occupies columns [h*d,(h+1)*d) of each row; ld* = row strides.
- * lse (optional, (B,heads,Nq)): log2-domain logsumexp of the scaled scores, consumed by the backward pass. */
-int ddpo_attention_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                       float* o, int ldo, float* lse, int B, int heads, int Nq, int Nk, int d, float scale,
-                       void* stream);
-/* Same contract on the bf16 MFMA datapath: Q, K, V and the probabilities are split into bf16 hi + lo and every
- * product takes three passes (fp32 accumulate, ~1e-5 relative).  d in {8, 16, 40, 64, 80}.
- * ws (optional, 16-byte aligned, >= ddpo_attention_fwd_bf16x3_ws_bytes): when given and Nk >= 256, K and V are split /
- * transposed once per (batch, head) into per-tile LDS images that the attention kernel streams; without it (or for
- * short key sequences, where the size query returns 0) every query tile stages K / V itself.  Results are identical. */
-size_t ddpo_attention_fwd_bf16x3_ws_bytes(int B, int heads, int Nk, int d);
-/* For keys / values that stay constant over many attention calls (the text context of the cross-attention layers over the DDIM
- * steps of a sampling call, /root/reference/ddpo/diffusers_patch/pipeline_flax_stable_diffusion.py:219-224 re-projects and
- * re-reads it every step): pack K / V ONCE into the per-tile images (any Nk, `images` 16-byte aligned, >=
- * ddpo_attention_kv_images_bytes) and run every attention from them.  Same kernels as above: identical results. */
+/* ---- Fused multi-head attention, softmax(q k^T * scale) v, flash-style (no N x N tensor is ever materialised).  Replaces
+ * nn.dot_product_attention of diffusers' FlaxAttentionBlock inside the U-Net call sites of
+ * ddpo/diffusers_patch/pipeline_flax_stable_diffusion.py:219-224 and ddpo/training/policy_gradient.py:87-102.
+ * LAYOUTS, common to every function of this section: q:(q_batches,Nq,.) k,v:(B,Nk,.) o:(B,Nq,.): head h occupies columns [h*d,(h+1)*d) of each
+ *   row; ld* = row strides in floats (multiples of 4), pointers 16-byte aligned.  lse (optional, (B,heads,Nq)): log2-domain logsumexp of the
+ *   scaled scores, consumed by the backward pass.
+ * QUERY PERIOD: q holds q_batches batches of Nq rows (1 <= q_batches <= B, B % q_batches == 0, DDPO_EINVAL otherwise) and the workgroups of
+ *   batch b read their queries from batch b % q_batches; K / V (or their images), the output rows and lse stay per b.  q_batches == B: every
+ *   batch has its own queries.  q_batches < B is for the cross-attention of a classifier-free-guidance batch [x; x], whose two halves share the
+ *   queries and differ in the text context only (pipeline_flax_stable_diffusion.py:219-224): the query projection runs, and is stored, once.
+ *   Same kernels and per-query arithmetic whatever the period. */
+
+/* The exact-fp32 kernel (fp32 MFMA 16x16x4): d in {4, 8, 16, 40, 64, 80, 160}. */
+int ddpo_attention_fwd(const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
+                       float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
+
+/* The same contract on the 16-bit MFMA kernels, d in {8, 16, 40, 64, 80}, in two arithmetic variants:
+ *   f16p == 0 (`bf16x3`): Q, K, V and the probabilities are split into bf16 hi + lo and every product takes three passes (fp32 accumulate,
+ *     ~1e-5 relative).
+ *   f16p != 0 (`f16p`, the attention of the f16mx datapath): the scores stay bf16 hi + lo on three MFMA passes; in the second product the
+ *     probabilities are ONE f16 term p = exp2(s - m + 14) (round to nearest even) against V split into f16 hi + lo — two passes — and the softmax
+ *     denominator is the sum of the same rounded probabilities (a row of ones in V^T where the head dim leaves a spare MFMA row), so O is an exact
+ *     convex combination of the values with weights perturbed by <= 2^-12 (csrc/attention_bf16.hip; 1.42 -> 1.29 ms on 4096^2 keys, d = 40,
+ *     batch 16).
+ * OUTPUT FORM: exactly one of o and o_hi is given (DDPO_EINVAL otherwise).  o: fp32 rows (o, ldo), as above.  o_hi (o must be NULL; o_lo must be
+ *   given too): the normalised output leaves as bf16 hi / lo PLANES (o_hi / o_lo: (B * Nq, heads * d) bf16 each, row stride ld_planes elements
+ *   (a multiple of 4), 8-byte aligned; ld_planes == 0: k-blocked (heads * d / 32, B * Nq, 32), heads * d % 32 == 0) holding exactly the split
+ *   hi = bf16(x), lo = bf16(x - hi) of the fp32 value the row form writes — the activation format of ddpo_gemm_conv_fwd_bf16_planes, so the
+ *   to_out projection behind the attention (diffusers FlaxAttentionBlock: proj_attn / to_out_0) reads planes by LDS-DMA and no fp32 tensor is
+ *   written or re-split: in the sampling forward at the 64x64 level that projection drops from 103 to 62 us per launch
+ *   (profiles/r04_timeline_sampling_step.txt).  Sampling path only (the training forward keeps the fp32 output its backward reads).
+ * WORKSPACE (ddpo_attention_fwd_x16): ws (optional, 16-byte aligned, >= ddpo_attention_fwd_x16_ws_bytes, which serves both variants): when
+ *   given and Nk >= 256, K and V are split / transposed once per (batch, head) into per-tile LDS images that the attention kernel streams;
+ *   without it (or for short key sequences, where the size query returns 0) every query tile stages K / V itself.  Results are identical.
+ * IMAGES (ddpo_attention_pack_kv + ddpo_attention_fwd_images), for keys / values that stay constant over many attention calls (the text context
+ *   of the cross-attention layers over the DDIM steps of a sampling call, pipeline_flax_stable_diffusion.py:219-224 re-projects and re-reads it
+ *   every step): pack K / V ONCE into the per-tile images (any Nk, `images` 16-byte aligned, >= ddpo_attention_kv_images_bytes — the same byte
+ *   size for both variants) and run every attention from them.  Images are only valid for a forward with the f16p they were packed with.  Same
+ *   kernels as the workspace form: identical results. */
+size_t ddpo_attention_fwd_x16_ws_bytes(int B, int heads, int Nk, int d);
+int ddpo_attention_fwd_x16(int f16p, const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv, float* o,
+                           int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d,
+                           float scale, void* ws, size_t ws_bytes, void* stream);
 size_t ddpo_attention_kv_images_bytes(int B, int heads, int Nk, int d);
-int ddpo_attention_pack_kv_bf16x3(const float* k, int ldk, const float* v, int ldv, void* images, size_t images_bytes,
-                                  int B, int heads, int Nk, int d, void* stream);
-int ddpo_attention_fwd_bf16x3_images(const float* q, int ldq, const void* images, size_t images_bytes, float* o, int ldo,
-                                     float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
-int ddpo_attention_fwd_bf16x3(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                              float* o, int ldo, float* lse, int B, int heads, int Nq, int Nk, int d, float scale,
-                              void* ws, size_t ws_bytes, void* stream);
-/* Attention backward with probability recomputation (no N x N tensor is ever materialised):
- * dvec (B,heads,Nq) scratch = rowsum(dO * O); dq/dk/dv have the layout of q/k/v with contiguous rows of heads*d. */
+int ddpo_attention_pack_kv(int f16p, const float* k, int ldk, const float* v, int ldv, void* images, size_t images_bytes, int B, int heads,
+                           int Nk, int d, void* stream);
+int ddpo_attention_fwd_images(int f16p, const float* q, int ldq, int q_batches, const void* images, size_t images_bytes, float* o,
+                              int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk,
+                              int d, float scale, void* stream);
+
+/* Attention backward with probability recomputation: dvec (B,heads,Nq) scratch = rowsum(dO * O); dq/dk/dv have the layout of q/k/v with
+ * contiguous rows of heads*d (one query batch per batch: no query period).  Exact fp32. */
 int ddpo_attention_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
                        const float* d_o, const float* lse, float* dvec, float* dq, float* dk, float* dv,
                        int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
-
-/* Attention backward on the bf16x3 datapath (same arguments; d in {8, 16, 40, 64, 80}): every product on three bf16 passes. */
-int ddpo_attention_bwd_bf16x3(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
-                              const float* d_o, const float* lse, float* dvec, float* dq, float* dk, float* dv,
-                              int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
-
-/* ---- `f16p` attention operators (ABI v11): the attention of the f16mx datapath.  Same arguments and layouts as the bf16x3 functions of the
- * same name; the images of ddpo_attention_pack_kv_f16p are only valid for ddpo_attention_fwd_f16p_images (same byte size,
- * ddpo_attention_kv_images_bytes).  Arithmetic: the scores stay bf16 hi + lo on three MFMA passes; in the second product the probabilities are
- * ONE f16 term p = exp2(s - m + 14) (round to nearest even) against V split into f16 hi + lo — two passes — and the softmax denominator is the
- * sum of the same rounded probabilities (a row of ones in V^T where the head dim leaves a spare MFMA row), so O is an exact convex combination
- * of the values with weights perturbed by <= 2^-12 (csrc/attention_bf16.hip; 1.42 -> 1.29 ms on 4096^2 keys, d = 40, batch 16).
- * Replaces nn.dot_product_attention of diffusers' FlaxAttentionBlock inside the U-Net call sites of
- * ddpo/diffusers_patch/pipeline_flax_stable_diffusion.py:219-224 and ddpo/training/policy_gradient.py:87-102. */
-int ddpo_attention_fwd_f16p(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
-                            float* o, int ldo, float* lse, int B, int heads, int Nq, int Nk, int d, float scale,
-                            void* ws, size_t ws_bytes, void* stream);
-int ddpo_attention_pack_kv_f16p(const float* k, int ldk, const float* v, int ldv, void* images, size_t images_bytes, int B, int heads,
-                                int Nk, int d, void* stream);
-int ddpo_attention_fwd_f16p_images(const float* q, int ldq, const void* images, size_t images_bytes, float* o, int ldo,
-                                   float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
-/* Backward of the same operator.  `dvec` is a scratch of B * heads * (Nq + 1) floats: rowsum(dO * O) followed by one word per (batch, head)
- * slab — the float bits of max |dO| over the slab, from which the kernels take the power of two that brings dO into the f16 range whatever the
- * loss scale.  Scores: bf16 hi + lo, three passes; dP = dO V^T, dV = P^T dO, dK = dS^T Q, dQ = dS K: a single f16 term (dO, P, dS) against an
- * f16 hi + lo split, two passes (csrc/attention_bwd_bf16.hip). */
-int ddpo_attention_bwd_f16p(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
-                            const float* d_o, const float* lse, float* dvec, float* dq, float* dk, float* dv,
-                            int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
-
-
-/* ---- Plane-emitting attention forwards (ABI v12).  Same arithmetic and arguments as the function of the same name without `_po`, except that
- * the normalised output leaves as bf16 hi / lo PLANES (o_hi / o_lo: (B * Nq, heads * d) bf16 each, row stride ld_planes elements, 8-byte
- * aligned; ld_planes == 0: k-blocked (heads * d / 32, B * Nq, 32), heads * d % 32 == 0) holding exactly the split hi = bf16(x), lo = bf16(x - hi)
- * of the fp32 value the plain function writes — the activation format of ddpo_gemm_conv_fwd_bf16_planes, so the to_out projection behind the
- * attention (diffusers FlaxAttentionBlock: proj_attn / to_out_0) reads planes by LDS-DMA and no fp32 tensor is written or re-split: in the
- * sampling forward at the 64x64 level that projection drops from 103 to 62 us per launch (profiles/r04_timeline_sampling_step.txt).
- * lse may be NULL.  Sampling path only (the training forward keeps the fp32 output its backward reads). */
-int ddpo_attention_fwd_bf16x3_po(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, uint16_t* o_hi, uint16_t* o_lo,
-                                 int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* ws, size_t ws_bytes,
-                                 void* stream);
-int ddpo_attention_fwd_f16p_po(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, uint16_t* o_hi, uint16_t* o_lo,
-                               int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* ws, size_t ws_bytes,
-                               void* stream);
-int ddpo_attention_fwd_bf16x3_images_po(const float* q, int ldq, const void* images, size_t images_bytes, uint16_t* o_hi, uint16_t* o_lo,
-                                        int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
-int ddpo_attention_fwd_f16p_images_po(const float* q, int ldq, const void* images, size_t images_bytes, uint16_t* o_hi, uint16_t* o_lo,
-                                      int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
-
-/* ---- Shared-query attention forwards (additive to ABI v14).  The same kernels and per-query arithmetic as the functions above, with a query
- * batch period: q holds q_batches batches of Nq rows (1 <= q_batches <= B, B % q_batches == 0, DDPO_EINVAL otherwise) and the workgroups of
- * batch b read their queries from batch b % q_batches; K / V (or their images), the output rows and lse stay per b.  q_batches == B is the plain
- * function.  For the cross-attention of a classifier-free-guidance batch [x; x], whose two halves share the queries and differ in the text
- * context only (pipeline_flax_stable_diffusion.py:219-224): the query projection runs, and is stored, once.
- *   ddpo_attention_fwd_shared_q          the exact-fp32 kernel (ddpo_attention_fwd);
- *   ddpo_attention_fwd_x16_shared_q      the 16-bit MFMA kernels: f16p == 0 ddpo_attention_fwd_bf16x3, else ddpo_attention_fwd_f16p;
- *   ddpo_attention_fwd_images_shared_q   the same from K / V images of the matching pack function (ddpo_attention_fwd_{bf16x3,f16p}_images).
- * Output of the last two: o_hi == NULL: fp32 rows (o, ldo); o_hi != NULL: o must be NULL and the output leaves as planes exactly as in the
- * `_po` functions (o_hi, o_lo, ld_planes). */
-int ddpo_attention_fwd_shared_q(const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
-                                float* lse, int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
-int ddpo_attention_fwd_x16_shared_q(int f16p, const float* q, int ldq, int q_batches, const float* k, int ldk, const float* v, int ldv, float* o,
-                                    int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk, int d,
-                                    float scale, void* ws, size_t ws_bytes, void* stream);
-int ddpo_attention_fwd_images_shared_q(int f16p, const float* q, int ldq, int q_batches, const void* images, size_t images_bytes, float* o,
-                                       int ldo, uint16_t* o_hi, uint16_t* o_lo, int ld_planes, float* lse, int B, int heads, int Nq, int Nk,
-                                       int d, float scale, void* stream);
+/* The same on the 16-bit MFMA kernels (same arguments behind f16p; d in {8, 16, 40, 64, 80}; csrc/attention_bwd_bf16.hip):
+ *   f16p == 0: every product on three bf16 passes.
+ *   f16p != 0: the backward of the f16p forward.  `dvec` is then a scratch of B * heads * (Nq + 1) floats: rowsum(dO * O) followed by one word
+ *     per (batch, head) slab — the float bits of max |dO| over the slab, from which the kernels take the power of two that brings dO into the
+ *     f16 range whatever the loss scale.  Scores: bf16 hi + lo, three passes; dP = dO V^T, dV = P^T dO, dK = dS^T Q, dQ = dS K: a single f16
+ *     term (dO, P, dS) against an f16 hi + lo split, two passes. */
+int ddpo_attention_bwd_x16(int f16p, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
+                           const float* d_o, const float* lse, float* dvec, float* dq, float* dk, float* dv,
+                           int B, int heads, int Nq, int Nk, int d, float scale, void* stream);
 
 /* Small element-wise pieces. */
 int ddpo_geglu_fwd(const float* x, float* y, int64_t rows, int F, void* stream);      /* y = x[:, :F] * gelu_tanh(x[:, F:]) */

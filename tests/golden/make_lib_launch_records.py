@@ -31,7 +31,7 @@ SWITCHES = ("PLANES", "PLANES_ALL", "PLANES_OUT", "TRAIN_PLANES", "BF16_PLANES",
             "UP2X_FOLD", "MX_CROSS")
 DEFAULTS = dict(PLANES=True, PLANES_ALL=False, PLANES_OUT=True, TRAIN_PLANES=True, BF16_PLANES=True, GEGLU_TALL=True, W_KBLOCKED=True,
                 A_KBLOCKED=False, DGRAD_FWD=True, UP2X_FOLD=True, MX_CROSS=True)
-FIXED = {"ddpo_abi_version": 14, "ddpo_gemm_splitk_min_ktiles": 40, "ddpo_groupnorm_ws_bytes": 4096, "ddpo_groupnorm_stats_floats": 512,
+FIXED = {"ddpo_abi_version": 15, "ddpo_gemm_splitk_min_ktiles": 40, "ddpo_groupnorm_ws_bytes": 4096, "ddpo_groupnorm_stats_floats": 512,
          "ddpo_groupnorm_bwd_ws_bytes": 4096}
 LIM = 0x7FFFFFFF
 _DT = {torch.float32: "f32", torch.int16: "i16", torch.uint8: "u8"}        # labels of tensors a wrapper allocates: dtype:shape#ordinal

@@ -22,7 +22,27 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in ddpo_hip.h but not exported"
     assert declared == set(L.EXPORTED_SYMBOLS)
-    assert L.load().ddpo_abi_version() == L.ABI_VERSION == 14
+    assert L.load().ddpo_abi_version() == L.ABI_VERSION == 15
+
+
+def test_signatures_match_the_header_prototypes():
+    """Every `int|size_t ddpo_*( ... );` prototype of the header against its row of L._SIGS: the parameter count, the return type, a pointer
+    exactly where the binding passes one, and the same scalar kind elsewhere — ctypes checks none of this on a positional call."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ddpo_hip.h")).read(), flags=re.S)
+    protos = re.findall(r"\b(int|size_t)\s+(ddpo_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert len(protos) == len(L._SIGS) == 83 and {name for _, name, _ in protos} == set(L._SIGS)
+    scalars = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+               "uint32_t": ctypes.c_uint32, "int": ctypes.c_int}
+    for ret, name, params in protos:
+        restype, argtypes = L._SIGS[name]
+        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
+        assert len(params) == len(argtypes), name
+        assert (restype is ctypes.c_size_t) == (ret == "size_t") and restype in (ctypes.c_size_t, ctypes.c_int), name
+        for i, (p, t) in enumerate(zip(params, argtypes)):
+            if "*" in p:
+                assert t is ctypes.c_void_p or issubclass(t, ctypes._Pointer), f"{name} argument {i}: {p}"
+            else:
+                assert t is scalars[p.split()[0]], f"{name} argument {i}: {p}"
 
 
 def test_struct_mirrors():

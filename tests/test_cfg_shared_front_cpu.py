@@ -28,7 +28,7 @@ def test_res_rows_is_the_trailing_field_of_the_descriptor():
 
 def test_shared_query_entry_points_are_declared_and_bound():
     hdr = open(os.path.join(ROOT, "include", "ddpo_hip.h")).read()
-    for name in ("ddpo_attention_fwd_shared_q", "ddpo_attention_fwd_x16_shared_q", "ddpo_attention_fwd_images_shared_q"):
+    for name in ("ddpo_attention_fwd", "ddpo_attention_fwd_x16", "ddpo_attention_fwd_images"):
         assert re.search(r"\b" + name + r"\s*\(", hdr) and name in L.EXPORTED_SYMBOLS and hasattr(L.load(), name)
 
 
@@ -65,13 +65,13 @@ def test_invalid_query_period_is_einval(q_batches):
     lib = L.load()
     B, heads, Nq, Nk, d = 4, 2, 64, 77, 40
     C = heads * d
-    assert lib.ddpo_attention_fwd_shared_q(FAKE, C, q_batches, FAKE, C, FAKE, C, FAKE, C, None, B, heads, Nq, Nk, d, 1.0, None) == -1
+    assert lib.ddpo_attention_fwd(FAKE, C, q_batches, FAKE, C, FAKE, C, FAKE, C, None, B, heads, Nq, Nk, d, 1.0, None) == -1
     for f16p in (0, 1):
-        assert lib.ddpo_attention_fwd_x16_shared_q(f16p, FAKE, C, q_batches, FAKE, C, FAKE, C, FAKE, C, None, None, 0, None, B, heads, Nq, Nk, d,
-                                                   1.0, None, 0, None) == -1
+        assert lib.ddpo_attention_fwd_x16(f16p, FAKE, C, q_batches, FAKE, C, FAKE, C, FAKE, C, None, None, 0, None, B, heads, Nq, Nk, d,
+                                          1.0, None, 0, None) == -1
         nb = lib.ddpo_attention_kv_images_bytes(B, heads, Nk, d)
-        assert lib.ddpo_attention_fwd_images_shared_q(f16p, FAKE, C, q_batches, FAKE, nb, FAKE, C, None, None, 0, None, B, heads, Nq, Nk, d, 1.0,
-                                                      None) == -1
+        assert lib.ddpo_attention_fwd_images(f16p, FAKE, C, q_batches, FAKE, nb, FAKE, C, None, None, 0, None, B, heads, Nq, Nk, d, 1.0,
+                                             None) == -1
 
 
 def test_shared_query_output_forms_are_exclusive():
@@ -79,5 +79,5 @@ def test_shared_query_output_forms_are_exclusive():
     B, heads, Nq, Nk, d = 4, 2, 64, 77, 40
     C = heads * d
     # fp32 rows AND planes at once, or neither
-    assert lib.ddpo_attention_fwd_x16_shared_q(0, FAKE, C, 2, FAKE, C, FAKE, C, FAKE, C, FAKE, FAKE, C, None, B, heads, Nq, Nk, d, 1.0, None, 0, None) == -1
-    assert lib.ddpo_attention_fwd_x16_shared_q(0, FAKE, C, 2, FAKE, C, FAKE, C, None, C, None, None, 0, None, B, heads, Nq, Nk, d, 1.0, None, 0, None) == -1
+    assert lib.ddpo_attention_fwd_x16(0, FAKE, C, 2, FAKE, C, FAKE, C, FAKE, C, FAKE, FAKE, C, None, B, heads, Nq, Nk, d, 1.0, None, 0, None) == -1
+    assert lib.ddpo_attention_fwd_x16(0, FAKE, C, 2, FAKE, C, FAKE, C, None, C, None, None, 0, None, B, heads, Nq, Nk, d, 1.0, None, 0, None) == -1

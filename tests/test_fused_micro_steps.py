@@ -1,4 +1,4 @@
-"""Fused PPO micro-steps (`train_steps_fused`, `ddpo_ddim_logprob_ppo_fwd_bwd_grouped`).
+"""Fused PPO micro-steps (`train_steps_fused`, `ddpo_ddim_logprob_ppo_fwd_bwd` with `group`).
 
 The reference runs the micro-steps of one accumulation window one at a time and sums their gradients
 (/root/reference/ddpo/training/policy_gradient.py:32-48; loop /root/reference/pipeline/policy_gradient.py:407-441).

@@ -25,7 +25,7 @@ Gates — none taken from the code under test:
           convolution gradients: 5e-5).
   f16mx   1e-3 everywhere: TOL of tests/test_gpu_train_parity.py (north_star), and the f16p gate of test_attention_bwd_bf16x3.
 Every case repeats the engine's backward with the cotangent times 2^-20 (a loss scale) against the SAME reference times 2^-20 — exact, and
-gradients are linear in the cotangent, so the same gates hold: the per-slab power-of-two scaling of dO in ddpo_attention_bwd_f16p and any
+gradients are linear in the cotangent, so the same gates hold: the per-slab power-of-two scaling of dO in ddpo_attention_bwd_x16 with f16p = 1 and any
 underflow of the bf16 split of small gradients, through a whole network.
 Measured values: profiles/r10_backward_budget.log."""
 import functools

@@ -216,8 +216,9 @@ def test_attention_bf16x3(datapath, B, heads, Nq, Nk, d, variant):
 @pytest.mark.parametrize("B,heads,Nq,Nk,d", [(2, 8, 64, 64, 8), (1, 8, 200, 77, 16), (2, 8, 1024, 1024, 40), (2, 8, 1024, 77, 40),
                                              (1, 8, 256, 256, 80), (1, 5, 130, 333, 64)])
 def test_attention_plane_emitting_output_is_the_split_of_the_fp32_output(datapath, B, heads, Nq, Nk, d, variant, monkeypatch):
-    """ABI v12 (ddpo_attention_fwd_*_po / *_images_po): the attention kernels write their result as bf16 hi / lo planes for a plane-fed to_out
-    projection.  The planes must be EXACTLY the split (hi = bf16(x), lo = bf16(x - hi)) of the fp32 tensor the plain entry points write — all
+    """The plane output form (o_hi / o_lo) of ddpo_attention_fwd_x16 / ddpo_attention_fwd_images: the attention kernels write their result as bf16
+    hi / lo planes for a plane-fed to_out projection.  The planes must be EXACTLY the split (hi = bf16(x), lo = bf16(x - hi)) of the fp32 tensor
+    the row form (o, ldo) of the same entry points writes — all
     three kernels (self-staging, packed images, LDS-DMA), workspace and image forms, row-major and k-blocked plane storage."""
     L.DATAPATH = variant
     g = torch.Generator().manual_seed(Nq + Nk + d)
@@ -233,11 +234,11 @@ def test_attention_plane_emitting_output_is_the_split_of_the_fp32_output(datapat
         for got in (L.attention(q, k, v, B, heads, Nq, Nk, d, planes_out=True), L.attention_from_images(q, img, B, heads, Nq, Nk, d, planes_out=True)):
             assert got.kblocked == kblocked and got.fmt == 0
             assert torch.equal(got.hi, want.hi) and torch.equal(got.lo, want.lo)
-    # argument checks of the new entry points: no planes, misaligned planes, k-blocked planes without whole 32-channel blocks
-    lib = L.load()
-    fn = lib.ddpo_attention_fwd_f16p_po if variant == "f16mx" else lib.ddpo_attention_fwd_bf16x3_po
+    # argument checks of the plane form (o = NULL): no planes, misaligned planes, k-blocked planes without whole 32-channel blocks
+    fn = L.load().ddpo_attention_fwd_x16
     pl = L.Planes(B * Nq, C, DEV)
-    args = lambda hi, lo, ld: (L._p(q), C, L._p(k), C, L._p(v), C, hi, lo, ld, None, B, heads, Nq, Nk, d, float(d ** -0.5), None, 0, L._stream())
+    args = lambda hi, lo, ld: (int(variant == "f16mx"), L._p(q), C, B, L._p(k), C, L._p(v), C, None, 0, hi, lo, ld, None, B, heads, Nq, Nk, d,
+                               float(d ** -0.5), None, 0, L._stream())
     assert fn(*args(None, L._p(pl.lo), C)) == -1
     assert fn(*args(L._p(pl.hi), None, C)) == -1
     assert fn(*args(pl.hi.data_ptr() + 2, L._p(pl.lo), C)) == -1

@@ -3,7 +3,7 @@
 Under classifier-free guidance the two halves of the U-Net batch carry the same latents and timestep and differ in the text context only, which
 first enters at attn2 of down_blocks_0.attentions_0.  `UNet2DCondition.forward(cfg_dup=True)` runs everything in front of that point on one half.
 Two kernel features keep the shared half from being copied where it meets the per-half data:
-  * attention with a query batch period (`q_batches`, ddpo_attention_fwd_*_shared_q): batch b reads the queries of batch b % q_batches;
+  * attention with a query batch period (`q_batches`, ddpo_attention_fwd, _x16, _images): batch b reads the queries of batch b % q_batches;
   * GEMM / conv output stage with a residual row period (`res_rows`, ddpo_gemm_desc.res_rows): output row m adds residual row m % res_rows.
 Both only change WHERE an operand is read, so every comparison below is bit for bit (torch.equal) against the same entry point fed the
 explicitly duplicated operand."""

@@ -24,7 +24,7 @@ gpu = pytest.mark.gpu
 DEV = "cuda"
 
 # ------------------------------------------------------------------------------------------------ shape tables
-# ddpo_ddim_logprob_ppo_fwd_bwd_grouped: nv = ceil(chw / 4 / 1024); cluster kernel ppo_cluster_kernel<NV> for B <= 64 and nv <= 16 with
+# ddpo_ddim_logprob_ppo_fwd_bwd: nv = ceil(chw / 4 / 1024); cluster kernel ppo_cluster_kernel<NV> for B <= 64 and nv <= 16 with
 # NV the first of {1, 2, 4, 8, 12, 16} that holds nv, else ppo_fwd_bwd_kernel + ppo_info_kernel.  Rows: (B, group, chw, branch).
 PPO_CHW_TABLE = [
     (4, 4, 4, 1),                       # NV1, one float4: slices 1-3 of the four-workgroup cluster are empty
@@ -132,7 +132,7 @@ def _ppo_branch(B, chw, ladder=(1, 2, 4, 8, 12, 16), max_b=64):
 
 def test_ppo_tables_cover_every_rung():
     """The branch noted beside each row of the PPO tables is the one the dispatch rule gives, and the tables reach every rung and both fall-backs.
-    IF YOU CHANGE THE LADDER (the PPO_LAUNCH chain, PPO_MAXB or the 1024-float4 tile of ddpo_ddim_logprob_ppo_fwd_bwd_grouped in
+    IF YOU CHANGE THE LADDER (the PPO_LAUNCH chain, PPO_MAXB or the 1024-float4 tile of ddpo_ddim_logprob_ppo_fwd_bwd in
     ddpo_amd/csrc/elementwise.hip): move the `chw` rows of PPO_CHW_TABLE / PPO_BIT_CHW / PPO_REARM so that every rung still has a row whose LAST
     tile is ragged (one float4), plus a full one for the first and the last rung, and keep B at PPO_MAXB / PPO_MAXB + 1 in PPO_B_TABLE."""
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ddpo_amd", "csrc", "elementwise.hip")).read()

@@ -161,7 +161,7 @@ def _check(family, ocfg, pred, hw, b, ts, ctx_dim, T, datapath, dtype, seed, fus
                 assert e < TOL, (k, e)
             # the whole gradient VECTOR, not only its length.  2e-3 on the fp32-class three-pass datapaths and at full size on every datapath; the
             # toy nets under f16mx (random weights, t = 21: the worst amplifier in the suite) get 3e-3 — its attention backward carries single f16
-            # terms (dO, P, dS: 2^-12 each, ddpo_attention_bwd_f16p): measured 2.1e-3 there; the SD-size margins are in profiles/r04_parity_margins.log
+            # terms (dO, P, dS: 2^-12 each, ddpo_attention_bwd_x16 with f16p = 1): measured 2.1e-3 there; the SD-size margins are in profiles/r04_parity_margins.log
             assert e_dir < (3 * TOL if (datapath == "f16mx" and hw < 64) else 2 * TOL)
             return info, kl_slack
 

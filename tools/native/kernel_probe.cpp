@@ -683,12 +683,11 @@ static void run_attn(int B, int heads, int Nq, int Nk, int d, int iters, bool f1
   float* o = (float*)dalloc((size_t)B * Nq * C * 4);
   const float scale = 1.0f / sqrtf((float)d);
   const bool bf = (d == 8 || d == 16 || d == 40 || d == 64 || d == 80);
-  const size_t wsb = bf ? ddpo_attention_fwd_bf16x3_ws_bytes(B, heads, Nk, d) : 0;
+  const size_t wsb = bf ? ddpo_attention_fwd_x16_ws_bytes(B, heads, Nk, d) : 0;
   void* ws = wsb ? dalloc(wsb) : nullptr;
   const float ms = time_ms(iters, [&] {
-    if (bf && f16p) ABI_OK(ddpo_attention_fwd_f16p(q.p, C, k.p, C, v.p, C, o, C, nullptr, B, heads, Nq, Nk, d, scale, ws, wsb, nullptr));
-    else if (bf) ABI_OK(ddpo_attention_fwd_bf16x3(q.p, C, k.p, C, v.p, C, o, C, nullptr, B, heads, Nq, Nk, d, scale, ws, wsb, nullptr));
-    else ABI_OK(ddpo_attention_fwd(q.p, C, k.p, C, v.p, C, o, C, nullptr, B, heads, Nq, Nk, d, scale, nullptr));
+    if (bf) ABI_OK(ddpo_attention_fwd_x16(f16p, q.p, C, B, k.p, C, v.p, C, o, C, nullptr, nullptr, 0, nullptr, B, heads, Nq, Nk, d, scale, ws, wsb, nullptr));
+    else ABI_OK(ddpo_attention_fwd(q.p, C, B, k.p, C, v.p, C, o, C, nullptr, B, heads, Nq, Nk, d, scale, nullptr));
   });
   double max_err = 0.0;
   std::vector<double> p(Nk);
@@ -765,7 +764,7 @@ static int probe_ppo() {
   for (int i = 0; i < B; ++i) old_h[i] = lp0_h[i] + doff[i];
   HIP_OK(hipMemcpy(d_old, old_h.data(), B * 4, hipMemcpyHostToDevice));
   float *dc = (float*)dalloc((size_t)B * chw * 4), *du = (float*)dalloc((size_t)B * chw * 4), *per = (float*)dalloc(B * 16), *info = (float*)dalloc(k * 12);
-  ABI_OK(ddpo_ddim_logprob_ppo_fwd_bwd_grouped(ec.p, eu.p, x.p, xn, d_ts, d_old, d_adv, g, clip, 1, &c, dc, du, per, info, B, b, chw, nullptr));
+  ABI_OK(ddpo_ddim_logprob_ppo_fwd_bwd(ec.p, eu.p, x.p, xn, d_ts, d_old, d_adv, g, clip, 1, &c, dc, du, per, info, B, b, chw, nullptr));
   std::vector<float> dc_h((size_t)B * chw), du_h((size_t)B * chw), per_h(B * 4), info_h(k * 3), xn_h((size_t)B * chw);
   HIP_OK(hipMemcpy(dc_h.data(), dc, dc_h.size() * 4, hipMemcpyDeviceToHost));
   HIP_OK(hipMemcpy(du_h.data(), du, du_h.size() * 4, hipMemcpyDeviceToHost));
@@ -778,7 +777,7 @@ static int probe_ppo() {
     const int64_t off = (int64_t)j * b * chw;
     float *dc2 = (float*)dalloc((size_t)b * chw * 4), *du2 = (float*)dalloc((size_t)b * chw * 4), *per2 = (float*)dalloc(b * 16), *info2 = (float*)dalloc(12);
     ABI_OK(ddpo_ddim_logprob_ppo_fwd_bwd(ec.p + off, eu.p + off, x.p + off, xn + off, d_ts + j * b, d_old + j * b, d_adv + j * b, g, clip, 1, &c,
-                                         dc2, du2, per2, info2, b, chw, nullptr));
+                                         dc2, du2, per2, info2, b, b, chw, nullptr));
     std::vector<float> a((size_t)b * chw), bb((size_t)b * chw), p2(b * 4), i2(3);
     HIP_OK(hipMemcpy(a.data(), dc2, a.size() * 4, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(bb.data(), du2, bb.size() * 4, hipMemcpyDeviceToHost));
