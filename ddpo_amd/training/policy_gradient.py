@@ -12,11 +12,14 @@ MI355X design notes
     `lax.pmean(grad)` of the reference (:141, every micro-step) becomes ONE RCCL all-reduce of that buffer per
     optimizer update — mean-over-ranks and sum-over-steps commute.
   * the update itself is one fused kernel: 1/(n_acc+1) scaling, global-norm clip, AdamW with bf16 first moment.
+  * `--optimizer adafactor` (the table's second row, optax.adafactor(lr, weight_decay_rate)) is five launches over the same flat
+    buffers, with a state of 1.9 M floats instead of 6 B/param (lib_optim.py).
 """
 import numpy as np
 import torch
 
 from .. import lib as L
+from .. import lib_optim as LO
 
 ADV_CLIP_MAX = 10.0
 # PPO micro-steps per U-Net forward/backward in the entrypoint's training loop (train_steps_fused).  16 turns the U-Net batch of 4
@@ -43,6 +46,8 @@ def train_fuse_default(unet_rows_per_micro_step=None, latent_pixels=None):
 class AdamWConfig:
     """Hyper-parameters of pipeline/policy_gradient.py:130-150 (defaults = config/base.py `pg`)."""
 
+    name = "adamw"
+
     def __init__(self, learning_rate=1e-5, b1=0.9, b2=0.999, eps=1e-8, weight_decay=1e-4, max_grad_norm=1.0,
                  mu_decay_in_bf16=True):
         self.learning_rate, self.b1, self.b2, self.eps = learning_rate, b1, b2, eps
@@ -50,15 +55,27 @@ class AdamWConfig:
         self.mu_decay_in_bf16 = mu_decay_in_bf16
 
 
+class AdafactorConfig:
+    """optax.adafactor(learning_rate, weight_decay_rate=weight_decay) behind clip_by_global_norm(max_grad_norm): the reference passes these two
+    arguments and leaves the rest at optax's defaults (lib_optim.py).  min_dim_size_to_factor is optax's 128; small tests lower it."""
+
+    name = "adafactor"
+
+    def __init__(self, learning_rate=1e-5, weight_decay=1e-4, max_grad_norm=1.0, min_dim_size_to_factor=LO.MIN_DIM_SIZE_TO_FACTOR):
+        self.learning_rate, self.weight_decay, self.max_grad_norm = learning_rate, weight_decay, max_grad_norm
+        self.min_dim_size_to_factor = min_dim_size_to_factor
+
+
 class AccumulatingTrainState:
     """TrainState that accumulates gradients over several steps before applying them (reference :13-57).
 
     fields: step, params (the U-Net's flat ParamStore), opt_state {count, mu (bf16), nu (fp32)}, grad_acc (flat), n_acc.
+    With an AdafactorConfig opt_state is {count, v}: one flat fp32 buffer laid out by `plan` (lib_optim.AdafactorPlan).
     LoRA mode (`lora`: a models/lora.LoraStore attached to the U-Net): the optimizer state, the gradient buffer and the update are the
     adapters' (`trainable` = lora.params); after each update lora.merge() rewrites the adapted U-Net weights and repacks only those.
     """
 
-    def __init__(self, unet, tx: AdamWConfig, process_group=None, lora=None):
+    def __init__(self, unet, tx, process_group=None, lora=None):
         self.unet = unet
         self.apply_fn = unet.forward
         self.params = unet.params
@@ -72,8 +89,12 @@ class AccumulatingTrainState:
         self.grad_acc = unet.ensure_grads() if lora is None else lora.grads
         n = self.trainable.flat.numel()
         dev = self.trainable.flat.device
-        self.opt_state = {"count": 0, "mu": torch.zeros(n, dtype=torch.bfloat16, device=dev),
-                          "nu": torch.zeros(n, dtype=torch.float32, device=dev)}
+        if isinstance(tx, AdafactorConfig):
+            self.plan = LO.AdafactorPlan.for_store(self.trainable, tx.min_dim_size_to_factor).to(dev)
+            self.opt_state = {"count": 0, "v": self.plan.new_state()}
+        else:
+            self.opt_state = {"count": 0, "mu": torch.zeros(n, dtype=torch.bfloat16, device=dev),
+                              "nu": torch.zeros(n, dtype=torch.float32, device=dev)}
         self._sqnorm = torch.zeros(1, dtype=torch.float64, device=dev)
         self.process_group = process_group
         self.last_grad_norm = None
@@ -118,9 +139,13 @@ class AccumulatingTrainState:
         L.grad_sqnorm(g, self._sqnorm)
         t = self.opt_state["count"] + 1
         tx = self.tx
-        L.adamw_bf16mu_step(self.trainable.flat, g, self.opt_state["mu"], self.opt_state["nu"], self._sqnorm, inv,
-                            tx.learning_rate, tx.b1, tx.b2, tx.eps, tx.weight_decay, tx.max_grad_norm, t,
-                            mu_decay_in_bf16=tx.mu_decay_in_bf16, zero_grad=True)
+        if isinstance(tx, AdafactorConfig):
+            LO.adafactor_step(self.trainable.flat, g, self.opt_state["v"], self.plan, self._sqnorm, inv, tx.learning_rate,
+                              self.opt_state["count"], tx.weight_decay, tx.max_grad_norm, zero_grad=True)
+        else:
+            L.adamw_bf16mu_step(self.trainable.flat, g, self.opt_state["mu"], self.opt_state["nu"], self._sqnorm, inv,
+                                tx.learning_rate, tx.b1, tx.b2, tx.eps, tx.weight_decay, tx.max_grad_norm, t,
+                                mu_decay_in_bf16=tx.mu_decay_in_bf16, zero_grad=True)
         self.last_grad_norm = torch.sqrt(self._sqnorm.clone()) * inv       # device scalar, no host sync
         if self.lora is not None:
             self.lora.merge()                                              # W' = W0 + s A B; repack of the adapted tensors only

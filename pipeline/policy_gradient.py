@@ -6,7 +6,7 @@
 
 Per epoch: sample DDIM trajectories (HIP sampler) -> decode -> reward callbacks (async thread) -> all-gather rewards
 -> advantages (per-prompt tracker or global normalisation) -> shuffle over batch and, per sample, over time ->
-PPO-clip updates on the stored log-probs (HIP forward/backward, one RCCL all-reduce + fused AdamW per update)
+PPO-clip updates on the stored log-probs (HIP forward/backward, one RCCL all-reduce + fused AdamW or Adafactor per update)
 -> .npy run artefacts, checkpoints, reward curve.
 
 Mirrors /root/reference/pipeline/policy_gradient.py:45-480 step for step (same flags, same artefacts under
@@ -35,7 +35,7 @@ import torch
 from ddpo_amd import training, utils
 from ddpo_amd.training import distributed as D
 from ddpo_amd.training.dp import DataParallel
-from ddpo_amd.training.policy_gradient import (AccumulatingTrainState, AdamWConfig, train_fuse_default, train_step,
+from ddpo_amd.training.policy_gradient import (AccumulatingTrainState, AdafactorConfig, AdamWConfig, train_fuse_default, train_step,
                                                train_steps_fused)
 from ddpo_amd.utils import prng
 from ddpo_amd.utils.serialization import load_params_file, load_resume, load_unet, mark_synthetic, save_checkpoint, save_rank_resume
@@ -58,6 +58,30 @@ class Parser(utils.Parser):
 def lora_seed(args, dp):
     """Seed of the LoRA adapters' initialisation: the configured seed without the per-process offset parser.set_seed added (the same on every rank)."""
     return int(args.seed) - int(dp.seed_process_index)
+
+
+def make_optimizer(args):
+    """The reference's optimizer table (/root/reference/pipeline/policy_gradient.py:132-145): `adamw` or `adafactor`, each behind
+    clip_by_global_norm(max_grad_norm)."""
+    if args.optimizer == "adamw":
+        # optax.adamw(mu_dtype=bfloat16) forms `b1 * mu` with mu in bf16: JAX's weak-type promotion keeps the ARRAY's dtype, so the product
+        # (and b1 itself, 0.9 -> 0.8984375) is rounded to bf16 before the f32 `(1 - b1) * g` is added — the default here and in
+        # oracle/optim.py.  `--mu_decay_in_bf16 False` / DDPO_MU_DECAY_IN_BF16=0 selects the all-f32 reading (decay in f32, one rounding at
+        # the store) should a real optax run disagree.
+        return AdamWConfig(learning_rate=args.learning_rate, b1=args.beta1, b2=args.beta2, eps=args.epsilon, weight_decay=args.weight_decay,
+                           max_grad_norm=args.max_grad_norm,
+                           mu_decay_in_bf16=_flag(getattr(args, "mu_decay_in_bf16", None), os.environ.get("DDPO_MU_DECAY_IN_BF16", "1") != "0"))
+    if args.optimizer == "adafactor":
+        return AdafactorConfig(learning_rate=args.learning_rate, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
+    raise NotImplementedError(f"unknown optimizer {args.optimizer!r}: the reference's table has adamw and adafactor")
+
+
+def check_resume_optimizer(rs, tx, where):
+    """A resume bundle carries the moments of the optimizer that wrote it (bundles from before the field existed are AdamW's)."""
+    wrote = rs.get("optimizer", "adamw")
+    if wrote != tx.name:
+        raise SystemExit(f"DDPO_RESUME: epoch {rs['epoch']} of {where} was trained with --optimizer {wrote}; "
+                         f"it cannot continue with --optimizer {tx.name}")
 
 
 def main(argv=None):
@@ -106,15 +130,14 @@ def main(argv=None):
                                  cache=args.cache, device=dev, seed=0)
     with open(f"{localpath}/args.json", "w") as f:      # after loading: says which weights the run really started from
         json.dump(dict(args._dict, synthetic_weights=bool(pipeline.synthetic_weights), weights_source=pipeline.weights_source,
-                       param_dtype=pipeline.param_dtype, datapath=L.DATAPATH), f, indent=4, default=str)
+                       param_dtype=pipeline.param_dtype, datapath=L.DATAPATH, optimizer=args.optimizer), f, indent=4, default=str)
     pipeline.safety_checker = None
     unet, vae = pipeline.unet, pipeline.vae
     noise_scheduler_state = pipeline.scheduler.set_timesteps(params["scheduler"], num_inference_steps=args.n_inference_steps)
 
     # ------------------------------- optimizer --------------------------------#
     print("initializing train state...")
-    if args.optimizer != "adamw":
-        raise NotImplementedError("only the adamw optimizer of the reference configs is implemented")
+    tx = make_optimizer(args)
     lora = None
     if args.lora_rank:
         # adapters on the attention projections; the pretrained weights are W0.  Drawn on the host from the BASE seed (args.seed carries the
@@ -122,17 +145,7 @@ def main(argv=None):
         from ddpo_amd.models.lora import LoraStore
         lora = LoraStore(unet, args.lora_rank, alpha=args.lora_alpha, seed=lora_seed(args, dp))
         print(f"[ policy_gradient ] LoRA rank {lora.rank}, scale {lora.scale:g}: {lora.n_params} trainable parameters on {len(lora.targets)} layers")
-    state = AccumulatingTrainState(unet, AdamWConfig(learning_rate=args.learning_rate, b1=args.beta1, b2=args.beta2,
-                                                     eps=args.epsilon, weight_decay=args.weight_decay,
-                                                     max_grad_norm=args.max_grad_norm,
-                                                     # optax.adamw(mu_dtype=bfloat16) forms `b1 * mu` with mu in bf16: JAX's weak-type
-                                                     # promotion keeps the ARRAY's dtype, so the product (and b1 itself, 0.9 -> 0.8984375) is
-                                                     # rounded to bf16 before the f32 `(1 - b1) * g` is added — the default here and in
-                                                     # oracle/optim.py.  `--mu_decay_in_bf16 False` / DDPO_MU_DECAY_IN_BF16=0 selects the all-f32
-                                                     # reading (decay in f32, one rounding at the store) should a real optax run disagree.
-                                                     mu_decay_in_bf16=_flag(getattr(args, "mu_decay_in_bf16", None),
-                                                                            os.environ.get("DDPO_MU_DECAY_IN_BF16", "1") != "0")),
-                                   lora=lora)
+    state = AccumulatingTrainState(unet, tx, lora=lora)
     sampling_scheduler_params = params["scheduler"]
 
     timer = utils.Timer()
@@ -160,9 +173,10 @@ def main(argv=None):
     t_start = time.time()
     start_epoch = 0
     if os.environ.get("DDPO_RESUME"):
-        # not in the reference (it never loads a policy-gradient run): continue from <run>/checkpoints — parameters, AdamW moments
+        # not in the reference (it never loads a policy-gradient run): continue from <run>/checkpoints — parameters, optimizer moments
         # and count, the sampling key, the host RNG streams of this rank, the per-prompt tracker and the reward history
         rs = load_resume(os.environ["DDPO_RESUME"], worker_id, os.environ.get("DDPO_RESUME_EPOCH"))
+        check_resume_optimizer(rs, tx, os.environ["DDPO_RESUME"])
         if lora is not None:
             # LoRA: the base weights are the pretrained ones already loaded (W0); the bundle carries the adapters
             if "lora_params" not in rs:
@@ -181,8 +195,9 @@ def main(argv=None):
             load_params_file(state.params, rs["params_path"])
             if L.DATAPATH != "fp32":
                 state.params.pack_bf16()
-        state.opt_state["mu"].copy_(rs["mu"])
-        state.opt_state["nu"].copy_(rs["nu"])
+        for k in state.opt_state:
+            if k != "count":                   # AdamW: mu, nu; Adafactor: v
+                state.opt_state[k].copy_(rs[k])
         state.opt_state["count"] = state.step = int(rs["opt_count"])
         if "sample_rng" in rs:
             sample_rng = rs["sample_rng"]
@@ -323,8 +338,8 @@ def main(argv=None):
             save_rank_resume(os.path.join(args.savepath, "checkpoints"), epoch, worker_id,
                              {"sample_rng": sample_rng, "py_random": random.getstate(), "np_random": np.random.get_state()})
             if worker_id == 0:
-                resume = {"epoch": epoch, "opt_count": state.opt_state["count"], "mu": state.opt_state["mu"].cpu(),
-                          "nu": state.opt_state["nu"].cpu(), "sample_rng": sample_rng,
+                resume = {"epoch": epoch, "opt_count": state.opt_state["count"], "optimizer": tx.name,
+                          **{k: v.cpu() for k, v in state.opt_state.items() if k != "count"}, "sample_rng": sample_rng,
                           "tracker": None if per_prompt_stats is None else per_prompt_stats.state_dict(),
                           "mean_rewards": list(mean_rewards), "std_rewards": list(std_rewards), "wall": list(wall)}
                 if lora is not None:           # adapters only (diffusers attention-processor keys) + the resume bundle
