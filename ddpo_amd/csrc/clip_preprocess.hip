@@ -13,8 +13,6 @@
 // rows their kernels share (about support / p of the image); nothing else is read twice from HBM.
 #include "common.h"
 #include "clip_preprocess_core.h"
-#include <algorithm>
-#include <vector>
 
 namespace {
 
@@ -23,16 +21,11 @@ constexpr int CP_TB = 512;
 struct CpArgs {
   const void* images;
   int N, H, W, rh, rw, top, left, size, patch;
-  const int32_t *hcoef, *hbounds;
-  int hk;
-  const int32_t *vcoef, *vbounds;
-  int vk, rows;
+  CpAxes ax;
   const float* norm;
   float* out;
   int ld;
 };
-
-__host__ __device__ inline int cp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // Everything the device and the host entry refuse alike (pointers and the LDS rule are checked by the callers)
 bool cp_geometry_ok(const CpArgs& a) {
@@ -40,7 +33,7 @@ bool cp_geometry_ok(const CpArgs& a) {
   if (a.patch > 1024 || a.size > (1 << 15) || a.H > (1 << 24) || a.W > (1 << 24)) return false;
   if (a.ld < 3 * a.patch * a.patch || (a.ld & 3)) return false;
   if (a.top < 0 || a.left < 0 || a.top > a.rh - a.size || a.left > a.rw - a.size) return false;      // crop window inside the resized image
-  if (a.hk < 1 || a.vk < 1) return false;
+  if (a.ax.hk < 1 || a.ax.vk < 1) return false;
   if ((int64_t)a.N * (a.size / a.patch) > 0x7fffffff) return false;
   return true;
 }
@@ -51,35 +44,15 @@ __global__ __launch_bounds__(CP_TB) void clip_preprocess_kernel(const CpArgs a) 
   const int t = threadIdx.x;
   const int g = a.size / a.patch;
   const int n = blockIdx.x / g, gy = blockIdx.x % g;
-  const int hrow = (int)cp_row_bytes(a.size), srow = (int)cp_row_bytes(a.W);
+  const int hrow = (int)iu_row_bytes(a.size), srow = (int)iu_row_bytes(a.W);
   uint8_t* s_h = reinterpret_cast<uint8_t*>(smem);                          // [rows][hrow]: horizontally resampled bytes
-  uint8_t* s_in = s_h + (size_t)a.rows * hrow;                              // [CP_STAGE_ROWS][srow]: input rows as bytes
+  uint8_t* s_in = s_h + (size_t)a.ax.rows * hrow;                              // [CP_STAGE_ROWS][srow]: input rows as bytes
   float* s_norm = reinterpret_cast<float*>(s_in + (size_t)CP_STAGE_ROWS * srow);
   for (int i = t; i < 256 * 3; i += CP_TB) s_norm[i] = a.norm[i];
 
-  // input rows [y_lo, y_lo + nrows) feed the output rows Y0 .. Y0 + p - 1 (the first bound of a table never decreases).  Bounds are clamped to
-  // the image and to the LDS the launch was given, so a bad table cannot make the kernel read or write outside its arguments.
-  const int Y0 = a.top + gy * a.patch;
-  int y_lo = a.vbounds[2 * Y0], y_hi = y_lo;
-  for (int r = 0; r < a.patch; ++r) y_hi = max(y_hi, a.vbounds[2 * (Y0 + r)] + a.vbounds[2 * (Y0 + r) + 1]);
-  y_lo = cp_clampi(y_lo, 0, a.H);
-  const int nrows = cp_clampi(min(y_hi, a.H) - y_lo, 0, a.rows);
-  const int s3 = a.size * 3, w3 = a.W * 3;
-
-  for (int r0 = 0; r0 < nrows; r0 += CP_STAGE_ROWS) {
-    const int nr = min(CP_STAGE_ROWS, nrows - r0);
-    const size_t row0 = ((size_t)n * a.H + (size_t)(y_lo + r0)) * w3;      // element index of the first staged row
-    cp_stage_rows<F32, VEC, CP_TB>(a.images, row0, nr, w3, s_in, srow, t);
-    __syncthreads();
-    for (int i = t; i < nr * s3; i += CP_TB) {
-      const int r = i / s3, rem = i - r * s3, xo = rem / 3, c = rem - xo * 3;
-      const int X = a.left + xo;
-      const int xmin = cp_clampi(a.hbounds[2 * X], 0, a.W);
-      const int cnt = cp_clampi(a.hbounds[2 * X + 1], 0, min(a.hk, a.W - xmin));
-      s_h[(r0 + r) * hrow + rem] = (uint8_t)cp_taps(s_in + r * srow + xmin * 3 + c, 3, a.hcoef + (size_t)X * a.hk, cnt);
-    }
-    __syncthreads();
-  }
+  const int Y0 = a.top + gy * a.patch;                                      // the band: the p output rows of this patch row, cropped columns only
+  const CpBand band = cp_band_rows(a.ax, Y0, a.patch, a.H);
+  cp_horizontal_pass<F32, VEC, CP_TB>(a.ax, a.images, n, a.H, a.W, band, a.left, a.size, s_h, hrow, s_in, srow, t);
   __syncthreads();                                                          // s_norm, also when no row was staged
 
   const int ld4 = a.ld >> 2, pp = a.patch * a.patch, kp = 3 * pp;
@@ -92,11 +65,7 @@ __global__ __launch_bounds__(CP_TB) void clip_preprocess_kernel(const CpArgs a) 
       float val = 0.0f;                                                     // pad columns
       if (col < kp) {
         const int c = col / pp, rem = col - c * pp, ky = rem / a.patch, kx = rem - ky * a.patch;
-        const int Y = Y0 + ky;
-        const int ymin = cp_clampi(a.vbounds[2 * Y] - y_lo, 0, nrows);
-        const int cnt = cp_clampi(a.vbounds[2 * Y + 1], 0, min(a.vk, nrows - ymin));
-        const int b = cp_taps(s_h + ymin * hrow + (gx * a.patch + kx) * 3 + c, hrow, a.vcoef + (size_t)Y * a.vk, cnt);
-        val = s_norm[b * 3 + c];
+        val = s_norm[cp_vertical_byte(a.ax, band, s_h, hrow, Y0 + ky, (gx * a.patch + kx) * 3 + c) * 3 + c];
       }
       v[j] = val;
     }
@@ -105,33 +74,23 @@ __global__ __launch_bounds__(CP_TB) void clip_preprocess_kernel(const CpArgs a) 
   }
 }
 
-template <bool F32, bool VEC>
-int cp_launch(const CpArgs& a, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&clip_preprocess_kernel<F32, VEC>), hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS_LIMIT);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((clip_preprocess_kernel<F32, VEC>), dim3((unsigned)(a.N * (a.size / a.patch))), dim3(CP_TB), lds, s, a);
-  DDPO_LAUNCH_CHECK();
-  return DDPO_OK;
-}
-
 }  // namespace
 
 extern "C" int ddpo_clip_preprocess(const void* images, int is_float32, int N, int H, int W, int rh, int rw, int top, int left, int size, int patch,
                                     const int32_t* hcoef, const int32_t* hbounds, int hksize, const int32_t* vcoef, const int32_t* vbounds,
                                     int vksize, int rows, const float* norm, float* out, int ld, void* stream) {
   if (!images || !hcoef || !hbounds || !vcoef || !vbounds || !norm || !out) return DDPO_EINVAL;
-  const CpArgs a{images, N, H, W, rh, rw, top, left, size, patch, hcoef, hbounds, hksize, vcoef, vbounds, vksize, rows, norm, out, ld};
+  const CpArgs a{images, N, H, W, rh, rw, top, left, size, patch, {hcoef, hbounds, hksize, vcoef, vbounds, vksize, rows}, norm, out, ld};
   if (!cp_geometry_ok(a) || rows < 1 || rows > H) return DDPO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(out) & 15) || (is_float32 && (reinterpret_cast<uintptr_t>(images) & 3))) return DDPO_EINVAL;
-  const size_t lds = cp_lds_bytes(rows, size, W);
+  if ((reinterpret_cast<uintptr_t>(out) & 15) || iu_misaligned(images, is_float32)) return DDPO_EINVAL;
+  const size_t lds = cp_lds_bytes(rows, size, W, true);
   if (lds > CP_LDS_LIMIT) return DDPO_EINVAL;                               // the LDS rule
-  const bool vec = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(images) & (is_float32 ? 15 : 3)) == 0;
-  hipStream_t s = as_stream(stream);
-  if (is_float32) return vec ? cp_launch<true, true>(a, lds, s) : cp_launch<true, false>(a, lds, s);
-  return vec ? cp_launch<false, true>(a, lds, s) : cp_launch<false, false>(a, lds, s);
+  iu_dispatch(is_float32, iu_vec_ok(images, is_float32, W), [&](auto F32, auto VEC) {
+    iu_large_lds<&clip_preprocess_kernel<F32(), VEC()>>(CP_LDS_LIMIT);
+    hipLaunchKernelGGL((clip_preprocess_kernel<F32(), VEC()>), dim3((unsigned)(N * (size / patch))), dim3(CP_TB), lds, as_stream(stream), a);
+  });
+  DDPO_LAUNCH_CHECK();
+  return DDPO_OK;
 }
 
 // Serial host path over the same functions (no GPU involved): what the kernel is held to, and what is held to Pillow.  The whole cropped window is
@@ -141,37 +100,16 @@ extern "C" int ddpo_clip_preprocess_host(const void* images, int is_float32, int
                                          int patch, const int32_t* hcoef, const int32_t* hbounds, int hksize, const int32_t* vcoef,
                                          const int32_t* vbounds, int vksize, const float* norm, float* out_host, int ld, uint8_t* resized_out_host) {
   if (!images || !hcoef || !hbounds || !vcoef || !vbounds || !norm || !out_host) return DDPO_EINVAL;
-  const CpArgs a{images, N, H, W, rh, rw, top, left, size, patch, hcoef, hbounds, hksize, vcoef, vbounds, vksize, 0, norm, out_host, ld};
+  const CpArgs a{images, N, H, W, rh, rw, top, left, size, patch, {hcoef, hbounds, hksize, vcoef, vbounds, vksize, 0}, norm, out_host, ld};
   if (!cp_geometry_ok(a)) return DDPO_EINVAL;
-  for (int X = left; X < left + size; ++X)
-    if (hbounds[2 * X] < 0 || hbounds[2 * X + 1] < 0 || hbounds[2 * X + 1] > hksize || hbounds[2 * X] > W - hbounds[2 * X + 1]) return DDPO_EINVAL;
-  for (int Y = top; Y < top + size; ++Y)
-    if (vbounds[2 * Y] < 0 || vbounds[2 * Y + 1] < 0 || vbounds[2 * Y + 1] > vksize || vbounds[2 * Y] > H - vbounds[2 * Y + 1] ||
-        (Y > top && vbounds[2 * Y] < vbounds[2 * (Y - 1)]))
-      return DDPO_EINVAL;
-  const int g = size / patch, pp = patch * patch, s3 = size * 3, w3 = W * 3;
-  int rows = 1, y_hi = 0;
-  for (int gy = 0; gy < g; ++gy) {
-    int hi = 0;
-    for (int r = 0; r < patch; ++r) hi = std::max(hi, vbounds[2 * (top + gy * patch + r)] + vbounds[2 * (top + gy * patch + r) + 1]);
-    rows = std::max(rows, hi - vbounds[2 * (top + gy * patch)]);
-    y_hi = std::max(y_hi, hi);
-  }
-  if (cp_lds_bytes(rows, size, W) > CP_LDS_LIMIT) return DDPO_EINVAL;       // the LDS rule: the same domain as the device entry
-  const int y_lo = vbounds[2 * top];
-  std::vector<uint8_t> in_row((size_t)w3), hbuf((size_t)std::max(y_hi - y_lo, 1) * s3);
+  if (!cp_axis_ok(hbounds, hksize, left, size, W, false) || !cp_axis_ok(vbounds, vksize, top, size, H, true)) return DDPO_EINVAL;
+  int y_hi;
+  const int rows = cp_band_max_rows(vbounds, top, size, patch, y_hi);
+  if (cp_lds_bytes(rows, size, W, true) > CP_LDS_LIMIT) return DDPO_EINVAL; // the LDS rule: the same domain as the device entry
+  const int g = size / patch, pp = patch * patch, s3 = size * 3, y_lo = vbounds[2 * top];
+  std::vector<uint8_t> hbuf((size_t)std::max(y_hi - y_lo, 1) * s3);
   for (int n = 0; n < N; ++n) {
-    for (int y = y_lo; y < y_hi; ++y) {
-      const size_t src = ((size_t)n * H + y) * w3;
-      for (int e = 0; e < w3; ++e)
-        in_row[e] = is_float32 ? (uint8_t)cp_float_to_u8(static_cast<const float*>(images)[src + e]) : static_cast<const uint8_t*>(images)[src + e];
-      for (int xo = 0; xo < size; ++xo)
-        for (int c = 0; c < 3; ++c) {
-          const int X = left + xo;
-          hbuf[(size_t)(y - y_lo) * s3 + xo * 3 + c] =
-              (uint8_t)cp_taps(in_row.data() + hbounds[2 * X] * 3 + c, 3, hcoef + (size_t)X * hksize, hbounds[2 * X + 1]);
-        }
-    }
+    cp_horizontal_host(a.ax, images, is_float32, n, H, W, y_lo, y_hi, left, size, hbuf.data());
     for (int yo = 0; yo < size; ++yo)
       for (int xo = 0; xo < size; ++xo)
         for (int c = 0; c < 3; ++c) {

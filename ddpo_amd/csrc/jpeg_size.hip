@@ -64,7 +64,7 @@ __global__ __launch_bounds__(TB) void jq_transform(const void* __restrict__ imag
     int R, G, B;
     if (F32) {
       const float* f = static_cast<const float*>(images) + p;
-      R = jq_float_to_u8(f[0]), G = jq_float_to_u8(f[1]), B = jq_float_to_u8(f[2]);
+      R = iu_float_to_u8(f[0]), G = iu_float_to_u8(f[1]), B = iu_float_to_u8(f[2]);
     } else {
       const uint8_t* u = static_cast<const uint8_t*>(images) + p;
       R = u[0], G = u[1], B = u[2];
@@ -275,7 +275,7 @@ struct JqBuffers {
 int jq_launch_streams(const void* images, int is_float32, int N, int H, int W, int quality, void* workspace, size_t workspace_bytes, hipStream_t s,
                       JqLayout& l, JqBuffers& b) {
   if (!images || !workspace || quality < 1 || quality > 100 || !jq_layout(N, H, W, l)) return DDPO_EINVAL;
-  if (workspace_bytes < l.bytes || (reinterpret_cast<uintptr_t>(workspace) & 15) || (is_float32 && (reinterpret_cast<uintptr_t>(images) & 3)))
+  if (workspace_bytes < l.bytes || (reinterpret_cast<uintptr_t>(workspace) & 15) || iu_misaligned(images, is_float32))
     return DDPO_EINVAL;
   char* ws = static_cast<char*>(workspace);
   b.coef = reinterpret_cast<int16_t*>(ws + l.coef);
@@ -287,10 +287,7 @@ int jq_launch_streams(const void* images, int is_float32, int N, int H, int W, i
   const size_t nblk_all = (size_t)nblk * N;
   if (hipMemsetAsync(b.bitbuf, 0, l.words_per_image * N * sizeof(uint32_t), s) != hipSuccess) return DDPO_ELAUNCH;
   const dim3 tgrid((unsigned)((size_t)N * mh * ((mw + MCUS - 1) / MCUS)));
-  if (is_float32)
-    hipLaunchKernelGGL(jq_transform<true>, tgrid, dim3(TB), 0, s, images, H, W, quality, b.coef, b.acbits);
-  else
-    hipLaunchKernelGGL(jq_transform<false>, tgrid, dim3(TB), 0, s, images, H, W, quality, b.coef, b.acbits);
+  iu_dispatch(is_float32, [&](auto F32) { hipLaunchKernelGGL(jq_transform<F32()>, tgrid, dim3(TB), 0, s, images, H, W, quality, b.coef, b.acbits); });
   DDPO_LAUNCH_CHECK();
   hipLaunchKernelGGL(jq_scan, dim3(N), dim3(SCAN_TB), 0, s, b.coef, b.acbits, nblk, b.offs, b.total);
   DDPO_LAUNCH_CHECK();

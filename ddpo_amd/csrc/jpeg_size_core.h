@@ -14,6 +14,7 @@
 #include <string.h>
 #include <vector>
 #include "../../include/ddpo_hip.h"
+#include "image_u8.h"
 
 #if defined(__HIPCC__)
 #define JQ_HD __host__ __device__ inline
@@ -85,12 +86,7 @@ constexpr uint8_t kJqNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 
                                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ---------------------------------------------------------------------------------------------------------------- pixels
-// float in [0, 1] -> uint8 the way the reward's reference does it: one fp32 multiply, truncation toward zero
-JQ_HD int jq_float_to_u8(float x) {
-  const int v = (int)(x * 255.0f);
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
+// float in [0, 1] -> uint8 the way the reward's reference does it, one fp32 multiply and truncation toward zero: iu_float_to_u8 of image_u8.h
 JQ_HD void jq_rgb_to_ycc(int r, int g, int b, int& y, int& cb, int& cr) {
   y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
   cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;

@@ -27,8 +27,6 @@ constexpr int SY_MAX_SLOTS = 64;                    // workgroups per image; lau
 constexpr int SY_TILE = 64;
 constexpr int SY_TILE_STRIDE = SY_TILE * 3 + 4;
 
-__host__ __device__ inline size_t sy_row_bytes(int W) { return ((size_t)W * 3 + 15) & ~(size_t)15; }
-
 // units of one image and the workgroups they are spread over
 inline int sy_units(int H, int mode) { return mode ? (H + 1) / 2 : H; }
 inline int sy_slots(int H, int mode) { return sy_units(H, mode) < SY_MAX_SLOTS ? sy_units(H, mode) : SY_MAX_SLOTS; }
@@ -36,35 +34,6 @@ inline int sy_slots(int H, int mode) { return sy_units(H, mode) < SY_MAX_SLOTS ?
 bool sy_stats_geometry_ok(int N, int H, int W, int mode) {
   if (N < 1 || H < 1 || W < 1 || W > SY_MAX_W || H > (1 << 24) || (mode != 0 && mode != 1)) return false;
   return (int64_t)N * sy_slots(H, mode) <= 0x7fffffff;
-}
-
-// `rows` rows of `count` elements, `src_stride` elements apart from element `src0` on, into bytes `dst_stride` apart.  VEC: count, src0 and
-// src_stride are multiples of 4, dst and dst_stride too, and the base is aligned for 4-element loads.
-template <bool F32, bool VEC>
-__device__ __forceinline__ void sy_stage(uint8_t* dst, int dst_stride, const void* images, size_t src0, size_t src_stride, int rows, int count,
-                                         int t) {
-  if (VEC) {
-    const int q = count >> 2;
-    for (int i = t; i < rows * q; i += SY_TB) {
-      const int r = i / q, e = (i - r * q) * 4;
-      const size_t src = src0 + (size_t)r * src_stride + e;
-      uint32_t pk;
-      if (F32) {
-        const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(images) + src);
-        pk = (uint32_t)cp_float_to_u8(v.x) | ((uint32_t)cp_float_to_u8(v.y) << 8) | ((uint32_t)cp_float_to_u8(v.z) << 16) |
-             ((uint32_t)cp_float_to_u8(v.w) << 24);
-      } else {
-        pk = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(images) + src);
-      }
-      *reinterpret_cast<uint32_t*>(dst + r * dst_stride + e) = pk;
-    }
-  } else {
-    for (int i = t; i < rows * count; i += SY_TB) {
-      const int r = i / count, e = i - r * count;
-      const size_t src = src0 + (size_t)r * src_stride + e;
-      dst[r * dst_stride + e] = F32 ? (uint8_t)cp_float_to_u8(static_cast<const float*>(images)[src]) : static_cast<const uint8_t*>(images)[src];
-    }
-  }
 }
 
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
@@ -84,7 +53,7 @@ __global__ __launch_bounds__(SY_TB) void symmetry_stats_kernel(const SyStatsArgs
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint64_t* red = reinterpret_cast<uint64_t*>(smem);                        // [SY_WAVES][4]
   uint8_t* s0 = reinterpret_cast<uint8_t*>(smem) + SY_WAVES * 4 * sizeof(uint64_t);
-  uint8_t* s1 = s0 + sy_row_bytes(a.W);                                     // present when mode == 1
+  uint8_t* s1 = s0 + iu_row_bytes(a.W);                                     // present when mode == 1
   const int t = threadIdx.x;
   const int n = blockIdx.x / a.slots, g = blockIdx.x - n * a.slots;
   const int per = (a.units + a.slots - 1) / a.slots;
@@ -94,8 +63,8 @@ __global__ __launch_bounds__(SY_TB) void symmetry_stats_kernel(const SyStatsArgs
   for (int y = u0; y < u1; ++y) {
     const int y2 = sy_partner_row(y, a.H, a.mode);
     const bool two = y2 != y;
-    sy_stage<F32, VEC>(s0, 0, a.images, ((size_t)n * a.H + y) * w3, 0, 1, w3, t);
-    if (two) sy_stage<F32, VEC>(s1, 0, a.images, ((size_t)n * a.H + y2) * w3, 0, 1, w3, t);
+    iu_stage<F32, VEC, SY_TB>(s0, 0, a.images, ((size_t)n * a.H + y) * w3, 0, 1, w3, t);
+    if (two) iu_stage<F32, VEC, SY_TB>(s1, 0, a.images, ((size_t)n * a.H + y2) * w3, 0, 1, w3, t);
     __syncthreads();
     const uint8_t* sp = two ? s1 : s0;
     SyPartial p = {{0, 0, 0, 0}};
@@ -138,7 +107,7 @@ __global__ __launch_bounds__(SY_TB) void rotate4_u8_kernel(const void* __restric
   const int n = blockIdx.x / (tiles * tiles), rem = blockIdx.x - n * tiles * tiles;
   const int ty0 = (rem / tiles) * SY_TILE, tx0 = (rem % tiles) * SY_TILE;
   const int th = min(SY_TILE, S - ty0), tw = min(SY_TILE, S - tx0);
-  sy_stage<F32, VEC>(tile, SY_TILE_STRIDE, images, (((size_t)n * S + ty0) * S + tx0) * 3, (size_t)S * 3, th, tw * 3, t);
+  iu_stage<F32, VEC, SY_TB>(tile, SY_TILE_STRIDE, images, (((size_t)n * S + ty0) * S + tx0) * 3, (size_t)S * 3, th, tw * 3, t);
   __syncthreads();
   for (int k = 0; k < 4; ++k) {
     int ay, ax, by, bx;                                                     // where two opposite corners of the tile land: the output rectangle
@@ -162,10 +131,6 @@ bool sy_rotate_geometry_ok(int N, int S) {
   return (int64_t)N * tiles * tiles <= 0x7fffffff;
 }
 
-inline int sy_byte(const void* images, int is_float32, size_t i) {
-  return is_float32 ? cp_float_to_u8(static_cast<const float*>(images)[i]) : (int)static_cast<const uint8_t*>(images)[i];
-}
-
 }  // namespace
 
 extern "C" int ddpo_symmetry_stats_workspace_bytes(int N, int H, int W, int mode, size_t* out_host) {
@@ -179,21 +144,14 @@ extern "C" int ddpo_symmetry_stats(const void* images, int is_float32, int N, in
   if (!images || !stats_out || !workspace || !sy_stats_geometry_ok(N, H, W, mode)) return DDPO_EINVAL;
   const int slots = sy_slots(H, mode);
   if (workspace_bytes < (size_t)N * slots * 4 * sizeof(uint64_t)) return DDPO_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 7) || (reinterpret_cast<uintptr_t>(stats_out) & 7) ||
-      (is_float32 && (reinterpret_cast<uintptr_t>(images) & 3)))
+  if ((reinterpret_cast<uintptr_t>(workspace) & 7) || (reinterpret_cast<uintptr_t>(stats_out) & 7) || iu_misaligned(images, is_float32))
     return DDPO_EINVAL;
   const SyStatsArgs a{images, H, W, mode, sy_units(H, mode), slots, static_cast<uint64_t*>(workspace)};
-  const size_t lds = SY_WAVES * 4 * sizeof(uint64_t) + (mode ? 2 : 1) * sy_row_bytes(W);          // <= 128 + 2 * 32640 bytes: inside the 64 KB default
-  const bool vec = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(images) & (is_float32 ? 15 : 3)) == 0;
+  const size_t lds = SY_WAVES * 4 * sizeof(uint64_t) + (mode ? 2 : 1) * iu_row_bytes(W);          // <= 128 + 2 * 32640 bytes: inside the 64 KB default
   hipStream_t s = as_stream(stream);
-  const dim3 grid((unsigned)(N * slots)), block(SY_TB);
-  if (is_float32) {
-    if (vec) hipLaunchKernelGGL((symmetry_stats_kernel<true, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((symmetry_stats_kernel<true, false>), grid, block, lds, s, a);
-  } else {
-    if (vec) hipLaunchKernelGGL((symmetry_stats_kernel<false, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((symmetry_stats_kernel<false, false>), grid, block, lds, s, a);
-  }
+  iu_dispatch(is_float32, iu_vec_ok(images, is_float32, W), [&](auto F32, auto VEC) {
+    hipLaunchKernelGGL((symmetry_stats_kernel<F32(), VEC()>), dim3((unsigned)(N * slots)), dim3(SY_TB), lds, s, a);
+  });
   DDPO_LAUNCH_CHECK();
   hipLaunchKernelGGL(symmetry_finish_kernel, dim3((unsigned)N), dim3(64), 0, s, a.partial, slots, stats_out);
   DDPO_LAUNCH_CHECK();
@@ -202,18 +160,11 @@ extern "C" int ddpo_symmetry_stats(const void* images, int is_float32, int N, in
 
 extern "C" int ddpo_rotate4_u8(const void* images, int is_float32, int N, int H, int W, uint8_t* out, void* stream) {
   if (!images || !out || H != W || !sy_rotate_geometry_ok(N, H)) return DDPO_EINVAL;
-  if (is_float32 && (reinterpret_cast<uintptr_t>(images) & 3)) return DDPO_EINVAL;
+  if (iu_misaligned(images, is_float32)) return DDPO_EINVAL;
   const int S = H, tiles = (S + SY_TILE - 1) / SY_TILE;
-  const bool vec = (S & 3) == 0 && (reinterpret_cast<uintptr_t>(images) & (is_float32 ? 15 : 3)) == 0;
-  hipStream_t s = as_stream(stream);
-  const dim3 grid((unsigned)(N * tiles * tiles)), block(SY_TB);
-  if (is_float32) {
-    if (vec) hipLaunchKernelGGL((rotate4_u8_kernel<true, true>), grid, block, 0, s, images, N, S, out);
-    else hipLaunchKernelGGL((rotate4_u8_kernel<true, false>), grid, block, 0, s, images, N, S, out);
-  } else {
-    if (vec) hipLaunchKernelGGL((rotate4_u8_kernel<false, true>), grid, block, 0, s, images, N, S, out);
-    else hipLaunchKernelGGL((rotate4_u8_kernel<false, false>), grid, block, 0, s, images, N, S, out);
-  }
+  iu_dispatch(is_float32, iu_vec_ok(images, is_float32, S), [&](auto F32, auto VEC) {
+    hipLaunchKernelGGL((rotate4_u8_kernel<F32(), VEC()>), dim3((unsigned)(N * tiles * tiles)), dim3(SY_TB), 0, as_stream(stream), images, N, S, out);
+  });
   DDPO_LAUNCH_CHECK();
   return DDPO_OK;
 }
@@ -227,7 +178,7 @@ extern "C" int ddpo_symmetry_stats_host(const void* images, int is_float32, int 
     for (int y = 0; y < H; ++y) {
       const size_t row = ((size_t)n * H + y) * w3, prow = ((size_t)n * H + sy_partner_row(y, H, mode)) * w3;
       SyPartial p = {{0, 0, 0, 0}};
-      for (int e = 0; e < w3; ++e) sy_add(p, sy_byte(images, is_float32, row + e), sy_byte(images, is_float32, prow + sy_mirror_offset(e, W)));
+      for (int e = 0; e < w3; ++e) sy_add(p, iu_byte(images, is_float32, row + e), iu_byte(images, is_float32, prow + sy_mirror_offset(e, W)));
       for (int k = 0; k < 4; ++k) acc[k] += p.s[k];
     }
     for (int k = 0; k < 4; ++k) stats_out_host[(size_t)n * 4 + k] = (int64_t)acc[k];
@@ -245,7 +196,7 @@ extern "C" int ddpo_rotate4_u8_host(const void* images, int is_float32, int N, i
           int iy, ix;
           sy_rot_src(k, S, oy, ox, iy, ix);
           for (int c = 0; c < 3; ++c)
-            out_host[((((size_t)k * N + n) * S + oy) * S + ox) * 3 + c] = (uint8_t)sy_byte(images, is_float32, (((size_t)n * S + iy) * S + ix) * 3 + c);
+            out_host[((((size_t)k * N + n) * S + oy) * S + ox) * 3 + c] = (uint8_t)iu_byte(images, is_float32, (((size_t)n * S + iy) * S + ix) * 3 + c);
         }
   return DDPO_OK;
 }

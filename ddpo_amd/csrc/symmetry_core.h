@@ -3,14 +3,14 @@
 // numbers mean is decided by the host entries against numpy / Pillow (tests/test_symmetry_cpu.py) and the kernels only have to agree with the
 // host entries.  Plain C++17: no HIP header is needed.
 //
-// Everything is integer once the pixel is a byte (cp_float_to_u8 of clip_preprocess_core.h), so every sum is exact and independent of the order
+// Everything is integer once the pixel is a byte (iu_float_to_u8 of image_u8.h), so every sum is exact and independent of the order
 // it is taken in.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-#include "clip_preprocess_core.h"
+#include "image_u8.h"
 
-#define SY_HD CP_HD
+#define SY_HD IU_HD
 
 // The widest image: one row of W x 3 bytes is staged in LDS (two rows for rotate-180), and no 32-bit partial below is fed more than
 // SY_U32_ELEMS elements before it is added to a 64-bit sum: the largest term is 255^2 = 65025 and 66051 * 65025 < 2^32 <= 66052 * 65025.

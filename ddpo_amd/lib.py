@@ -1601,16 +1601,47 @@ def _workspace_or_scratch(who, workspace, nbytes, device, tag):
     return workspace
 
 
+def _images_nhwc(who, images, square=False):
+    """The rules every reward entry shares, each refused by name: (N, H, W) of a float32 / uint8 contiguous N x H x W x 3 batch, a tensor or a
+    numpy array, that is not empty (and square, for rotate4_u8)."""
+    is_tensor = isinstance(images, torch.Tensor)
+    f32, u8 = (torch.float32, torch.uint8) if is_tensor else ("float32", "uint8")
+    if images.dtype not in (f32, u8):
+        raise ValueError(f"{who}: the dtype must be float32 or uint8, got {images.dtype} (uint8 or float32 images only)")
+    shape = tuple(images.shape)
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError(f"{who} needs N x H x W x 3 images (last dimension 3), got shape {shape}")
+    if shape[0] < 1 or shape[1] < 1 or shape[2] < 1:
+        raise ValueError(f"{who}: empty batch or empty images, got shape {shape}")
+    if not (images.is_contiguous() if is_tensor else images.flags.c_contiguous):
+        raise ValueError(f"{who} needs contiguous images (N x H x W x 3 in memory order)")
+    if square and shape[1] != shape[2]:
+        raise ValueError(f"{who} needs square images (a right-angle turn of a {shape[1]} x {shape[2]} image has another shape)")
+    return int(shape[0]), int(shape[1]), int(shape[2])
+
+
+def _out_or_empty(who, out, shape, dtype, device, name="out"):
+    """`out` checked — contiguous, `dtype`, `shape`, on `device`: the kernels write shape-many elements from its pointer on — or, when None, a
+    new tensor"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise DdpoHipError(f"{who}: {name} must be a contiguous {str(dtype).split('.')[-1]} {tuple(shape)} tensor on {device}")
+    return out
+
+
+def _np_ptr(a):
+    return a.ctypes.data_as(c_void_p)
+
+
 # ------------------------------------------------------------------------------------------------ JPEG file size
 JPEG_FIXED_BYTES = 625        # DDPO_JPEG_FIXED_BYTES of include/ddpo_hip.h: the bytes of a file that are not entropy-coded data
 JPEG_SIZE_RULE = "height and width must be multiples of 16 (the 4:2:0 MCU): edge replication and dummy blocks are not built"
 
 
-def _jpeg_size_args(shape, quality):
-    if len(shape) != 4 or shape[3] != 3 or shape[0] < 1:
-        raise ValueError(f"jpeg_size needs N x H x W x 3 images, got shape {tuple(shape)}")
-    n, h, w = int(shape[0]), int(shape[1]), int(shape[2])
-    if h < 16 or w < 16 or h % 16 or w % 16:
+def _jpeg_size_args(images, quality):
+    n, h, w = _images_nhwc("jpeg_size", images)
+    if h % 16 or w % 16:
         raise ValueError(f"jpeg_size: {h} x {w} images: {JPEG_SIZE_RULE}")
     if int(quality) != quality or not 1 <= quality <= 100:
         raise ValueError(f"jpeg_size: quality must be an integer in 1..100, got {quality!r}")
@@ -1629,13 +1660,13 @@ def jpeg_size_workspace_bytes(n, h, w):
 def jpeg_size(images, quality=95, workspace=None, out=None):
     """len(PIL JPEG bytes at `quality`) of every image of an N x H x W x 3 CUDA tensor — uint8, or float32 in [0, 1] truncated as
     (x * 255).astype(uint8) — as an int64 CUDA tensor, on the current stream; no file is produced (ddpo_jpeg_size).  H and W must be multiples of 16
-    (ValueError).  `workspace`: a uint8 CUDA tensor of at least jpeg_size_workspace_bytes(N, H, W) bytes; default: this stream's scratch."""
+    (ValueError).  `workspace`: a uint8 CUDA tensor of at least jpeg_size_workspace_bytes(N, H, W) bytes; default: this stream's scratch.
+    `out`: a contiguous int64 CUDA tensor (N,) to write into."""
     _cuda_images("jpeg_size", images)
-    n, h, w, quality = _jpeg_size_args(images.shape, quality)
+    n, h, w, quality = _jpeg_size_args(images, quality)
     nb = jpeg_size_workspace_bytes(n, h, w)
     workspace = _workspace_or_scratch("jpeg_size", workspace, nb, images.device, "jpeg_size")
-    if out is None:
-        out = torch.empty(n, dtype=torch.int64, device=images.device)
+    out = _out_or_empty("jpeg_size", out, (n,), torch.int64, images.device)
     _check(load().ddpo_jpeg_size(_p(images), int(images.dtype == torch.float32), n, h, w, quality, _p(workspace), workspace.numel(), _p(out),
                                  _stream()), "ddpo_jpeg_size")
     return out
@@ -1647,9 +1678,9 @@ def jpeg_size_host(images_u8, quality=95):
     a = np.ascontiguousarray(images_u8)
     if a.dtype != np.uint8:
         raise ValueError("jpeg_size_host needs uint8 images")
-    n, h, w, quality = _jpeg_size_args(a.shape, quality)
+    n, h, w, quality = _jpeg_size_args(a, quality)
     out = np.zeros(n, dtype=np.int64)
-    _check(load().ddpo_jpeg_size_host(a.ctypes.data_as(c_void_p), n, h, w, quality, out.ctypes.data_as(c_void_p)), "ddpo_jpeg_size_host")
+    _check(load().ddpo_jpeg_size_host(_np_ptr(a), n, h, w, quality, _np_ptr(out)), "ddpo_jpeg_size_host")
     return out
 
 
@@ -1658,8 +1689,8 @@ JPEG_HEADER_BYTES = 623       # DDPO_JPEG_HEADER_BYTES: everything a file holds 
 JPEG_MAX_DIM = 65500          # the largest height or width libjpeg writes
 
 
-def _jpeg_encode_args(shape, quality):
-    n, h, w, quality = _jpeg_size_args(shape, quality)
+def _jpeg_encode_args(images, quality):
+    n, h, w, quality = _jpeg_size_args(images, quality)
     if h > JPEG_MAX_DIM or w > JPEG_MAX_DIM:
         raise ValueError(f"jpeg_encode: {h} x {w} images: a JPEG file holds at most {JPEG_MAX_DIM} rows and columns")
     return n, h, w, quality
@@ -1682,7 +1713,7 @@ def jpeg_encode(images, quality=80, workspace=None, files=None, stride=None):
     jpeg_encode_max_bytes(H, W) is never exceeded) leaves its first `stride` bytes and still reports its full length; bytes of a row past the
     file are not written.  `files`: a contiguous uint8 CUDA tensor (N, stride) to write into.  `workspace`: as for jpeg_size."""
     _cuda_images("jpeg_encode", images)
-    n, h, w, quality = _jpeg_encode_args(images.shape, quality)
+    n, h, w, quality = _jpeg_encode_args(images, quality)
     if stride is None:
         stride = int(files.shape[1]) if files is not None and files.dim() == 2 else h * w * 3 + JPEG_FIXED_BYTES
     if int(stride) != stride or stride < JPEG_FIXED_BYTES:
@@ -1690,10 +1721,7 @@ def jpeg_encode(images, quality=80, workspace=None, files=None, stride=None):
     stride = int(stride)
     nb = jpeg_size_workspace_bytes(n, h, w)
     workspace = _workspace_or_scratch("jpeg_encode", workspace, nb, images.device, "jpeg_size")
-    if files is None:
-        files = torch.empty((n, stride), dtype=torch.uint8, device=images.device)
-    if files.dtype != torch.uint8 or tuple(files.shape) != (n, stride) or not files.is_contiguous() or files.device != images.device:
-        raise DdpoHipError(f"jpeg_encode: `files` must be a contiguous uint8 tensor of shape ({n}, {stride}) on {images.device}")
+    files = _out_or_empty("jpeg_encode", files, (n, stride), torch.uint8, images.device, name="files")
     lengths = torch.empty(n, dtype=torch.int64, device=images.device)
     _check(load().ddpo_jpeg_encode(_p(images), int(images.dtype == torch.float32), n, h, w, quality, _p(workspace), workspace.numel(), _p(files),
                                    stride, _p(lengths), _stream()), "ddpo_jpeg_encode")
@@ -1707,11 +1735,10 @@ def jpeg_encode_host(images_u8, quality=80):
     a = np.ascontiguousarray(images_u8)
     if a.dtype != np.uint8:
         raise ValueError("jpeg_encode_host needs uint8 images")
-    n, h, w, quality = _jpeg_encode_args(a.shape, quality)
+    n, h, w, quality = _jpeg_encode_args(a, quality)
     stride = jpeg_encode_max_bytes(h, w)
     files, lengths = np.empty((n, stride), dtype=np.uint8), np.zeros(n, dtype=np.int64)
-    _check(load().ddpo_jpeg_encode_host(a.ctypes.data_as(c_void_p), n, h, w, quality, files.ctypes.data_as(c_void_p), stride,
-                                        lengths.ctypes.data_as(c_void_p)), "ddpo_jpeg_encode_host")
+    _check(load().ddpo_jpeg_encode_host(_np_ptr(a), n, h, w, quality, _np_ptr(files), stride, _np_ptr(lengths)), "ddpo_jpeg_encode_host")
     return [files[i, :lengths[i]].tobytes() for i in range(n)]
 
 
@@ -1789,9 +1816,16 @@ def clip_norm_table(mean=None, std=None):
     return t
 
 
-def _clip_lds_bytes(rows, size, w):
+def _band_lds_bytes(rows, out_w, w, norm_table):
+    """cp_lds_bytes of csrc/clip_preprocess_core.h"""
     up = lambda px: (px * 3 + 15) // 16 * 16
-    return rows * up(size) + CLIP_STAGE_ROWS * up(w) + 256 * 3 * 4
+    return rows * up(out_w) + CLIP_STAGE_ROWS * up(w) + (256 * 3 * 4 if norm_table else 0)
+
+
+def _band_rows(vb, first, count, band):
+    """The most input rows a band of `band` output rows spans, over the output rows [first, first + count) of a vertical bound table"""
+    ends = vb[:, 0] + vb[:, 1]
+    return max(int(ends[y0:min(y0 + band, first + count)].max() - vb[y0, 0]) for y0 in range(first, first + count, band))
 
 
 @functools.lru_cache(maxsize=None)
@@ -1810,11 +1844,9 @@ def clip_preprocess_geometry(h, w, size, patch, k_pad):
     ow, oh = (new_short, new_long) if w <= h else (new_long, new_short)
     top, left = (oh - size) // 2, (ow - size) // 2
     _, vb, _ = clip_preprocess_tables(h, oh)
-    rows = 1
-    for y0 in range(top, top + size, patch):
-        rows = max(rows, int((vb[y0:y0 + patch, 0] + vb[y0:y0 + patch, 1]).max() - vb[y0, 0]))
-    if _clip_lds_bytes(rows, size, w) > CLIP_LDS_LIMIT:
-        raise ValueError(f"clip_preprocess: {h} x {w} images to {size} need {rows} rows = {_clip_lds_bytes(rows, size, w)} bytes: {CLIP_PREPROCESS_RULE}")
+    rows = max(_band_rows(vb, top, size, patch), 1)
+    if _band_lds_bytes(rows, size, w, True) > CLIP_LDS_LIMIT:
+        raise ValueError(f"clip_preprocess: {h} x {w} images to {size} need {rows} rows = {_band_lds_bytes(rows, size, w, True)} bytes: {CLIP_PREPROCESS_RULE}")
     return dict(oh=oh, ow=ow, top=top, left=left, rows=rows)
 
 
@@ -1831,28 +1863,19 @@ def _clip_device_tables(key, make, device):
     return ent
 
 
-def _clip_images_shape(shape):
-    if len(shape) != 4 or shape[3] != 3 or shape[0] < 1:
-        raise ValueError(f"clip_preprocess needs N x H x W x 3 images, got shape {tuple(shape)}")
-    return int(shape[0]), int(shape[1]), int(shape[2])
-
-
 def clip_preprocess(images, size, patch, k_pad, out=None):
     """models.clip_vision.preprocess + the im2col of the patch embedding in one launch on the current stream (ddpo_clip_preprocess): an
     N x H x W x 3 CUDA tensor — float32 in [0, 1], truncated as (x * 255).astype(uint8), or uint8 — to the (N * g * g, k_pad) float32 patch
     matrix, g = size // patch, rows (n, gy, gx), columns (c, ky, kx), pad columns zero.  Equal bit for bit to the host path (Pillow's bicubic
     resize of the short side to `size`, centre crop, CLIP normalisation).  ValueError names the broken rule (CLIP_PREPROCESS_RULE for LDS)."""
     _cuda_images("clip_preprocess", images)
-    n, h, w = _clip_images_shape(images.shape)
+    n, h, w = _images_nhwc("clip_preprocess", images)
     geo = clip_preprocess_geometry(h, w, size, patch, k_pad)
     g = size // patch
     hc, hb = _clip_device_tables(("axis", w, geo["ow"]), lambda: clip_preprocess_tables(w, geo["ow"])[:2], images.device)
     vc, vb = _clip_device_tables(("axis", h, geo["oh"]), lambda: clip_preprocess_tables(h, geo["oh"])[:2], images.device)
     norm, = _clip_device_tables(("norm",), lambda: (clip_norm_table(),), images.device)
-    if out is None:
-        out = torch.empty(n * g * g, k_pad, dtype=torch.float32, device=images.device)
-    if out.dtype != torch.float32 or tuple(out.shape) != (n * g * g, k_pad) or out.device != images.device:
-        raise DdpoHipError(f"clip_preprocess: out must be a float32 ({n * g * g}, {k_pad}) tensor on {images.device}")
+    out = _out_or_empty("clip_preprocess", out, (n * g * g, k_pad), torch.float32, images.device)
     _check(load().ddpo_clip_preprocess(_p(images), int(images.dtype == torch.float32), n, h, w, geo["oh"], geo["ow"], geo["top"], geo["left"],
                                        int(size), int(patch), _p(hc), _p(hb), hc.shape[1], _p(vc), _p(vb), vc.shape[1], geo["rows"], _p(norm),
                                        _p(out), int(k_pad), _stream()), "ddpo_clip_preprocess")
@@ -1864,9 +1887,7 @@ def clip_preprocess_host(images, size, patch, k_pad, return_resized=False):
     GPU-free reference.  return_resized: also the N x size x size x 3 uint8 image before normalisation (what Pillow's resize + crop gives)."""
     import numpy as np
     a = np.ascontiguousarray(images)
-    if a.dtype not in (np.uint8, np.float32):
-        raise ValueError(f"clip_preprocess_host takes uint8 or float32 images, got {a.dtype}")
-    n, h, w = _clip_images_shape(a.shape)
+    n, h, w = _images_nhwc("clip_preprocess_host", a)
     geo = clip_preprocess_geometry(h, w, size, patch, k_pad)
     g = size // patch
     hc, hb, hk = clip_preprocess_tables(w, geo["ow"])
@@ -1874,10 +1895,9 @@ def clip_preprocess_host(images, size, patch, k_pad, return_resized=False):
     norm = clip_norm_table()
     out = np.full((n * g * g, k_pad), np.nan, dtype=np.float32)
     resized = np.zeros((n, size, size, 3), dtype=np.uint8)
-    ptr = lambda x: x.ctypes.data_as(c_void_p)
-    _check(load().ddpo_clip_preprocess_host(ptr(a), int(a.dtype == np.float32), n, h, w, geo["oh"], geo["ow"], geo["top"], geo["left"], int(size),
-                                            int(patch), ptr(hc), ptr(hb), hk, ptr(vc), ptr(vb), vk, ptr(norm), ptr(out), int(k_pad), ptr(resized)),
-           "ddpo_clip_preprocess_host")
+    _check(load().ddpo_clip_preprocess_host(_np_ptr(a), int(a.dtype == np.float32), n, h, w, geo["oh"], geo["ow"], geo["top"], geo["left"],
+                                            int(size), int(patch), _np_ptr(hc), _np_ptr(hb), hk, _np_ptr(vc), _np_ptr(vb), vk, _np_ptr(norm),
+                                            _np_ptr(out), int(k_pad), _np_ptr(resized)), "ddpo_clip_preprocess_host")
     return (out, resized) if return_resized else out
 
 
@@ -1885,11 +1905,6 @@ def clip_preprocess_host(images, size, patch, k_pad, return_resized=False):
 RESIZE_U8_BAND = 2            # output rows of one workgroup (measured: DESIGN.md 2e); 1 where 2 break the LDS rule
 RESIZE_U8_RULE = ("the input rows one band of output rows needs (2 output rows, or 1 where 2 do not fit), resampled horizontally to bytes "
                   "(rows x ow x 3), plus 8 staged input rows (W x 3 bytes each) must fit the 160 KB of LDS")
-
-
-def _resize_lds_bytes(rows, ow, w):
-    up = lambda px: (px * 3 + 15) // 16 * 16
-    return rows * up(ow) + CLIP_STAGE_ROWS * up(w)
 
 
 @functools.lru_cache(maxsize=None)
@@ -1904,11 +1919,11 @@ def resize_u8_geometry(h, w, oh, ow):
     _, vb, _ = clip_preprocess_tables(h, oh)
     band = RESIZE_U8_BAND
     while True:
-        rows = max(int((vb[y0:y0 + band, 0] + vb[y0:y0 + band, 1]).max() - vb[y0, 0]) for y0 in range(0, oh, band))
-        if _resize_lds_bytes(rows, ow, w) <= CLIP_LDS_LIMIT:
+        rows = _band_rows(vb, 0, oh, band)
+        if _band_lds_bytes(rows, ow, w, False) <= CLIP_LDS_LIMIT:
             return dict(band=band, rows=max(rows, 1))
         if band == 1:
-            raise ValueError(f"resize_u8: {h} x {w} images to {oh} x {ow} need {rows} rows = {_resize_lds_bytes(rows, ow, w)} bytes: {RESIZE_U8_RULE}")
+            raise ValueError(f"resize_u8: {h} x {w} images to {oh} x {ow} need {rows} rows = {_band_lds_bytes(rows, ow, w, False)} bytes: {RESIZE_U8_RULE}")
         band //= 2
 
 
@@ -1922,16 +1937,13 @@ def resize_u8(images, oh, ow, out=None):
     """PIL.Image.resize((ow, oh), BICUBIC) of every image of an N x H x W x 3 CUDA batch — uint8, or float32 in [0, 1] truncated as
     (x * 255).astype(uint8) — as one uint8 CUDA tensor (N, oh, ow, 3), in one launch on the current stream (ddpo_resize_u8): Pillow's bytes
     exactly, up-scales included.  ValueError names the broken rule (RESIZE_U8_RULE for LDS)."""
-    _cuda_images("resize_u8", images, any_dtype=True)          # _symmetry_images names the dtype rule
-    n, h, w = _symmetry_images("resize_u8", images, True)
+    _cuda_images("resize_u8", images, any_dtype=True)          # _images_nhwc names the dtype rule
+    n, h, w = _images_nhwc("resize_u8", images)
     oh, ow = _resize_target("resize_u8", oh, ow)
     geo = resize_u8_geometry(h, w, oh, ow)
     hc, hb = _clip_device_tables(("axis", w, ow), lambda: clip_preprocess_tables(w, ow)[:2], images.device)
     vc, vb = _clip_device_tables(("axis", h, oh), lambda: clip_preprocess_tables(h, oh)[:2], images.device)
-    if out is None:
-        out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=images.device)
-    if out.dtype != torch.uint8 or tuple(out.shape) != (n, oh, ow, 3) or not out.is_contiguous() or out.device != images.device:
-        raise DdpoHipError(f"resize_u8: out must be a contiguous uint8 ({n}, {oh}, {ow}, 3) tensor on {images.device}")
+    out = _out_or_empty("resize_u8", out, (n, oh, ow, 3), torch.uint8, images.device)
     _check(load().ddpo_resize_u8(_p(images), int(images.dtype == torch.float32), n, h, w, oh, ow, _p(hc), _p(hb), hc.shape[1], _p(vc), _p(vb),
                                  vc.shape[1], geo["band"], geo["rows"], _p(out), _stream()), "ddpo_resize_u8")
     return out
@@ -1942,15 +1954,14 @@ def resize_u8_host(images, oh, ow):
     reference, held to Pillow itself."""
     import numpy as np
     a = np.asarray(images)
-    n, h, w = _symmetry_images("resize_u8_host", a, False)
+    n, h, w = _images_nhwc("resize_u8_host", a)
     oh, ow = _resize_target("resize_u8_host", oh, ow)
     geo = resize_u8_geometry(h, w, oh, ow)
     hc, hb, hk = clip_preprocess_tables(w, ow)
     vc, vb, vk = clip_preprocess_tables(h, oh)
     out = np.zeros((n, oh, ow, 3), dtype=np.uint8)
-    ptr = lambda x: x.ctypes.data_as(c_void_p)
-    _check(load().ddpo_resize_u8_host(ptr(a), int(a.dtype == np.float32), n, h, w, oh, ow, ptr(hc), ptr(hb), hk, ptr(vc), ptr(vb), vk, geo["band"],
-                                      ptr(out)), "ddpo_resize_u8_host")
+    _check(load().ddpo_resize_u8_host(_np_ptr(a), int(a.dtype == np.float32), n, h, w, oh, ow, _np_ptr(hc), _np_ptr(hb), hk, _np_ptr(vc),
+                                      _np_ptr(vb), vk, geo["band"], _np_ptr(out)), "ddpo_resize_u8_host")
     return out
 
 
@@ -1964,24 +1975,6 @@ def _symmetry_mode(mode):
     if mode not in SYMMETRY_MODES:
         raise ValueError(f"symmetry_stats: mode must be one of {sorted(SYMMETRY_MODES)}, got {mode!r}")
     return SYMMETRY_MODES[mode]
-
-
-def _symmetry_images(who, images, is_tensor, square=False):
-    """The rules the symmetry entries share with clip_preprocess, each refused by name: (N, H, W) of a float32 / uint8 contiguous
-    N x H x W x 3 batch that is not empty (and square, for rotate4_u8)."""
-    f32, u8 = (torch.float32, torch.uint8) if is_tensor else ("float32", "uint8")
-    if images.dtype not in (f32, u8):
-        raise ValueError(f"{who}: the dtype must be float32 or uint8, got {images.dtype}")
-    shape = tuple(images.shape)
-    if len(shape) != 4 or shape[3] != 3:
-        raise ValueError(f"{who} needs N x H x W x 3 images (last dimension 3), got shape {shape}")
-    if shape[0] < 1 or shape[1] < 1 or shape[2] < 1:
-        raise ValueError(f"{who}: empty batch or empty images, got shape {shape}")
-    if not (images.is_contiguous() if is_tensor else images.flags.c_contiguous):
-        raise ValueError(f"{who} needs contiguous images (N x H x W x 3 in memory order)")
-    if square and shape[1] != shape[2]:
-        raise ValueError(f"{who} needs square images (a right-angle turn of a {shape[1]} x {shape[2]} image has another shape)")
-    return int(shape[0]), int(shape[1]), int(shape[2])
 
 
 def symmetry_stats_workspace_bytes(n, h, w, mode):
@@ -1999,15 +1992,12 @@ def symmetry_stats(images, mode, workspace=None, out=None):
     (y, W-1-x, c), "rot180": (H-1-y, W-1-x, c) —: [0] sum of ((a - b) mod 256)^2 mod 256 (what numpy's uint8 arithmetic makes of (a - b) ** 2),
     [1] sum of a, [2] sum of a^2, [3] sum of a b.  `workspace`: a uint8 CUDA tensor of at least symmetry_stats_workspace_bytes(N, H, W, mode)
     bytes; default: this stream's scratch.  ValueError names the broken rule."""
-    _cuda_images("symmetry_stats", images, any_dtype=True)          # _symmetry_images names the dtype rule
+    _cuda_images("symmetry_stats", images, any_dtype=True)          # _images_nhwc names the dtype rule
     m = _symmetry_mode(mode)
-    n, h, w = _symmetry_images("symmetry_stats", images, True)
+    n, h, w = _images_nhwc("symmetry_stats", images)
     nb = symmetry_stats_workspace_bytes(n, h, w, mode)
     workspace = _workspace_or_scratch("symmetry_stats", workspace, nb, images.device, "symmetry_stats")
-    if out is None:
-        out = torch.empty((n, 4), dtype=torch.int64, device=images.device)
-    if out.dtype != torch.int64 or tuple(out.shape) != (n, 4) or not out.is_contiguous() or out.device != images.device:
-        raise DdpoHipError(f"symmetry_stats: out must be a contiguous int64 ({n}, 4) tensor on {images.device}")
+    out = _out_or_empty("symmetry_stats", out, (n, 4), torch.int64, images.device)
     _check(load().ddpo_symmetry_stats(_p(images), int(images.dtype == torch.float32), n, h, w, m, _p(out), _p(workspace), workspace.numel(),
                                       _stream()), "ddpo_symmetry_stats")
     return out
@@ -2019,12 +2009,11 @@ def symmetry_stats_host(images, mode):
     import numpy as np
     a = np.asarray(images)
     m = _symmetry_mode(mode)
-    n, h, w = _symmetry_images("symmetry_stats_host", a, False)
+    n, h, w = _images_nhwc("symmetry_stats_host", a)
     if w > SYMMETRY_MAX_W:
         raise ValueError(f"symmetry_stats_host: {h} x {w} images: {SYMMETRY_WIDTH_RULE}")
     out = np.zeros((n, 4), dtype=np.int64)
-    _check(load().ddpo_symmetry_stats_host(a.ctypes.data_as(c_void_p), int(a.dtype == np.float32), n, h, w, m, out.ctypes.data_as(c_void_p)),
-           "ddpo_symmetry_stats_host")
+    _check(load().ddpo_symmetry_stats_host(_np_ptr(a), int(a.dtype == np.float32), n, h, w, m, _np_ptr(out)), "ddpo_symmetry_stats_host")
     return out
 
 
@@ -2032,12 +2021,9 @@ def rotate4_u8(images, out=None):
     """The four right-angle turns of a square N x S x S x 3 CUDA batch — uint8, or float32 in [0, 1] truncated as (x * 255).astype(uint8) — as
     one uint8 CUDA tensor (4N, S, S, 3), on the current stream (ddpo_rotate4_u8): block k N + n is PIL.Image.rotate(90 k) of image n, k = 0..3.
     ValueError names the broken rule."""
-    _cuda_images("rotate4_u8", images, any_dtype=True)          # _symmetry_images names the dtype rule
-    n, s, _ = _symmetry_images("rotate4_u8", images, True, square=True)
-    if out is None:
-        out = torch.empty((4 * n, s, s, 3), dtype=torch.uint8, device=images.device)
-    if out.dtype != torch.uint8 or tuple(out.shape) != (4 * n, s, s, 3) or not out.is_contiguous() or out.device != images.device:
-        raise DdpoHipError(f"rotate4_u8: out must be a contiguous uint8 ({4 * n}, {s}, {s}, 3) tensor on {images.device}")
+    _cuda_images("rotate4_u8", images, any_dtype=True)          # _images_nhwc names the dtype rule
+    n, s, _ = _images_nhwc("rotate4_u8", images, square=True)
+    out = _out_or_empty("rotate4_u8", out, (4 * n, s, s, 3), torch.uint8, images.device)
     _check(load().ddpo_rotate4_u8(_p(images), int(images.dtype == torch.float32), n, s, s, _p(out), _stream()), "ddpo_rotate4_u8")
     return out
 
@@ -2046,10 +2032,9 @@ def rotate4_u8_host(images):
     """The same turns made serially on the host (ddpo_rotate4_u8_host) for a uint8 or float32 N x S x S x 3 numpy array: the GPU-free reference."""
     import numpy as np
     a = np.asarray(images)
-    n, s, _ = _symmetry_images("rotate4_u8_host", a, False, square=True)
+    n, s, _ = _images_nhwc("rotate4_u8_host", a, square=True)
     out = np.zeros((4 * n, s, s, 3), dtype=np.uint8)
-    _check(load().ddpo_rotate4_u8_host(a.ctypes.data_as(c_void_p), int(a.dtype == np.float32), n, s, s, out.ctypes.data_as(c_void_p)),
-           "ddpo_rotate4_u8_host")
+    _check(load().ddpo_rotate4_u8_host(_np_ptr(a), int(a.dtype == np.float32), n, s, s, _np_ptr(out)), "ddpo_rotate4_u8_host")
     return out
 
 

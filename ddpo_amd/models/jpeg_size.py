@@ -42,7 +42,7 @@ class JpegSizer(DeviceScorer):
         A CUDA tensor is read on this scorer's stream after `ready` — an event recorded on the producing stream once the images were complete;
         default: one recorded now on the caller's current stream — and is referenced here until that work has finished."""
         images, ready = jpeg_images(images, ready, "JpegSizer")
-        L._jpeg_size_args(images.shape, self.quality)
+        L._jpeg_size_args(images, self.quality)
         with self.on_stream(ready):
             if not isinstance(images, torch.Tensor):
                 images = torch.from_numpy(images).to(self.device)

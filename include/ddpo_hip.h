@@ -410,7 +410,7 @@ int ddpo_cosine_rows(const float* a, const float* b, int rows, int cols, float s
 /* JPEG file size without the file (csrc/jpeg_size.hip; additive to ABI v14): bytes_out[n] = len of the baseline JPEG a libjpeg encoder writes for
  *   image n at `quality` (1..100) with its defaults — 4:2:0, standard Huffman tables, one scan, JFIF header — i.e. what PIL's
  *   Image.save(buf, "JPEG", quality=q) returns.  images: N x H x W x 3 (NHWC, contiguous), uint8 or (is_float32) float32 in [0, 1], which is
- *   truncated as (uint8)(x * 255.0f).  H and W must be multiples of 16 (no edge replication / dummy blocks): anything else is DDPO_EINVAL.
+ *   truncated as (uint8)(x * 255.0f) (clamped; NaN -> 0).  H and W must be multiples of 16 (no edge replication / dummy blocks): anything else is DDPO_EINVAL.
  *   All scratch is the caller's `workspace` (device, >= ddpo_jpeg_size_workspace_bytes, 16-byte aligned); the launch sequence zeroes what it needs
  *   on `stream`, so calls on different streams with different workspaces may overlap.  ddpo_jpeg_size_host: the same arithmetic, serially, on
  *   host memory (no GPU).  DDPO_JPEG_FIXED_BYTES: the bytes of such a file that are not entropy-coded data (623 before the scan data + EOI). */

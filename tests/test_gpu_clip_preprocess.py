@@ -73,6 +73,11 @@ def test_wrapper_refusals():
         L.clip_preprocess(torch.zeros(1, 2400, 2400, 3, dtype=torch.uint8, device=DEV), 56, PATCH, KP)
     with pytest.raises(ValueError, match="N x H x W x 3"):
         L.clip_preprocess(x[..., :2].contiguous(), 56, PATCH, KP)
+    wide = torch.full(((56 // PATCH) ** 2, 2 * KP), 7.0, dtype=torch.float32, device=DEV)
+    with pytest.raises(L.DdpoHipError, match="out must be"):             # the right shape, but rows 2 KP apart: the kernel strides by KP
+        L.clip_preprocess(x, 56, PATCH, KP, out=wide[:, :KP])
+    torch.cuda.synchronize()
+    assert bool((wide == 7.0).all())                                       # nothing was launched
 
 
 # ------------------------------------------------------------------------------------------------ scorers

@@ -92,6 +92,35 @@ def test_wrapper_refuses_sizes_off_the_mcu_grid():
         JpegSizer()(np.zeros((1, 24, 40, 3), np.float32))
 
 
+def test_floats_outside_the_unit_interval_follow_the_documented_rule():
+    """float32 -> byte is "truncated as (uint8)(x * 255.0f), clamped; NaN -> 0" for every float, not only those in [0, 1]."""
+    special = {np.nan: 0, np.inf: 255, -np.inf: 0, 1e30: 255, -1e30: 0, -0.0: 0, 1 + 2.0 ** -23: 255, -2.0 ** -149: 0}
+    rng = np.random.default_rng(5)
+    x = rng.random((1, 16, 16, 3), dtype=np.float32)
+    u8 = (x * 255).astype(np.uint8)
+    for i, (v, b) in enumerate(special.items()):
+        for c in range(3):
+            x[0, i, (5 * i + 7 * c) % 16, c], u8[0, i, (5 * i + 7 * c) % 16, c] = v, b
+    assert np.isnan(x).sum() == 3 and np.isinf(x).sum() == 6 and (x == np.float32(1 + 2.0 ** -23)).sum() == 3
+    dev = torch.from_numpy(x).cuda()
+    for q in (50, 95):
+        assert L.jpeg_size(dev, q).tolist() == L.jpeg_size(torch.from_numpy(u8).cuda(), q).tolist() == L.jpeg_size_host(u8, q).tolist()
+        files, lengths = L.jpeg_encode(dev, q)
+        assert bytes(files[0, :int(lengths[0])].cpu().numpy()) == L.jpeg_encode_host(u8, q)[0]
+
+
+def test_wrapper_refuses_an_out_it_would_overrun():
+    x = torch.zeros(2, 16, 16, 3, dtype=torch.uint8, device="cuda")
+    for bad in (torch.full((2,), 7, dtype=torch.int32, device="cuda"), torch.full((1,), 7, dtype=torch.int64, device="cuda"),
+                torch.full((2, 2), 7, dtype=torch.int64, device="cuda")[:, 0]):
+        with pytest.raises(L.DdpoHipError, match="out must be"):
+            L.jpeg_size(x, 95, out=bad)
+        torch.cuda.synchronize()
+        assert bool((bad == 7).all())                                      # nothing was launched
+    good = torch.full((2,), 7, dtype=torch.int64, device="cuda")
+    assert L.jpeg_size(x, 95, out=good) is good and good.tolist() == L.jpeg_size(x, 95).tolist()
+
+
 def test_device_callbacks_equal_the_host_callbacks():
     imgs = np.stack([_as_float(make_image(r, 80 + i, 64, 64)) for i, r in enumerate(RECIPES)])
     prompts = ["x"] * len(imgs)

@@ -37,7 +37,7 @@ def strip_params(n):
 
 print(f"{'VGPR':>5} {'AGPR':>5} {'vspill':>6} {'SGPR':>5} {'sspill':>6} {'occ':>3} {'scratch':>7} {'lds':>6}  kernel")
 for r, n in zip(rows, names):
-    n = strip_params(n)
+    n = strip_params(n.replace("(anonymous namespace)::", ""))          # its '(' is no parameter list
     if flt and flt not in n:
         continue
     print(f"{r.get('VGPRs', '?'):>5} {r.get('AGPRs', '?'):>5} {r.get('VGPRs Spill', '?'):>6} {r.get('TotalSGPRs', '?'):>5} {r.get('SGPRs Spill', '?'):>6} "
