@@ -34,46 +34,14 @@
 //   accumulate apart (channel dc = 32n + 8g + 4h + i in tile n, register group g; row dc + 48 in the SAME lane at (n + 1, g + 2) or (n + 2, g - 2))
 //   and are added in fp32 before the normalisation (attn_store_o).  The bf16x3 variant splits P as well, so stacking V would save it one tile
 //   in six: it keeps its two V^T planes and takes the stacked K only.
-#include "common.h"
+// Vector types, MFMA macros, the packed conversions (never inline assembly: see there), the hi / lo splits and the transposed scatter are
+// attention_x16.h's, shared with the backward (attention_bwd_bf16.hip).
+#include "attention_x16.h"
 #include <cstdlib>
 
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t cvt_pk_bf16_a(float lo, float hi) {      // v_cvt_pk_bf16_f32, selected by the compiler (see cvt_pk_f16_a)
-  const bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(uint32_t, v);
-}
-// Two floats -> packed f16 pair, round to nearest even (v_cvt_pk_f16_f32).  Deliberately NOT inline assembly: the operands are the results
-// of v_exp_f32, a transcendental-unit instruction, and gfx950 needs a wait state between a TRANS result and a VALU consumer — the compiler's
-// hazard recognizer inserts it for instructions it selects itself and does not look inside an asm statement (round 4: the asm form read stale
-// registers whenever the scheduler put the last exponential of a pair directly in front of it: ~10 % errors on long key sequences, NaNs at d = 64).
-__device__ __forceinline__ uint32_t cvt_pk_f16_a(float lo, float hi) {
-  const f16x2 v = {(_Float16)lo, (_Float16)hi};
-  return __builtin_bit_cast(uint32_t, v);
-}
-// two floats -> packed bf16 hi pair and packed bf16 lo pair
-__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = cvt_pk_bf16_a(a, b);
-  lo = cvt_pk_bf16_a(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xFFFF0000u));
-}
-// two floats -> packed f16 hi pair and packed f16 lo pair (the V operand; magnitudes beyond the f16 range saturate)
-__device__ __forceinline__ void split2h(float a, float b, uint32_t& hi, uint32_t& lo) {
-  const float lim = 65504.f;
-  a = fminf(fmaxf(a, -lim), lim);
-  b = fminf(fmaxf(b, -lim), lim);
-  hi = cvt_pk_f16_a(a, b);
-  const f16x2 h = __builtin_bit_cast(f16x2, hi);
-  lo = cvt_pk_f16_a(a - (float)h[0], b - (float)h[1]);
-}
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-#define MFMA32H(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 #define ATTN_P_SHIFT 14.0f            /* p = exp2(s - m + 14): the f16 probabilities use the exponent range [2^-14, 2^14] */
 #define ATTN_F16_ONE 0x3C00u
+#define ATTN_F16_MAX 65504.f             /* the V operand saturates at the f16 maximum */
 
 // Geometry of one 64-key tile's K / V^T image = the LDS picture of every kernel below (byte offsets; the staging code, the packer and the
 // MFMA helpers all take theirs from here).  D = 40 with DKP = 80 selects the stacked layout of the header comment: K hi and lo side by
@@ -111,8 +79,7 @@ __device__ __forceinline__ void attn_image_init(char* smem, int t) {
 template <class I, int D, bool F16P>
 __device__ __forceinline__ void attn_stage_tile(char* smem, const float* kb, int ldk, const float* vb, int ldv, int kt0, int Nk, int t) {
   char* Khi = smem; char* Klo = Khi + I::KLO;
-  uint16_t* vh = reinterpret_cast<uint16_t*>(smem + I::KP);
-  uint16_t* vl = reinterpret_cast<uint16_t*>(smem + I::KP + I::VLO);
+  char* Vhi = smem + I::KP; char* Vlo = Vhi + I::VLO;
   for (int i = t; i < I::KT * (D / 4); i += 256) {
     const int key = i / (D / 4), c4 = i - key * (D / 4);
     float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
@@ -125,13 +92,9 @@ __device__ __forceinline__ void attn_stage_tile(char* smem, const float* kb, int
     split2(kv.z, kv.w, h1, l1);
     *reinterpret_cast<uint2*>(Khi + (key * I::LDK + c4 * 4) * 2) = make_uint2(h0, h1);
     *reinterpret_cast<uint2*>(Klo + (key * I::LDK + c4 * 4) * 2) = make_uint2(l0, l1);
-    if (F16P) { split2h(vv.x, vv.y, h0, l0); split2h(vv.z, vv.w, h1, l1); }
+    if (F16P) { split2h(vv.x, vv.y, h0, l0, ATTN_F16_MAX); split2h(vv.z, vv.w, h1, l1, ATTN_F16_MAX); }
     else { split2(vv.x, vv.y, h0, l0); split2(vv.z, vv.w, h1, l1); }
-    const int d0 = c4 * 4;
-    vh[(d0 + 0) * I::LDVT + key] = (uint16_t)(h0 & 0xFFFFu); vh[(d0 + 1) * I::LDVT + key] = (uint16_t)(h0 >> 16);
-    vh[(d0 + 2) * I::LDVT + key] = (uint16_t)(h1 & 0xFFFFu); vh[(d0 + 3) * I::LDVT + key] = (uint16_t)(h1 >> 16);
-    vl[(d0 + 0) * I::LDVT + key] = (uint16_t)(l0 & 0xFFFFu); vl[(d0 + 1) * I::LDVT + key] = (uint16_t)(l0 >> 16);
-    vl[(d0 + 2) * I::LDVT + key] = (uint16_t)(l1 & 0xFFFFu); vl[(d0 + 3) * I::LDVT + key] = (uint16_t)(l1 >> 16);
+    scatter_tr(Vhi, Vlo, I::LDVT, key, c4 * 4, h0, h1, l0, l1);
   }
 }
 
