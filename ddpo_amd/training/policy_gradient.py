@@ -14,6 +14,9 @@ MI355X design notes
   * the update itself is one fused kernel: 1/(n_acc+1) scaling, global-norm clip, AdamW with bf16 first moment.
   * `--optimizer adafactor` (the table's second row, optax.adafactor(lr, weight_decay_rate)) is five launches over the same flat
     buffers, with a state of 1.9 M floats instead of 6 B/param (lib_optim.py).
+  * `--kl_coef` (not in the reference): kl_coef * KL(policy || frozen pretrained policy) per DDIM step, a closed form in the two noise
+    predictions.  One inference forward of the frozen copy (kl_reference.py) and one additive pass behind the PPO launch (lib_ppo_kl.py),
+    both inside the captured step; with kl_coef == 0 neither exists and the step is the one above, launch for launch.
 """
 import numpy as np
 import torch
@@ -157,10 +160,17 @@ class AccumulatingTrainState:
         return self
 
 
-def _fwd_bwd(state, batch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range, group=None, on_ready=None):
+def _fwd_bwd(state, batch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range, group=None, on_ready=None,
+             kl_coef=0.0, ref_unet=None):
     """U-Net forward (cond + uncond as one batch), scoring-mode log-prob + PPO-clip forward/backward, U-Net backward
     (parameter gradients accumulate in place).  Pure device work: capturable into a HIP graph.
-    `group`: rows per PPO micro-batch when the batch holds several micro-batches (train_steps_fused); info is then (k, 3)."""
+    `group`: rows per PPO micro-batch when the batch holds several micro-batches (train_steps_fused); info is then (k, 3).
+    kl_coef > 0: `ref_unet` (kl_reference.KLReference) runs its inference forward on the same rows and the KL pass adds the penalty's
+    gradient to the PPO gradient and kl_coef * kl to info's loss column; the third result is the per-micro-batch KL (else None)."""
+    if not kl_coef >= 0:
+        raise ValueError(f"kl_coef must be >= 0, got {kl_coef}")
+    if kl_coef > 0 and ref_unet is None:
+        raise ValueError("kl_coef > 0 needs ref_unet: the frozen pretrained policy (training/kl_reference.KLReference)")
     unet = state.unet
     lat = batch["latents"]
     b = lat.shape[0]
@@ -169,33 +179,45 @@ def _fwd_bwd(state, batch, noise_scheduler_state, noise_scheduler, train_cfg, gu
     if train_cfg:
         lat2 = torch.cat([lat, lat])
         ctx2 = torch.cat([batch["uncond_embeds"], batch["prompt_embeds"]]).contiguous()
-        out = unet.forward(lat2, torch.cat([ts, ts]), ctx2, tape=tape)
+        ts2 = torch.cat([ts, ts])
+        out = unet.forward(lat2, ts2, ctx2, tape=tape)
         eps_u, eps_c = out[:b].contiguous(), out[b:].contiguous()
+        if kl_coef > 0:
+            rout = ref_unet.forward(lat2, ts2, ctx2)
+            ref_u, ref_c = rout[:b].contiguous(), rout[b:].contiguous()
     else:
         out = unet.forward(lat, ts, batch["prompt_embeds"], tape=tape)
         eps_u, eps_c = None, out
+        if kl_coef > 0:
+            ref_u, ref_c = None, ref_unet.forward(lat, ts, batch["prompt_embeds"])
     consts = noise_scheduler.kernel_consts(noise_scheduler_state, eta)
     d_c, d_u, per_sample, info = L.ddim_logprob_ppo_fwd_bwd(eps_c, eps_u, lat, batch["next_latents"], ts, batch["log_probs"],
                                                             batch["advantages"], guidance_scale, clip_range, train_cfg, consts,
                                                             group=group)
+    kl = None
+    if kl_coef > 0:
+        from .. import lib_ppo_kl as LK
+        _, kl = LK.ddim_kl_ref_fwd_bwd(eps_c, eps_u, ref_c, ref_u, ts, guidance_scale, kl_coef, train_cfg, consts, d_c, d_u, loss_info=info,
+                                       group=group)
     d_out = torch.cat([d_u, d_c]) if train_cfg else d_c
     unet.backward(tape, d_out, on_ready=on_ready)
-    return info, per_sample
+    return info, per_sample, kl
 
 
 _KEYS = ("latents", "next_latents", "ts", "log_probs", "advantages", "prompt_embeds", "uncond_embeds")
 
 
-def _graphed_fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group=None):
+def _graphed_fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group=None, kl_coef=0.0, ref_unet=None):
     """Replay of _fwd_bwd as a captured HIP graph (one per batch geometry / hyper-parameter set): ~3000 kernel launches per
     micro-step become one graph launch.  Gradients still accumulate into the same flat buffer."""
     key = (tuple(batch["latents"].shape), tuple(batch["prompt_embeds"].shape), bool(train_cfg), float(guidance_scale), float(eta),
            float(clip_range), sched_state.num_inference_steps, L.current_datapath(), group,
-           0 if state.lora is None else state.lora.rank)
+           0 if state.lora is None else state.lora.rank, float(kl_coef), ref_unet is not None)
+    klkw = dict(kl_coef=kl_coef, ref_unet=ref_unet)
     cache = state.__dict__.setdefault("_graphs", {})
     ent = cache.get(key)
     if ent == "eager":
-        return _fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group)
+        return _fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group, **klkw)
     if ent is None:
         static = {k: batch[k].clone() for k in _KEYS}
         gflat = state.grad_acc.flat
@@ -203,33 +225,35 @@ def _graphed_fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale
         side = torch.cuda.Stream(gflat.device)
         side.wait_stream(torch.cuda.current_stream(gflat.device))
         with torch.cuda.stream(side):
-            _fwd_bwd(state, static, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group)      # warm-up (allocations, attrs)
+            _fwd_bwd(state, static, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group, **klkw)      # warm-up (allocations, attrs)
         torch.cuda.current_stream(gflat.device).wait_stream(side)
         try:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                info, per_sample = _fwd_bwd(state, static, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group)
+                info, per_sample, kl = _fwd_bwd(state, static, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group, **klkw)
         except Exception as exc:                # capture is an optimisation only: fall back to eager launches, loudly
             print(f"[ ddpo_amd ] WARNING: HIP-graph capture of train_step failed ({type(exc).__name__}: {exc}); launching eagerly")
             torch.cuda.synchronize(gflat.device)
             gflat.copy_(saved)
             cache[key] = "eager"
-            return _fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group)
+            return _fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group, **klkw)
         gflat.copy_(saved)                      # warm-up passes must not leak into the accumulated gradients
-        ent = (graph, static, info, per_sample)
+        ent = (graph, static, info, per_sample, kl)
         cache[key] = ent
-    graph, static, info, per_sample = ent
+    graph, static, info, per_sample, kl = ent
     for k in _KEYS:
         static[k].copy_(batch[k])
     graph.replay()
-    return info.clone(), per_sample.clone()
+    return info.clone(), per_sample.clone(), None if kl is None else kl.clone()
 
 
 def train_step(state: AccumulatingTrainState, batch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale,
-               eta, clip_range, do_opt_update, jit=True):
+               eta, clip_range, do_opt_update, jit=True, kl_coef=0.0, ref_unet=None):
     """One PPO micro-step (reference :63-146).  batch: latents, next_latents (b,4,h,w), ts (b,) int32, log_probs,
     advantages (b,), prompt_embeds, uncond_embeds (b,77,D) — device tensors.  Returns (state, info) with info a dict
-    of device scalars {approx_kl, clipfrac, loss}."""
+    of device scalars {approx_kl, clipfrac, loss}.
+    kl_coef > 0 (with ref_unet, the frozen pretrained policy): loss includes kl_coef * KL to it and info gains "kl_ref", that KL."""
+    klkw = dict(kl_coef=float(kl_coef), ref_unet=ref_unet) if kl_coef > 0 else {}
     assert isinstance(state, AccumulatingTrainState)
     b = batch["latents"].shape[0]
     assert b == batch["ts"].shape[0] == batch["next_latents"].shape[0] == batch["log_probs"].shape[0]
@@ -239,19 +263,23 @@ def train_step(state: AccumulatingTrainState, batch, noise_scheduler_state, nois
         dbatch["uncond_embeds"] = dbatch["prompt_embeds"]
     bucketer = state.overlap_bucketer() if do_opt_update else None
     if bucketer is not None:
-        info, per_sample = _fwd_bwd(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range,
-                                    on_ready=bucketer.ready)
+        info, per_sample, kl = _fwd_bwd(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range,
+                                        on_ready=bucketer.ready, **klkw)
         bucketer.finish()
     elif jit:
-        info, per_sample = _graphed_fwd_bwd(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range)
+        info, per_sample, kl = _graphed_fwd_bwd(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range,
+                                                **klkw)
     else:
-        info, per_sample = _fwd_bwd(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range)
+        info, per_sample, kl = _fwd_bwd(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range, **klkw)
     state = state.apply_gradients(do_update=do_opt_update, reduced=bucketer is not None)
-    return state, {"approx_kl": info[0], "clipfrac": info[1], "loss": info[2], "log_prob": per_sample[:, 0]}
+    out = {"approx_kl": info[0], "clipfrac": info[1], "loss": info[2], "log_prob": per_sample[:, 0]}
+    if kl is not None:
+        out["kl_ref"] = kl
+    return state, out
 
 
 def train_steps_fused(state: AccumulatingTrainState, batches, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale,
-                      eta, clip_range, do_opt_update, jit=True):
+                      eta, clip_range, do_opt_update, jit=True, kl_coef=0.0, ref_unet=None):
     """k consecutive PPO micro-steps that see the SAME parameters — no optimizer update between them, i.e. any run of
     `train_step(..., do_opt_update=False)` calls optionally closed by one with `do_opt_update=True` — executed as ONE U-Net
     forward/backward over the concatenated rows.  The reference runs them one by one and sums their gradients in
@@ -268,8 +296,9 @@ def train_steps_fused(state: AccumulatingTrainState, batches, noise_scheduler_st
     assert k >= 1
     if k == 1:
         state, info = train_step(state, batches[0], noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta,
-                                 clip_range, do_opt_update, jit=jit)
+                                 clip_range, do_opt_update, jit=jit, kl_coef=kl_coef, ref_unet=ref_unet)
         return state, [info]
+    klkw = dict(kl_coef=float(kl_coef), ref_unet=ref_unet) if kl_coef > 0 else {}
     b = batches[0]["latents"].shape[0]
     for bt in batches:
         assert bt["latents"].shape == batches[0]["latents"].shape and bt["ts"].shape[0] == b
@@ -280,14 +309,14 @@ def train_steps_fused(state: AccumulatingTrainState, batches, noise_scheduler_st
     bucketer = state.overlap_bucketer() if do_opt_update else None
     if bucketer is not None:
         # the launch that closes an optimizer update runs eagerly, with the bucketed gradient all-reduce hanging on the backward's progress
-        info, per_sample = _fwd_bwd(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range, b,
-                                    on_ready=bucketer.ready)
+        info, per_sample, kl = _fwd_bwd(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range, b,
+                                        on_ready=bucketer.ready, **klkw)
         bucketer.finish()
     else:
         fn = _graphed_fwd_bwd if jit else _fwd_bwd
-        info, per_sample = fn(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range, b)
+        info, per_sample, kl = fn(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range, b, **klkw)
     for _ in range(k - 1):
         state = state.apply_gradients(do_update=False)
     state = state.apply_gradients(do_update=do_opt_update, reduced=bucketer is not None)
-    return state, [{"approx_kl": info[j, 0], "clipfrac": info[j, 1], "loss": info[j, 2], "log_prob": per_sample[j * b:(j + 1) * b, 0]}
-                   for j in range(k)]
+    return state, [dict({"approx_kl": info[j, 0], "clipfrac": info[j, 1], "loss": info[j, 2], "log_prob": per_sample[j * b:(j + 1) * b, 0]},
+                        **({} if kl is None else {"kl_ref": kl[j]})) for j in range(k)]

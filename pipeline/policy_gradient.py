@@ -17,6 +17,7 @@ DDPO_DP_SEMANTICS=single_host reproduces the single-host N-device run instead (d
 Differences, all deliberate: trajectories stay in HBM instead of round-tripping through host numpy (:292-295,:415-423);
 gradients are all-reduced once per optimizer update instead of every micro-step (ddpo/training/policy_gradient.py:141);
 `info` is fetched once per inner epoch instead of a blocking device_get + assert_equal per step (:442-445).
+Not in the reference: `--kl_coef c` adds c * KL(policy || frozen pretrained policy) per DDIM step to the PPO loss.
 """
 import json
 import os
@@ -76,6 +77,12 @@ def make_optimizer(args):
     raise NotImplementedError(f"unknown optimizer {args.optimizer!r}: the reference's table has adamw and adafactor")
 
 
+def check_kl_args(args):
+    """A message to exit with, or None: --kl_coef must be finite and >= 0, and a positive one needs --eta > 0 (training/kl_reference.py)."""
+    from ddpo_amd.training.kl_reference import check_kl_args as check
+    return check(getattr(args, "kl_coef", 0.0), args.eta)
+
+
 def check_resume_optimizer(rs, tx, where):
     """A resume bundle carries the moments of the optimizer that wrote it (bundles from before the field existed are AdamW's)."""
     wrote = rs.get("optimizer", "adamw")
@@ -101,6 +108,11 @@ def main(argv=None):
     dp = DataParallel(rank=worker_id, world=n_workers)
     args = Parser(argv).parse_args("pg", process_index=dp.seed_process_index)
     utils.init_logging("policy_gradient", args.verbose)
+
+    bad = check_kl_args(args)
+    if bad:
+        raise SystemExit(bad)
+    kl_coef = float(args.kl_coef)
 
     rng = prng.PRNGKey(args.seed)
     n_devices = 1                                            # one process drives one GPU
@@ -130,9 +142,17 @@ def main(argv=None):
                                  cache=args.cache, device=dev, seed=0)
     with open(f"{localpath}/args.json", "w") as f:      # after loading: says which weights the run really started from
         json.dump(dict(args._dict, synthetic_weights=bool(pipeline.synthetic_weights), weights_source=pipeline.weights_source,
-                       param_dtype=pipeline.param_dtype, datapath=L.DATAPATH, optimizer=args.optimizer), f, indent=4, default=str)
+                       param_dtype=pipeline.param_dtype, datapath=L.DATAPATH, optimizer=args.optimizer, kl_coef=kl_coef), f, indent=4,
+                  default=str)
     pipeline.safety_checker = None
     unet, vae = pipeline.unet, pipeline.vae
+    ref_unet = None
+    if kl_coef > 0:
+        # the frozen pretrained policy of the KL penalty: a copy taken NOW, before LoRA adapters are attached and before DDPO_RESUME
+        # overwrites anything, so a resumed or adapted run is still held to the pretrained_model weights
+        from ddpo_amd.training.kl_reference import KLReference
+        ref_unet = KLReference(unet)
+        print(f"[ policy_gradient ] kl_coef {kl_coef:g}: frozen reference U-Net of {ref_unet.params.n_params} parameters")
     noise_scheduler_state = pipeline.scheduler.set_timesteps(params["scheduler"], num_inference_steps=args.n_inference_steps)
 
     # ------------------------------- optimizer --------------------------------#
@@ -169,7 +189,7 @@ def main(argv=None):
     if args.per_prompt_stats_bufsize is not None:
         per_prompt_stats = PerPromptStatTracker(args.per_prompt_stats_bufsize, args.per_prompt_stats_min_count)
 
-    mean_rewards, std_rewards, wall = [], [], []
+    mean_rewards, std_rewards, wall, kl_ref_epochs = [], [], [], []
     t_start = time.time()
     start_epoch = 0
     if os.environ.get("DDPO_RESUME"):
@@ -276,6 +296,7 @@ def main(argv=None):
         devs["advantages"] = torch.as_tensor(np.asarray(advantages, dtype=np.float32).reshape(-1)).to(dev)
         devs = dp.gather_global(devs, args.num_sample_batches_per_epoch)      # single_host: the per-epoch trajectory exchange
 
+        inner_kl = []
         for inner_epoch in range(args.num_inner_epochs):
             total_batch_size, num_timesteps = devs["log_probs"].shape
             assert total_batch_size == args.num_sample_batches_per_epoch * n_devices * args.sample_batch_size * (n_workers if dp.single_host else 1)
@@ -292,6 +313,7 @@ def main(argv=None):
             num_train_ts = int(num_timesteps * args.train_timestep_ratio)
             n_mini = total_batch_size // (n_devices * args.train_batch_size)
             all_infos = []
+            info_keys = ("approx_kl", "clipfrac", "loss") + (("kl_ref",) if kl_coef > 0 else ())
             do_opt_update = False
             train_fuse = train_fuse_default(args.train_batch_size * (2 if args.train_cfg else 1),
                                             mine["latents"].shape[-1] * mine["latents"].shape[-2])
@@ -310,8 +332,9 @@ def main(argv=None):
                     if do_opt_update:
                         print(f"opt update at {i}, {js[-1]}")
                     state, infos_k = train_steps_fused(state, batches, noise_scheduler_state, pipeline.scheduler, args.train_cfg,
-                                                       args.guidance_scale, args.eta, args.ppo_clip_range, do_opt_update)
-                    all_infos += [torch.stack([info["approx_kl"], info["clipfrac"], info["loss"]]) for info in infos_k]
+                                                       args.guidance_scale, args.eta, args.ppo_clip_range, do_opt_update,
+                                                       kl_coef=kl_coef, ref_unet=ref_unet)
+                    all_infos += [torch.stack([info[k] for k in info_keys]) for info in infos_k]
                 for j in (range(num_train_ts) if train_fuse <= 1 else ()):
                     batch = {"prompt_embeds": mine["embeds"][sl], "uncond_embeds": train_uncond_prompt_embeds,
                              "advantages": mine["advantages"][sl], "latents": mine["latents"][sl, j],
@@ -322,18 +345,23 @@ def main(argv=None):
                     if do_opt_update:
                         print(f"opt update at {i}, {j}")
                     state, info = train_step(state, batch, noise_scheduler_state, pipeline.scheduler, args.train_cfg,
-                                             args.guidance_scale, args.eta, args.ppo_clip_range, do_opt_update)
-                    all_infos.append(torch.stack([info["approx_kl"], info["clipfrac"], info["loss"]]))
+                                             args.guidance_scale, args.eta, args.ppo_clip_range, do_opt_update,
+                                             kl_coef=kl_coef, ref_unet=ref_unet)
+                    all_infos.append(torch.stack([info[k] for k in info_keys]))
             assert do_opt_update
             infos = torch.stack(all_infos).cpu().numpy()            # ONE host sync per inner epoch
             if n_workers > 1:
                 infos = D.allgather_array(infos[None]).mean(0)       # lax.pmean(info)
-            all_infos = {"approx_kl": infos[:, 0], "clipfrac": infos[:, 1], "loss": infos[:, 2]}
+            all_infos = {k: infos[:, c] for c, k in enumerate(info_keys)}
+            if kl_coef > 0:
+                inner_kl.append(float(all_infos["kl_ref"].mean()))
             print(f"mean info: { {k: float(v.mean()) for k, v in all_infos.items()} } | "
                   f"{len(infos)} train steps in {time.time() - t_train:.2f}s")
             if worker_id == 0:
                 np.save(utils.fs.join_and_create(localpath, f"train_info/{worker_id}_{epoch}_{inner_epoch}.npy"), all_infos)
 
+        if kl_coef > 0:
+            kl_ref_epochs.append(float(np.mean(inner_kl)))
         if (epoch + 1) % args.save_freq == 0 or epoch == args.num_train_epochs - 1:
             save_rank_resume(os.path.join(args.savepath, "checkpoints"), epoch, worker_id,
                              {"sample_rng": sample_rng, "py_random": random.getstate(), "np_random": np.random.get_state()})
@@ -371,7 +399,10 @@ def main(argv=None):
             except ImportError:
                 pass
     executor.shutdown()
-    return {"mean_rewards": mean_rewards, "localpath": localpath, "state": state}
+    out = {"mean_rewards": mean_rewards, "localpath": localpath, "state": state}
+    if kl_coef > 0:
+        out["kl_ref"] = kl_ref_epochs            # per epoch run by this call: mean KL to the pretrained policy over its train steps
+    return out
 
 
 if __name__ == "__main__":
