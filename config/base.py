@@ -34,6 +34,13 @@ _PG_DEFAULTS = (
     # DESIGN.md §4): loss += kl_coef * KL(policy || pretrained) per DDIM step, in the units of the PPO loss.  0 = off (the reference's
     # only mode): no second U-Net is built and the training step is unchanged.  Needs eta > 0.
     ("kl_coef", 0.0),
+    # engine-specific addition: the training objective.  "ppo" = the reference's only mode.  "d3po" (Yang et al., "Using Human Feedback to
+    # Fine-tune Diffusion Models without Any Reward Model"): prompts are drawn once per two adjacent rows, the pair is ranked by
+    # the sign of its reward difference and a DPO loss is applied per DDIM step on the policy-to-pretrained log-ratio; rewards' scale, the
+    # per-prompt tracker, the stored log-probs and ppo_clip_range are not used.  Needs eta > 0 and even sample / train batch sizes.
+    # d3po_beta 0.1 is the value the D3PO authors ship (their log-prob is a mean over the latent, as here); it has not been measured in a
+    # training run on this engine.
+    ("pg_loss", "ppo"), ("d3po_beta", 0.1),
 )
 
 _SAMPLE_DEFAULTS = (

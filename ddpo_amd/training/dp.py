@@ -65,13 +65,17 @@ class DataParallel:
         return sample_seeds[self.rank if self.single_host else 0]
 
     # ------------------------------------------------------------------ prompts
-    def make_prompts(self, prompt_fn, per_rank_batch, identical_batch=False, **kwargs):
+    def make_prompts(self, prompt_fn, per_rank_batch, identical_batch=False, pairs=False, **kwargs):
         """This rank's (sample_prompts, training_prompts, prompt_metadata).  single_host: every rank draws the prompts of all
         `world * per_rank_batch` samples from its (identically seeded) `random` stream — device d owns block d, the `shard`
-        reshape of ddpo/utils/preprocessing.py:35-49 — so the streams stay in lockstep on all ranks."""
+        reshape of ddpo/utils/preprocessing.py:35-49 — so the streams stay in lockstep on all ranks.
+        pairs: one draw per two adjacent rows (prompts.make_prompts); per_rank_batch is even, so a pair never straddles two ranks."""
+        pkw = dict(pairs=True) if pairs else {}
         if not self.single_host:
-            return _make_prompts(prompt_fn, per_rank_batch, identical_batch, **kwargs)
-        p, t, m = _make_prompts(prompt_fn, self.world * per_rank_batch, identical_batch, **kwargs)
+            return _make_prompts(prompt_fn, per_rank_batch, identical_batch, **pkw, **kwargs)
+        if pairs and per_rank_batch % 2:
+            raise ValueError(f"pairs need an even per-rank batch, got {per_rank_batch}")
+        p, t, m = _make_prompts(prompt_fn, self.world * per_rank_batch, identical_batch, **pkw, **kwargs)
         sl = slice(self.rank * per_rank_batch, (self.rank + 1) * per_rank_batch)
         return list(p[sl]), list(t[sl]), list(m[sl])
 
@@ -111,28 +115,43 @@ class DataParallel:
         return {k: (v if k == "advantages" else D.allgather_tensor(v)[order]) for k, v in devs.items()}
 
     @staticmethod
-    def shuffle(devs, np_random=np.random):
+    def _draw_permutations(total, T, pairs, np_random):
+        """The numpy draws of one shuffle as (perm (total,), perms (total, T)) over rows.  pairs: one permutation over the total / 2 adjacent
+        pairs, then one time permutation per pair, each applied to both of its rows — the pair stays adjacent and its two rows show the same
+        step index at every position."""
+        if not pairs:
+            return np_random.permutation(total), np.array([np_random.permutation(T) for _ in range(total)])
+        if total % 2:
+            raise ValueError(f"pairs need an even number of rows, got {total}")
+        pperm = np_random.permutation(total // 2)
+        perm = np.stack([2 * pperm, 2 * pperm + 1], 1).reshape(-1)
+        return perm, np.repeat(np.array([np_random.permutation(T) for _ in range(total // 2)]), 2, axis=0)
+
+    @staticmethod
+    def shuffle(devs, np_random=np.random, pairs=False):
         """pipeline/policy_gradient.py:385-393: one permutation of the batch, then one permutation of time per sample, drawn from
-        the numpy stream in that order; applied on the tensors' device."""
+        the numpy stream in that order; applied on the tensors' device.  pairs: see _draw_permutations."""
         total, T = devs["log_probs"].shape
         dev = devs["log_probs"].device
-        perm = torch.as_tensor(np_random.permutation(total), device=dev)
+        perm, perms = DataParallel._draw_permutations(total, T, pairs, np_random)
+        perm = torch.as_tensor(perm, device=dev)
         out = {k: v[perm] for k, v in devs.items()}
-        perms = torch.as_tensor(np.array([np_random.permutation(T) for _ in range(total)]), device=dev)
+        perms = torch.as_tensor(perms, device=dev)
         rows = torch.arange(total, device=dev)[:, None]
         for k in ("latents", "next_latents", "log_probs", "ts"):
             out[k] = out[k][rows, perms]
         return out
 
-    def shuffled_rows(self, devs, train_batch_size, np_random=np.random):
+    def shuffled_rows(self, devs, train_batch_size, np_random=np.random, pairs=False):
         """`my_rows(shuffle(devs))` without materialising the shuffled GLOBAL set: the numpy stream is drawn exactly as `shuffle` draws it (one
         batch permutation, then one time permutation per sample of the whole set), but only this rank's rows are gathered.  single_host with
         num_inner_epochs == 1 (the default) uses it so that a rank holds the gathered global copy plus its own rows, not two global copies
         (an inner epoch after the first shuffles the already shuffled set, which needs the full copy: `shuffle` + `my_rows`)."""
         total, T = devs["log_probs"].shape
         dev = devs["log_probs"].device
-        perm = np_random.permutation(total)
-        perms = np.array([np_random.permutation(T) for _ in range(total)])
+        perm, perms = self._draw_permutations(total, T, pairs, np_random)
+        if pairs and train_batch_size % 2:
+            raise ValueError(f"pairs need an even train_batch_size, got {train_batch_size}")
         if self.single_host and self.world > 1:
             assert total % (self.world * train_batch_size) == 0
             mine = np.arange(total).reshape(-1, self.world, train_batch_size)[:, self.rank].reshape(-1)

@@ -17,6 +17,9 @@ MI355X design notes
   * `--kl_coef` (not in the reference): kl_coef * KL(policy || frozen pretrained policy) per DDIM step, a closed form in the two noise
     predictions.  One inference forward of the frozen copy (kl_reference.py) and one additive pass behind the PPO launch (lib_ppo_kl.py),
     both inside the captured step; with kl_coef == 0 neither exists and the step is the one above, launch for launch.
+  * `--pg_loss d3po` (not in the reference): a DPO loss per DDIM step on adjacent row pairs ranked by preference, on the policy-to-pretrained
+    log-ratio of each stored transition (lib_pref.py).  Its pass stands in the place of the PPO launch and reads the same
+    frozen forward a KL penalty would; with the default `ppo` none of it is imported or launched.
 """
 import numpy as np
 import torch
@@ -31,6 +34,8 @@ ADV_CLIP_MAX = 10.0
 # sample-timesteps/s on one box (profiles/r02_ab_train_fuse.log; k = 1: 28).  The default 50 timesteps run as 16 + 16 + 16 + 2.
 # DDPO_TRAIN_FUSE=1 restores one launch per micro-step.
 DEFAULT_TRAIN_FUSE = 16
+LOSSES = ("ppo", "d3po")
+D3PO_BETA = 0.1          # config/base.py `d3po_beta`: the D3PO authors' shipped value
 
 
 def train_fuse_default(unet_rows_per_micro_step=None, latent_pixels=None):
@@ -161,16 +166,25 @@ class AccumulatingTrainState:
 
 
 def _fwd_bwd(state, batch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range, group=None, on_ready=None,
-             kl_coef=0.0, ref_unet=None):
+             kl_coef=0.0, ref_unet=None, loss="ppo", d3po_beta=None):
     """U-Net forward (cond + uncond as one batch), scoring-mode log-prob + PPO-clip forward/backward, U-Net backward
     (parameter gradients accumulate in place).  Pure device work: capturable into a HIP graph.
     `group`: rows per PPO micro-batch when the batch holds several micro-batches (train_steps_fused); info is then (k, 3).
     kl_coef > 0: `ref_unet` (kl_reference.KLReference) runs its inference forward on the same rows and the KL pass adds the penalty's
-    gradient to the PPO gradient and kl_coef * kl to info's loss column; the third result is the per-micro-batch KL (else None)."""
+    gradient to the PPO gradient and kl_coef * kl to info's loss column; the third result is the per-micro-batch KL (else None).
+    loss == "d3po": the preference-pair pass (lib_pref.py) stands in the place of the PPO launch; batch["advantages"] carries the labels
+    (+1 winner, -1 loser, 0 tie; rows in adjacent pairs), batch["log_probs"] is not read, info is {pref_acc, pref_margin, loss} and the second
+    result is per_pair (b / 2, 4).  The one frozen forward serves this pass and the KL pass alike."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+    d3po = loss == "d3po"
     if not kl_coef >= 0:
         raise ValueError(f"kl_coef must be >= 0, got {kl_coef}")
     if kl_coef > 0 and ref_unet is None:
         raise ValueError("kl_coef > 0 needs ref_unet: the frozen pretrained policy (training/kl_reference.KLReference)")
+    if d3po and ref_unet is None:
+        raise ValueError("loss 'd3po' needs ref_unet: the frozen pretrained policy (training/kl_reference.KLReference)")
+    need_ref = d3po or kl_coef > 0
     unet = state.unet
     lat = batch["latents"]
     b = lat.shape[0]
@@ -182,18 +196,24 @@ def _fwd_bwd(state, batch, noise_scheduler_state, noise_scheduler, train_cfg, gu
         ts2 = torch.cat([ts, ts])
         out = unet.forward(lat2, ts2, ctx2, tape=tape)
         eps_u, eps_c = out[:b].contiguous(), out[b:].contiguous()
-        if kl_coef > 0:
+        if need_ref:
             rout = ref_unet.forward(lat2, ts2, ctx2)
             ref_u, ref_c = rout[:b].contiguous(), rout[b:].contiguous()
     else:
         out = unet.forward(lat, ts, batch["prompt_embeds"], tape=tape)
         eps_u, eps_c = None, out
-        if kl_coef > 0:
+        if need_ref:
             ref_u, ref_c = None, ref_unet.forward(lat, ts, batch["prompt_embeds"])
     consts = noise_scheduler.kernel_consts(noise_scheduler_state, eta)
-    d_c, d_u, per_sample, info = L.ddim_logprob_ppo_fwd_bwd(eps_c, eps_u, lat, batch["next_latents"], ts, batch["log_probs"],
-                                                            batch["advantages"], guidance_scale, clip_range, train_cfg, consts,
-                                                            group=group)
+    if d3po:
+        from .. import lib_pref as LP
+        d_c, d_u, per_sample, info = LP.ddim_pref_fwd_bwd(eps_c, eps_u, ref_c, ref_u, lat, batch["next_latents"], ts, batch["advantages"],
+                                                          guidance_scale, D3PO_BETA if d3po_beta is None else d3po_beta, train_cfg, consts,
+                                                          group=group)
+    else:
+        d_c, d_u, per_sample, info = L.ddim_logprob_ppo_fwd_bwd(eps_c, eps_u, lat, batch["next_latents"], ts, batch["log_probs"],
+                                                                batch["advantages"], guidance_scale, clip_range, train_cfg, consts,
+                                                                group=group)
     kl = None
     if kl_coef > 0:
         from .. import lib_ppo_kl as LK
@@ -207,13 +227,17 @@ def _fwd_bwd(state, batch, noise_scheduler_state, noise_scheduler, train_cfg, gu
 _KEYS = ("latents", "next_latents", "ts", "log_probs", "advantages", "prompt_embeds", "uncond_embeds")
 
 
-def _graphed_fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group=None, kl_coef=0.0, ref_unet=None):
+def _graphed_fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group=None, kl_coef=0.0, ref_unet=None,
+                     loss="ppo", d3po_beta=None):
     """Replay of _fwd_bwd as a captured HIP graph (one per batch geometry / hyper-parameter set): ~3000 kernel launches per
     micro-step become one graph launch.  Gradients still accumulate into the same flat buffer."""
     key = (tuple(batch["latents"].shape), tuple(batch["prompt_embeds"].shape), bool(train_cfg), float(guidance_scale), float(eta),
            float(clip_range), sched_state.num_inference_steps, L.current_datapath(), group,
            0 if state.lora is None else state.lora.rank, float(kl_coef), ref_unet is not None)
     klkw = dict(kl_coef=kl_coef, ref_unet=ref_unet)
+    if loss != "ppo":
+        key += (loss, float(D3PO_BETA if d3po_beta is None else d3po_beta))
+        klkw.update(loss=loss, d3po_beta=d3po_beta)
     cache = state.__dict__.setdefault("_graphs", {})
     ent = cache.get(key)
     if ent == "eager":
@@ -247,16 +271,44 @@ def _graphed_fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale
     return info.clone(), per_sample.clone(), None if kl is None else kl.clone()
 
 
+def _loss_kwargs(kl_coef, ref_unet, loss, d3po_beta):
+    """Keyword arguments of _fwd_bwd beyond the default step's: none at all for PPO without a penalty."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+    kw = dict(kl_coef=float(kl_coef), ref_unet=ref_unet) if kl_coef > 0 else {}
+    if loss != "ppo":
+        kw.update(loss=loss, d3po_beta=d3po_beta, ref_unet=ref_unet)
+    return kw
+
+
+def _with_log_probs(batch, loss):
+    """d3po never reads the stored log-probs: a batch without them gets a placeholder so the static graph inputs keep one layout."""
+    if loss == "ppo" or "log_probs" in batch:
+        return batch
+    return dict(batch, log_probs=torch.zeros_like(batch["advantages"], dtype=torch.float32))
+
+
+def _info_dict(loss, info, per_sample, rows=None):
+    """One micro-batch's info row as the dict train_step returns.  `rows`: its slice of the per-row results (fused steps)."""
+    if loss == "d3po":
+        return {"pref_acc": info[0], "pref_margin": info[1], "loss": info[2]}
+    return {"approx_kl": info[0], "clipfrac": info[1], "loss": info[2], "log_prob": per_sample[:, 0] if rows is None else per_sample[rows, 0]}
+
+
 def train_step(state: AccumulatingTrainState, batch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale,
-               eta, clip_range, do_opt_update, jit=True, kl_coef=0.0, ref_unet=None):
+               eta, clip_range, do_opt_update, jit=True, kl_coef=0.0, ref_unet=None, loss="ppo", d3po_beta=None):
     """One PPO micro-step (reference :63-146).  batch: latents, next_latents (b,4,h,w), ts (b,) int32, log_probs,
     advantages (b,), prompt_embeds, uncond_embeds (b,77,D) — device tensors.  Returns (state, info) with info a dict
     of device scalars {approx_kl, clipfrac, loss}.
-    kl_coef > 0 (with ref_unet, the frozen pretrained policy): loss includes kl_coef * KL to it and info gains "kl_ref", that KL."""
-    klkw = dict(kl_coef=float(kl_coef), ref_unet=ref_unet) if kl_coef > 0 else {}
+    kl_coef > 0 (with ref_unet, the frozen pretrained policy): loss includes kl_coef * KL to it and info gains "kl_ref", that KL.
+    loss="d3po" (with ref_unet): rows are adjacent preference pairs, batch["advantages"] their labels (+1 / -1 / 0), batch["log_probs"] is
+    ignored and may be absent; info is {pref_acc, pref_margin, loss} (+ kl_ref), d3po_beta the DPO temperature (default D3PO_BETA)."""
+    klkw = _loss_kwargs(kl_coef, ref_unet, loss, d3po_beta)
     assert isinstance(state, AccumulatingTrainState)
     b = batch["latents"].shape[0]
-    assert b == batch["ts"].shape[0] == batch["next_latents"].shape[0] == batch["log_probs"].shape[0]
+    assert b == batch["ts"].shape[0] == batch["next_latents"].shape[0] == batch["advantages"].shape[0]
+    batch = _with_log_probs(batch, loss)
+    assert b == batch["log_probs"].shape[0]
     dbatch = {k: batch[k].contiguous() for k in _KEYS if k in batch}
     dbatch["ts"] = dbatch["ts"].to(torch.int32)
     if not train_cfg and "uncond_embeds" not in dbatch:
@@ -272,14 +324,14 @@ def train_step(state: AccumulatingTrainState, batch, noise_scheduler_state, nois
     else:
         info, per_sample, kl = _fwd_bwd(state, dbatch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range, **klkw)
     state = state.apply_gradients(do_update=do_opt_update, reduced=bucketer is not None)
-    out = {"approx_kl": info[0], "clipfrac": info[1], "loss": info[2], "log_prob": per_sample[:, 0]}
+    out = _info_dict(loss, info, per_sample)
     if kl is not None:
         out["kl_ref"] = kl
     return state, out
 
 
 def train_steps_fused(state: AccumulatingTrainState, batches, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale,
-                      eta, clip_range, do_opt_update, jit=True, kl_coef=0.0, ref_unet=None):
+                      eta, clip_range, do_opt_update, jit=True, kl_coef=0.0, ref_unet=None, loss="ppo", d3po_beta=None):
     """k consecutive PPO micro-steps that see the SAME parameters — no optimizer update between them, i.e. any run of
     `train_step(..., do_opt_update=False)` calls optionally closed by one with `do_opt_update=True` — executed as ONE U-Net
     forward/backward over the concatenated rows.  The reference runs them one by one and sums their gradients in
@@ -290,15 +342,17 @@ def train_steps_fused(state: AccumulatingTrainState, batches, noise_scheduler_st
     (`ddpo_ddim_logprob_ppo_fwd_bwd` with `group`) and its own info row, and n_acc advances by k.
 
     batches: list of k dicts as for `train_step`, all with the same shapes.  `do_opt_update` applies after the LAST one.
+    `loss` / `d3po_beta` as for `train_step`: with "d3po" every micro-batch is a whole number of adjacent preference pairs.
     Returns (state, [info_0, ..., info_{k-1}])."""
     assert isinstance(state, AccumulatingTrainState)
     k = len(batches)
     assert k >= 1
     if k == 1:
         state, info = train_step(state, batches[0], noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta,
-                                 clip_range, do_opt_update, jit=jit, kl_coef=kl_coef, ref_unet=ref_unet)
+                                 clip_range, do_opt_update, jit=jit, kl_coef=kl_coef, ref_unet=ref_unet, loss=loss, d3po_beta=d3po_beta)
         return state, [info]
-    klkw = dict(kl_coef=float(kl_coef), ref_unet=ref_unet) if kl_coef > 0 else {}
+    klkw = _loss_kwargs(kl_coef, ref_unet, loss, d3po_beta)
+    batches = [_with_log_probs(bt, loss) for bt in batches]
     b = batches[0]["latents"].shape[0]
     for bt in batches:
         assert bt["latents"].shape == batches[0]["latents"].shape and bt["ts"].shape[0] == b
@@ -318,5 +372,5 @@ def train_steps_fused(state: AccumulatingTrainState, batches, noise_scheduler_st
     for _ in range(k - 1):
         state = state.apply_gradients(do_update=False)
     state = state.apply_gradients(do_update=do_opt_update, reduced=bucketer is not None)
-    return state, [dict({"approx_kl": info[j, 0], "clipfrac": info[j, 1], "loss": info[j, 2], "log_prob": per_sample[j * b:(j + 1) * b, 0]},
-                        **({} if kl is None else {"kl_ref": kl[j]})) for j in range(k)]
+    return state, [dict(_info_dict(loss, info[j], per_sample, slice(j * b, (j + 1) * b)), **({} if kl is None else {"kl_ref": kl[j]}))
+                   for j in range(k)]

@@ -90,12 +90,18 @@ def register(fn):
     return fn
 
 
-def make_prompts(fn_name, batch_size, identical_batch=False, **kwargs):
+def make_prompts(fn_name, batch_size, identical_batch=False, pairs=False, **kwargs):
+    """pairs (not in the reference; `--pg_loss d3po`): batch_size / 2 draws, each repeated on two adjacent rows — the two trajectories of one
+    prompt that a preference label compares.  `identical_batch` is unchanged by it."""
     prompt_fn = globals()[fn_name]
+    if pairs and batch_size % 2:
+        raise ValueError(f"pairs need an even batch, got {batch_size}")
     if identical_batch:
         prompt, training, meta = prompt_fn(**kwargs)
         return [prompt] * batch_size, [training] * batch_size, [meta] * batch_size
-    drawn = [prompt_fn(**kwargs) for _ in range(batch_size)]
+    drawn = [prompt_fn(**kwargs) for _ in range(batch_size // 2 if pairs else batch_size)]
+    if pairs:
+        drawn = [d for d in drawn for _ in range(2)]
     prompts, training, meta = zip(*drawn)
     return list(prompts), training, meta
 

@@ -17,7 +17,9 @@ DDPO_DP_SEMANTICS=single_host reproduces the single-host N-device run instead (d
 Differences, all deliberate: trajectories stay in HBM instead of round-tripping through host numpy (:292-295,:415-423);
 gradients are all-reduced once per optimizer update instead of every micro-step (ddpo/training/policy_gradient.py:141);
 `info` is fetched once per inner epoch instead of a blocking device_get + assert_equal per step (:442-445).
-Not in the reference: `--kl_coef c` adds c * KL(policy || frozen pretrained policy) per DDIM step to the PPO loss.
+Not in the reference: `--kl_coef c` adds c * KL(policy || frozen pretrained policy) per DDIM step to the PPO loss (DESIGN.md §4);
+`--pg_loss d3po` trains on preference pairs instead: prompts are drawn once per two adjacent rows, each pair is ranked by the sign of its reward
+difference, and a DPO loss per DDIM step on the policy-to-pretrained log-ratio stands in the place of PPO-clip.
 """
 import json
 import os
@@ -83,6 +85,15 @@ def check_kl_args(args):
     return check(getattr(args, "kl_coef", 0.0), args.eta)
 
 
+def check_d3po_args(args):
+    """A message to exit with, or None: --pg_loss d3po needs --eta > 0, a finite --d3po_beta > 0 and even batch sizes (training/preference.py)."""
+    pg_loss = getattr(args, "pg_loss", "ppo")
+    if pg_loss == "ppo":
+        return None
+    from ddpo_amd.training.preference import check_d3po_args as check
+    return check(pg_loss, getattr(args, "d3po_beta", 0.1), args.eta, args.sample_batch_size, args.train_batch_size)
+
+
 def check_resume_optimizer(rs, tx, where):
     """A resume bundle carries the moments of the optimizer that wrote it (bundles from before the field existed are AdamW's)."""
     wrote = rs.get("optimizer", "adamw")
@@ -109,10 +120,14 @@ def main(argv=None):
     args = Parser(argv).parse_args("pg", process_index=dp.seed_process_index)
     utils.init_logging("policy_gradient", args.verbose)
 
-    bad = check_kl_args(args)
+    bad = check_kl_args(args) or check_d3po_args(args)
     if bad:
         raise SystemExit(bad)
     kl_coef = float(args.kl_coef)
+    d3po = args.pg_loss == "d3po"
+    # keyword arguments of the prompt draw, the shuffles and the training step beyond the default run's: none at all for --pg_loss ppo
+    pairkw = dict(pairs=True) if d3po else {}
+    losskw = dict(loss="d3po", d3po_beta=float(args.d3po_beta)) if d3po else {}
 
     rng = prng.PRNGKey(args.seed)
     n_devices = 1                                            # one process drives one GPU
@@ -142,17 +157,18 @@ def main(argv=None):
                                  cache=args.cache, device=dev, seed=0)
     with open(f"{localpath}/args.json", "w") as f:      # after loading: says which weights the run really started from
         json.dump(dict(args._dict, synthetic_weights=bool(pipeline.synthetic_weights), weights_source=pipeline.weights_source,
-                       param_dtype=pipeline.param_dtype, datapath=L.DATAPATH, optimizer=args.optimizer, kl_coef=kl_coef), f, indent=4,
+                       param_dtype=pipeline.param_dtype, datapath=L.DATAPATH, optimizer=args.optimizer, kl_coef=kl_coef,
+                       pg_loss=args.pg_loss, d3po_beta=float(args.d3po_beta)), f, indent=4,
                   default=str)
     pipeline.safety_checker = None
     unet, vae = pipeline.unet, pipeline.vae
     ref_unet = None
-    if kl_coef > 0:
-        # the frozen pretrained policy of the KL penalty: a copy taken NOW, before LoRA adapters are attached and before DDPO_RESUME
+    if kl_coef > 0 or d3po:
+        # the frozen pretrained policy of the KL penalty and of the preference loss (one copy serves both): taken taken NOW, before LoRA adapters are attached and before DDPO_RESUME
         # overwrites anything, so a resumed or adapted run is still held to the pretrained_model weights
         from ddpo_amd.training.kl_reference import KLReference
         ref_unet = KLReference(unet)
-        print(f"[ policy_gradient ] kl_coef {kl_coef:g}: frozen reference U-Net of {ref_unet.params.n_params} parameters")
+        print(f"[ policy_gradient ] kl_coef {kl_coef:g}, pg_loss {args.pg_loss}: frozen reference U-Net of {ref_unet.params.n_params} parameters")
     noise_scheduler_state = pipeline.scheduler.set_timesteps(params["scheduler"], num_inference_steps=args.n_inference_steps)
 
     # ------------------------------- optimizer --------------------------------#
@@ -189,7 +205,7 @@ def main(argv=None):
     if args.per_prompt_stats_bufsize is not None:
         per_prompt_stats = PerPromptStatTracker(args.per_prompt_stats_bufsize, args.per_prompt_stats_min_count)
 
-    mean_rewards, std_rewards, wall, kl_ref_epochs = [], [], [], []
+    mean_rewards, std_rewards, wall, kl_ref_epochs, pref_acc_epochs = [], [], [], [], []
     t_start = time.time()
     start_epoch = 0
     if os.environ.get("DDPO_RESUME"):
@@ -236,7 +252,7 @@ def main(argv=None):
         for i in range(args.num_sample_batches_per_epoch):
             # ----------------------------- make prompts ----------------------------- #
             sample_prompts, training_prompts, prompt_metadata = dp.make_prompts(
-                args.prompt_fn, n_devices * args.sample_batch_size, args.identical_batch, evaluate=args.evaluate, **args.prompt_kwargs)
+                args.prompt_fn, n_devices * args.sample_batch_size, args.identical_batch, evaluate=args.evaluate, **pairkw, **args.prompt_kwargs)
             # ----------------------------- sample ----------------------------- #
             sample_rng, sample_seed = prng.split(sample_rng)
             sample_seeds = prng.split(sample_seed, dp.n_key_devices)
@@ -277,7 +293,11 @@ def main(argv=None):
 
         # allgather rewards (for multi-process training)
         rewards, prompts = dp.gather_rewards(host["rewards"], host["prompts"].tolist(), args.num_sample_batches_per_epoch)
-        if per_prompt_stats is not None:
+        if d3po:
+            # labels in the place of advantages: the sign of each adjacent pair's reward difference; no tracker, no normalisation
+            from ddpo_amd.training.preference import pair_labels
+            advantages = pair_labels(rewards)
+        elif per_prompt_stats is not None:
             advantages = per_prompt_stats.update(prompts, rewards)
             if worker_id == 0:
                 np.save(utils.fs.join_and_create(localpath, f"per_prompt_stats/{worker_id}_{epoch}.npy"), per_prompt_stats.get_stats())
@@ -293,27 +313,29 @@ def main(argv=None):
         np.save(utils.fs.join_and_create(localpath, f"rewards/{worker_id}_{epoch}.npy"), host["rewards"])
         np.save(utils.fs.join_and_create(localpath, f"prompts/{worker_id}_{epoch}.npy"), host["prompts"])
         np.save(utils.fs.join_and_create(localpath, f"callback_info/{worker_id}_{epoch}.npy"), callback_info)
+        if d3po:
+            np.save(utils.fs.join_and_create(localpath, f"pref_labels/{worker_id}_{epoch}.npy"), np.asarray(advantages, dtype=np.float32))
         devs["advantages"] = torch.as_tensor(np.asarray(advantages, dtype=np.float32).reshape(-1)).to(dev)
         devs = dp.gather_global(devs, args.num_sample_batches_per_epoch)      # single_host: the per-epoch trajectory exchange
 
-        inner_kl = []
+        inner_kl, inner_acc = [], []
         for inner_epoch in range(args.num_inner_epochs):
             total_batch_size, num_timesteps = devs["log_probs"].shape
             assert total_batch_size == args.num_sample_batches_per_epoch * n_devices * args.sample_batch_size * (n_workers if dp.single_host else 1)
             assert num_timesteps == args.n_inference_steps
             # shuffle samples along the batch dimension, then along time independently for each sample; keep this rank's rows
             if args.num_inner_epochs == 1:
-                mine = dp.shuffled_rows(devs, args.train_batch_size)          # same draws, only this rank's rows gathered
+                mine = dp.shuffled_rows(devs, args.train_batch_size, **pairkw)          # same draws, only this rank's rows gathered
                 if dp.single_host:
                     devs = None                                               # the gathered global copy is not needed again this epoch
             else:
-                devs = dp.shuffle(devs)
+                devs = dp.shuffle(devs, **pairkw)
                 mine = dp.my_rows(devs, args.train_batch_size)
             total_batch_size = mine["log_probs"].shape[0]
             num_train_ts = int(num_timesteps * args.train_timestep_ratio)
             n_mini = total_batch_size // (n_devices * args.train_batch_size)
             all_infos = []
-            info_keys = ("approx_kl", "clipfrac", "loss") + (("kl_ref",) if kl_coef > 0 else ())
+            info_keys = (("pref_acc", "pref_margin", "loss") if d3po else ("approx_kl", "clipfrac", "loss")) + (("kl_ref",) if kl_coef > 0 else ())
             do_opt_update = False
             train_fuse = train_fuse_default(args.train_batch_size * (2 if args.train_cfg else 1),
                                             mine["latents"].shape[-1] * mine["latents"].shape[-2])
@@ -333,7 +355,7 @@ def main(argv=None):
                         print(f"opt update at {i}, {js[-1]}")
                     state, infos_k = train_steps_fused(state, batches, noise_scheduler_state, pipeline.scheduler, args.train_cfg,
                                                        args.guidance_scale, args.eta, args.ppo_clip_range, do_opt_update,
-                                                       kl_coef=kl_coef, ref_unet=ref_unet)
+                                                       kl_coef=kl_coef, ref_unet=ref_unet, **losskw)
                     all_infos += [torch.stack([info[k] for k in info_keys]) for info in infos_k]
                 for j in (range(num_train_ts) if train_fuse <= 1 else ()):
                     batch = {"prompt_embeds": mine["embeds"][sl], "uncond_embeds": train_uncond_prompt_embeds,
@@ -346,7 +368,7 @@ def main(argv=None):
                         print(f"opt update at {i}, {j}")
                     state, info = train_step(state, batch, noise_scheduler_state, pipeline.scheduler, args.train_cfg,
                                              args.guidance_scale, args.eta, args.ppo_clip_range, do_opt_update,
-                                             kl_coef=kl_coef, ref_unet=ref_unet)
+                                             kl_coef=kl_coef, ref_unet=ref_unet, **losskw)
                     all_infos.append(torch.stack([info[k] for k in info_keys]))
             assert do_opt_update
             infos = torch.stack(all_infos).cpu().numpy()            # ONE host sync per inner epoch
@@ -355,6 +377,8 @@ def main(argv=None):
             all_infos = {k: infos[:, c] for c, k in enumerate(info_keys)}
             if kl_coef > 0:
                 inner_kl.append(float(all_infos["kl_ref"].mean()))
+            if d3po:
+                inner_acc.append(float(all_infos["pref_acc"].mean()))
             print(f"mean info: { {k: float(v.mean()) for k, v in all_infos.items()} } | "
                   f"{len(infos)} train steps in {time.time() - t_train:.2f}s")
             if worker_id == 0:
@@ -362,6 +386,8 @@ def main(argv=None):
 
         if kl_coef > 0:
             kl_ref_epochs.append(float(np.mean(inner_kl)))
+        if d3po:
+            pref_acc_epochs.append(float(np.mean(inner_acc)))
         if (epoch + 1) % args.save_freq == 0 or epoch == args.num_train_epochs - 1:
             save_rank_resume(os.path.join(args.savepath, "checkpoints"), epoch, worker_id,
                              {"sample_rng": sample_rng, "py_random": random.getstate(), "np_random": np.random.get_state()})
@@ -402,6 +428,8 @@ def main(argv=None):
     out = {"mean_rewards": mean_rewards, "localpath": localpath, "state": state}
     if kl_coef > 0:
         out["kl_ref"] = kl_ref_epochs            # per epoch run by this call: mean KL to the pretrained policy over its train steps
+    if d3po:
+        out["pref_acc"] = pref_acc_epochs        # per epoch run by this call: share of untied pairs the policy ranks as labelled, over its train steps
     return out
 
 
