@@ -78,6 +78,7 @@ enum class KLoop : int {
   tall_geglu = 6,    // the same k-loop with the GEGLU output stage on value / gate wave pairs
   tall_mx = 7,       // f16mx on the tall tile
   tall_ring = 8,     // single-pass bf16 / f16 on the tall tile: four-stage LDS ring
+  tall_mx_geglu = 9, // tall_mx's k-loop with tall_geglu's output stage (FF1 + GEGLU as an f16mx layer)
 };
 
 // the f16mx cross-term MFMA: A = e5m2 (cbsz 1), B = e4m3 (blgp 0); the weight scale is byte `opb` of `sb` (op_sel is an immediate: the
@@ -545,7 +546,7 @@ __global__ void __launch_bounds__(BF_THREADS) gemm_conv_bf16_kernel(const ddpo_g
 // {0, +1} (phase 1) per axis on the source grid, the phase's own weight planes (K * N elements apart) and E8M0 scales (N apart), rows stored
 // through fold_row.  A compile-time switch: the instantiations without it are the same code as before it existed.
 //
-// Instantiated combinations (35; kernel_exists() below is the same table for the host side):
+// Instantiated combinations (36; kernel_exists() below is the same table for the host side):
 //   tile (BM x BN, WM x WN)                 k-loop       datapaths                          FOLD
 //   128x128, 128x64 (2x2), 128x320 (4x2)    regs         bf16x1, bf16x3                     no           6
 //   128x128, 128x64 (2x2), 128x320 (4x2)    planes3w     bf16x1, bf16x3, f16mx, f16x1       no          12
@@ -553,6 +554,7 @@ __global__ void __launch_bounds__(BF_THREADS) gemm_conv_bf16_kernel(const ddpo_g
 //   256x320 (4x2)                           tall         bf16x3                             no, yes      2
 //   256x320 (4x2)                           tall_geglu   bf16x3                             no           1
 //   256x320 (4x2)                           tall_mx      f16mx                              no, yes      2
+//   256x320 (4x2)                           tall_mx_geglu f16mx                             no           1
 //   256x320 (4x2)                           tall_ring    bf16x1 (no, yes), f16x1 (no)                    3
 template <int BM, int BN, Datapath DP, int WM = 2, int WN = 2, KLoop KL = KLoop::regs, bool FOLD = false>
 __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) gemm_conv_bf16_buf_kernel(const ddpo_gemm_desc d, const uint16_t* __restrict__ w_hi_,
@@ -569,8 +571,8 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
   constexpr bool BFULL = (BN % BR) == 0;                // else the last W pass covers only part of the threads
   static_assert(BM % AR == 0 && WTM % 32 == 0 && WTN % 32 == 0, "tile / wave-grid mismatch");
   constexpr bool MX = DP == Datapath::f16mx;                       // f16mx datapath (plane-fed only): f16 plane + 8-bit plane per operand
-  static_assert(!MX || KL == KLoop::planes3w || KL == KLoop::tall_mx, "the f16mx datapath exists on the plane-fed 128-row tiles and on the tall tile");
-  static_assert(!FOLD || (KL != KLoop::regs && KL != KLoop::tall_geglu), "folded up-sampler phases exist on the plane-fed kernels");
+  static_assert(!MX || KL == KLoop::planes3w || KL == KLoop::tall_mx || KL == KLoop::tall_mx_geglu, "the f16mx datapath exists on the plane-fed 128-row tiles and on the tall tile");
+  static_assert(!FOLD || (KL != KLoop::regs && KL != KLoop::tall_geglu && KL != KLoop::tall_mx_geglu), "folded up-sampler phases exist on the plane-fed kernels");
   const int ph = FOLD ? (int)blockIdx.z : 0;                                   // phase (py, px) = (ph >> 1, ph & 1)
   const uint16_t* __restrict__ w_hi = FOLD ? w_hi_ + (int64_t)ph * d.K * d.N : w_hi_;
   const uint16_t* __restrict__ w_lo = (FOLD && w_lo_) ? w_lo_ + (int64_t)ph * d.K * d.N : w_lo_;
@@ -597,7 +599,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
   const int tile_n = in_group / gsz, tile_m = gm0 + (in_group - tile_n * gsz);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
-  const bool conv = d.ksize > 0;
+  const bool conv = KL != KLoop::tall_mx_geglu && d.ksize > 0;      // (the f16mx GEGLU tile is dense only: the tap bookkeeping would cost it registers it does not have)
   const int VH = (!FOLD && d.upsample) ? d.H * 2 : d.H, VW = (!FOLD && d.upsample) ? d.W * 2 : d.W;
   const bool zins = !FOLD && d.upsample == 2;
   const int cin = conv ? d.Cin : d.K;            // reduction channels per tap (dense: one "tap" spanning K)
@@ -934,7 +936,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         __builtin_amdgcn_sched_barrier(0);
         as = as_n; ws = ws_n;
       }
-    } else if constexpr (KL == KLoop::tall_mx) {
+    } else if constexpr (KL == KLoop::tall_mx || KL == KLoop::tall_mx_geglu) {
       // f16mx on the TALL 256 x 320 tile (round 5): eight waves of 64 x 160, two per SIMD (256 registers per lane: 160 accumulators + 96).
       // Why a tall tile: the f16mx kernels are bound by the chip's L2 -> LDS stream (8.4 - 11.4 TB/s, tools/native/dma_bench), not by the
       // matrix pipe — the 128 x 320 tile fetches 57 KB per k-tile for 1.31 M MAC (23 MAC / B), this one 73.7 KB for 2.62 M (35.5 MAC / B):
@@ -1270,7 +1272,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
       Epi ep;
       const int colb = n0 + wn * WTN;
       static_assert(TM == 2, "the tall tile's output stage is written for two 32-row passes per wave");
-      if constexpr (KL == KLoop::tall_geglu) {
+      if constexpr (KL == KLoop::tall_geglu || KL == KLoop::tall_mx_geglu) {
         // GEGLU on the tall tile (round 5; its own instantiation, KLoop::tall_geglu, so that the plain tall tile's code does not change by an instruction).  The weight columns of tile t come as [a (160) | gate (160)] of output columns 160 t .. 160 t + 159
         // (ddpo_gemm_desc.epilogue == 2), so the wave pair (wm, 0) / (wm, 1) holds the value and the gate accumulators of the SAME 64 x 160
         // outputs.  Per 32-row pass: both waves add their bias IN REGISTERS (a lane's column is fixed per accumulator block) and transpose
@@ -1279,6 +1281,9 @@ __global__ void __launch_bounds__(64 * WM * WN, (BM * BN <= 128 * 64 ? 3 : 1)) g
         // the pre-activation rows in the original [a | gate] column order (aux_out) — so the gelus and the stores are spread over all eight
         // waves.  Same arithmetic per element as the 128 x 128 GEGLU tile — (acc_a + b_a) * gelu_tanh(acc_g + b_g) on the same accumulation
         // order — so the two tiles agree bit for bit (tests/test_gpu_bf16.py::test_linear_geglu_tall_tile_is_bit_identical).
+        // KLoop::tall_mx_geglu: this stage behind the f16mx tall k-loop (FF1 registered as an f16mx layer), again its own instantiation; the
+        // accumulators hold the 128-row f16mx tile's sums (f16 ks 0, f16 ks 1, MX per k-tile), so it equals that tile's GEGLU bit for bit
+        // (tests/test_gpu_ff1_f16mx.py).
         static_assert(WN == 2 && WTN == 160, "value / gate wave pairs of 160 columns");
         const int oc0 = (n0 / 320) * 160;                  // first OUTPUT column of this tile
         float bj[TN];
@@ -1549,10 +1554,11 @@ using TileTall = Tile<256, 320, 4, 2, TC_TALL, 8 * 32 * 160 * 4, false>;    // 8
 // the instantiations of gemm_conv_bf16_buf_kernel that exist (the table at its head); launch_tile instantiates nothing else
 template <class T, Datapath DP, KLoop KL, bool FOLD>
 constexpr bool kernel_exists() {
-  if (FOLD && (DP == Datapath::f16x1 || KL == KLoop::regs || KL == KLoop::tall_geglu)) return false;
+  if (FOLD && (DP == Datapath::f16x1 || KL == KLoop::regs || KL == KLoop::tall_geglu || KL == KLoop::tall_mx_geglu)) return false;
   if (T::BM == 256) {
     if (DP == Datapath::bf16x3) return KL == KLoop::tall || KL == KLoop::tall_geglu;
-    return KL == (DP == Datapath::f16mx ? KLoop::tall_mx : KLoop::tall_ring);
+    if (DP == Datapath::f16mx) return KL == KLoop::tall_mx || KL == KLoop::tall_mx_geglu;
+    return KL == KLoop::tall_ring;
   }
   return KL == KLoop::planes3w || (KL == KLoop::regs && (DP == Datapath::bf16x1 || DP == Datapath::bf16x3));
 }
@@ -1657,7 +1663,7 @@ static int launch_route(const Route& r, const ddpo_gemm_desc& d, const uint16_t*
   constexpr KLoop KT = !PLANES ? KLoop::regs : (DP == Datapath::bf16x3 ? KLoop::tall : (DP == Datapath::f16mx ? KLoop::tall_mx : KLoop::tall_ring));
   switch (r.tile) {
     case RT_TALL: return launch_tile<TileTall, DP, KT, FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
-    case RT_TALL_GEGLU: return launch_tile<TileTall, DP, PLANES && DP == Datapath::bf16x3 ? KLoop::tall_geglu : KLoop::regs, FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
+    case RT_TALL_GEGLU: return launch_tile<TileTall, DP, !PLANES ? KLoop::regs : (DP == Datapath::bf16x3 ? KLoop::tall_geglu : (DP == Datapath::f16mx ? KLoop::tall_mx_geglu : KLoop::regs)), FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
     case RT_WIDE: return launch_tile<TileWide, DP, KL, FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
     case RT_128: return launch_tile<Tile128x128, DP, KL, FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
     default: return launch_tile<Tile128x64, DP, KL, FOLD>(d, w_hi, w_lo, ldw, ws, r.splits, st);
@@ -1687,8 +1693,10 @@ static int dispatch_bf16(const ddpo_gemm_desc& d, const uint16_t* w_hi, const ui
     if ((d.epilogue != 1 && d.epilogue != 2) || (d.N & 127) || !buf_path_ok(d, ldw) || d.rowbias || d.residual || d.alpha != 1.0f || d.w_dgrad) return DDPO_EINVAL;
     if ((d.ld_out & 3) || (reinterpret_cast<uintptr_t>(d.out) & 15) || (d.bias && (reinterpret_cast<uintptr_t>(d.bias) & 15))) return DDPO_EINVAL;
     if (reinterpret_cast<uintptr_t>(d.aux_out) & 15) return DDPO_EINVAL;
-    // epilogue 2: the tall 256 x 320 tile with value / gate wave pairs: plane-fed bf16x3 only, columns in [a (160) | gate (160)] blocks
-    if (d.epilogue == 2 && (!PLANES || npass != 3 || d.N % 320 || ((d.N >> 1) & 3))) return DDPO_EINVAL;
+    // epilogue 2: the tall 256 x 320 tile with value / gate wave pairs: plane-fed bf16x3 or f16mx (with its cross terms), columns in
+    // [a (160) | gate (160)] blocks
+    if (d.epilogue == 2 && (!PLANES || (npass != 3 && npass != 4) || d.N % 320 || ((d.N >> 1) & 3))) return DDPO_EINVAL;
+    if (d.epilogue == 2 && npass == 4 && d.ksize > 0) return DDPO_EINVAL;      // the f16mx form is instantiated for dense layers only
     return launch_npass<PLANES, FOLD>(npass, Route{d.epilogue == 2 ? RT_TALL_GEGLU : RT_128, 1}, d, w_hi, w_lo, ldw, nullptr, st);
   }
   float* wsf = (ws && !(reinterpret_cast<uintptr_t>(ws) & 15)) ? reinterpret_cast<float*>(ws) : nullptr;

@@ -183,7 +183,8 @@ def shipped_datapath():
 
 
 # "f16mx" (round 3; the shipped default since round 4): every plane-eligible forward contraction with a LONG reduction (K >= MX_MIN_K: all 3x3 convolutions, FF2 of the
-# lower levels — a property of the layer, never of the batch) runs on the f16 + MX-fp8 cross-term kernel (ddpo_gemm_conv_fwd_f16mx_planes); its
+# lower levels — a property of the layer, never of the batch), and FF1 + GEGLU where the model registers it as an f16mx layer (pack_weights_geglu(mx=True);
+# FF1_MX below: the one compute-bound short reduction of the step), runs on the f16 + MX-fp8 cross-term kernel (ddpo_gemm_conv_fwd_f16mx_planes); its
 # activation planes come from the producing kernel (GroupNorm / LayerNorm / GEMM output stages, which ask planes_pay() for the consumer's
 # format) or, when the producer wrote fp32 (training forward: the weight gradients read the fp32 tensor), from ddpo_split_planes_f16mx on the
 # way in — the same bits either way, so the sampler and the training forward of a layer always take the same arithmetic.  Everything else
@@ -293,6 +294,9 @@ PLANES = os.environ.get("DDPO_PLANES", "1") == "1"
 TRAIN_PLANES = os.environ.get("DDPO_TRAIN_PLANES", "1") == "1"
 # FF1 + GEGLU of the sampling forward on the 256 x 320 tile where its grid fills the chip (round 5; geglu_tall_pays).  DDPO_GEGLU_TALL=0: the 128 x 128 tile everywhere.
 GEGLU_TALL = os.environ.get("DDPO_GEGLU_TALL", "1") == "1"
+# FF1 + GEGLU as an f16mx layer where the model registers it as one (pack_weights_geglu(mx=True)): its 107 GFLOP launches are the one compute-bound
+# three-pass family of the step, and f16mx spends two matrix passes per product instead of three.  DDPO_FF1_MX=0: the bf16x3 route (the A/B).
+FF1_MX = os.environ.get("DDPO_FF1_MX", "1") == "1"
 # GEMM output stages that emit planes for a following GEMM (GEGLU -> FF2, block output -> down / up-sampler convolution)
 PLANES_OUT = os.environ.get("DDPO_PLANES_OUT", "1") == "1"
 PLANES_ALL = os.environ.get("DDPO_PLANES_ALL", "0") == "1"      # plane-feed every eligible layer, also where it is measured slower
@@ -1061,10 +1065,12 @@ def _dgrad_fwd(dy, dg, *, M, conv=None, residual=None, ld_res=None, out=None):
     return out
 
 
-def pack_weights_geglu(w, bias):
+def pack_weights_geglu(w, bias, mx=False):
     """Second set of forward planes for a GEGLU feed-forward weight w (K, 2F) with its columns (and bias) re-ordered into
     interleaved 32-column blocks [a_q | gate_q], the layout ddpo_gemm_desc.epilogue = 1 expects.  Returns False when
-    the shape does not qualify (the caller then keeps the unfused linear + geglu pair)."""
+    the shape does not qualify (the caller then keeps the unfused linear + geglu pair).
+    mx: the MODEL registers the layer as an f16mx layer whatever its reduction length (the U-Net's FF1): under the f16mx datapath with its cross
+    terms (MX_CROSS) and FF1_MX it gets f16mx planes in both column orders (geglu_mx_layer()).  Without the keyword nothing changes."""
     K, N = w.shape
     F = N // 2
     if current_datapath() == "fp32" or (N % 128) or (K % 32):
@@ -1085,21 +1091,34 @@ def pack_weights_geglu(w, bias):
     else:
         _check(load().ddpo_pack_weights_bf16(_p(wp), K, N, K, _p(g["hi"]), _p(g["lo"]), None, None, _stream()), "ddpo_pack_weights_bf16")
     # second column order for the 256 x 320 GEGLU tile (ddpo_gemm_desc.epilogue = 2, ABI v13): 320-column blocks [a (160) | gate (160)]; bf16x3 layers
-    # only (FF1's reduction is the model width: never an f16mx layer), k-blocked planes.  Which of the two orders a call uses: geglu_tall_pays().
+    # only (an FF1 registered with mx=True: the f16mx planes of the same order instead, below), k-blocked planes.  Which of the two orders a call
+    # uses: geglu_tall_pays().
+    ff1_mx = bool(mx and FF1_MX and MX_CROSS and _mx())           # (DDPO_MX_CROSS=0: the tall GEGLU tile has no single-pass f16 form — FF1 stays bf16x3)
+    mxp = lambda: dict(w16=torch.zeros(K // 32, N, 32, dtype=torch.int16, device=w.device), w8=torch.zeros(K // 32, N, 64, dtype=torch.uint8, device=w.device),
+                       scale=torch.zeros(N, dtype=torch.uint8, device=w.device))
     if GEGLU_TALL and W_KBLOCKED and _x3() and N % 320 == 0 and not (_mx() and K >= MX_MIN_K):
         if "tall" not in g:
             idx = torch.arange(F, device=w.device).view(F // 160, 1, 160)
-            g["tall"] = dict(perm=torch.cat([idx, idx + F], dim=1).reshape(-1), hi=mk(), lo=mk(), bias=torch.empty(N, dtype=torch.float32, device=w.device))
+            g["tall"] = dict(perm=torch.cat([idx, idx + F], dim=1).reshape(-1), **({} if ff1_mx else dict(hi=mk(), lo=mk())),
+                             bias=torch.empty(N, dtype=torch.float32, device=w.device))
         t = g["tall"]
         wt = w.index_select(1, t["perm"]).contiguous()
         torch.index_select(bias, 0, t["perm"], out=t["bias"])
-        _check(load().ddpo_pack_weights_bf16_kblocked(_p(wt), K, N, _p(t["hi"]), _p(t["lo"]), _stream()), "ddpo_pack_weights_bf16_kblocked")
+        if ff1_mx:                       # the tall column order as f16mx planes (ddpo_gemm_desc.epilogue = 2 on the f16mx entry point)
+            if "mx" not in t:
+                t["mx"] = mxp()
+            m = t["mx"]
+            _check(load().ddpo_pack_weights_f16mx(_p(wt), K, N, _p(m["w16"]), _p(m["w8"]), _p(m["scale"]), _stream()), "ddpo_pack_weights_f16mx")
+        else:
+            t.pop("mx", None)
+            if "hi" not in t:
+                t.update(hi=mk(), lo=mk())
+            _check(load().ddpo_pack_weights_bf16_kblocked(_p(wt), K, N, _p(t["hi"]), _p(t["lo"]), _stream()), "ddpo_pack_weights_bf16_kblocked")
     else:
         g.pop("tall", None)
-    if _mx() and K >= MX_MIN_K:
+    if _mx() and (K >= MX_MIN_K or ff1_mx):
         if "mx" not in g:
-            g["mx"] = dict(w16=torch.zeros(K // 32, N, 32, dtype=torch.int16, device=w.device), w8=torch.zeros(K // 32, N, 64, dtype=torch.uint8, device=w.device),
-                           scale=torch.zeros(N, dtype=torch.uint8, device=w.device))
+            g["mx"] = mxp()
         m = g["mx"]
         _check(load().ddpo_pack_weights_f16mx(_p(wp), K, N, _p(m["w16"]), _p(m["w8"]), _p(m["scale"]), _stream()), "ddpo_pack_weights_f16mx")
     else:
@@ -1108,14 +1127,26 @@ def pack_weights_geglu(w, bias):
     return True
 
 
+def geglu_mx_layer(w):
+    """True when the fused FF1 + GEGLU of weight `w` runs on the f16mx kernel: f16mx datapath and f16mx planes in the GEGLU column order registered
+    (pack_weights_geglu: K >= MX_MIN_K, or mx=True).  A property of the layer, as mx_layer() — the caller's LayerNorm then emits f16mx planes
+    (`planes=2`; the training forward keeps fp32, which linear_geglu splits on the way in)."""
+    if not _mx():
+        return False
+    ent = PACKED.get(w.data_ptr())
+    return ent is not None and "geglu" in ent and not ent["geglu"]["stale"] and "mx" in ent["geglu"]
+
+
 def geglu_tall_pays(w, rows):
     """True when the fused FF1 + GEGLU of weight `w` on `rows` rows should run on the 256 x 320 tile (epilogue = 2): registered with the tall column
     order and the grid of tall tiles fills whole rounds of the 256 CUs well — the rule the C++ dispatch
     applies to the plain tall tile (_tall_tiles_fill).  The caller then feeds bf16 hi / lo PLANES
-    (LayerNorm `planes=1`).  Why: at K = 320 .. 1280 the 128 x 128 GEGLU tile streams 16 MAC per operand byte and FF1 sits on the chip's L2 -> LDS
+    (LayerNorm `planes=1`) — or, for an FF1 registered as an f16mx layer (geglu_mx_layer), f16mx planes (`planes=2`).  Why: at K = 320 .. 1280 the 128 x 128 GEGLU tile streams 16 MAC per operand byte and FF1 sits on the chip's L2 -> LDS
     stream (3.3 GB per launch at the 64 x 64 level = 8 TB/s); the tall tile moves 35 MAC per byte."""
     ent = PACKED.get(w.data_ptr())
     if not (GEGLU_TALL and PLANES and _x3() and ent is not None and "geglu" in ent and not ent["geglu"]["stale"] and "tall" in ent["geglu"]):
+        return False
+    if geglu_mx_layer(w) and "mx" not in ent["geglu"]["tall"]:      # an f16mx layer runs the tall tile on f16mx planes of the tall order only
         return False
     K, N = ent["K"], ent["N"]
     if not _fits_buf(rows * K * 4) or K % 32:
@@ -1150,14 +1181,14 @@ def linear_geglu(x, w, out=None, planes_out=False, pre_out=False):
         opl = Planes(M, N // 2, x.device, fmt=1 if planes_out == 2 else 0)            # planes_out = the CONSUMER's planes_pay value
     elif out is None:
         out = torch.empty(M, N // 2, dtype=torch.float32, device=x.device)
-    tall = pl is not None and pl.fmt == 0 and geglu_tall_pays(w, M)
+    tall = pl is not None and geglu_tall_pays(w, M) and ("mx" if mxl else "hi") in g["tall"]       # (past the check above the planes are of the layer's format: bf16 hi / lo, or f16mx for an f16mx layer)
     gw = g["tall"] if tall else g
     pre = torch.empty(M, N, dtype=torch.float32, device=x.device) if pre_out else None
     d = _gemm_desc(M, N, K, src=x, ld_src=K, out=None if planes_out else out, ld_out=N // 2, bias=gw["bias"], aux_out=pre,
                    out_planes=opl and (opl.hi, opl.lo, opl.ld, opl.fmt), epilogue=2 if tall else 1)
     with _profiled(2.0 * M * N * K, 4.0 * (M * K + K * N + M * N // 2), _family(mx=mxl)):     # (past the checks above, mxl = "pl holds f16mx planes")
         if mxl:
-            _launch_fwd(d, pl, g["mx"])
+            _launch_fwd(d, pl, gw["mx"])
         elif pl is not None:
             _launch_fwd(d, pl, (gw["hi"], gw["lo"], K, 3 if _x3() else 1), w_layout=1 if tall else g["w_layout"])
         else:

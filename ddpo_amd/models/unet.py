@@ -97,7 +97,7 @@ class ParamStore:
                 if n.endswith(".upsamplers_0.conv.kernel"):
                     L.pack_weights_up2x_folded(v)
                 if n.endswith(".ff.net_0.proj.kernel"):
-                    L.pack_weights_geglu(v, self.views[n[:-len("kernel")] + "bias"])
+                    L.pack_weights_geglu(v, self.views[n[:-len("kernel")] + "bias"], mx=True)
                 m = re.search(r"\.attn1\.to_[qkv]\.kernel$", n)
                 if QKV_FUSED and m and n[:m.start()] + ".attn1." not in qkv:
                     qkv.append(n[:m.start()] + ".attn1.")
@@ -109,8 +109,8 @@ class ParamStore:
                 L.pack_weights(v, bwd=bwd)
                 if n.endswith(".upsamplers_0.conv.kernel"):      # nearest-2x up-sampler: the folded phase planes (U-Net and VAE decoder)
                     L.pack_weights_up2x_folded(v)
-                if n.endswith(".ff.net_0.proj.kernel"):          # GEGLU feed-forward: extra planes for the fused forward
-                    L.pack_weights_geglu(v, self.views[n[:-len("kernel")] + "bias"])
+                if n.endswith(".ff.net_0.proj.kernel"):          # GEGLU feed-forward: extra planes for the fused forward; an f16mx layer under that datapath (lib.FF1_MX)
+                    L.pack_weights_geglu(v, self.views[n[:-len("kernel")] + "bias"], mx=True)
                 if QKV_FUSED and n.endswith(".attn1.to_q.kernel"):
                     # self-attention of the SAMPLING forward: q, k, v as ONE (K, 3C) projection of the LayerNorm output (round 5).  Three launches
                     # of N = C columns become one of 3C: at the 16x16 level (M = 4096 at batch 16) that is 128 x 320 tiles instead of 128 x 64
@@ -470,7 +470,11 @@ class UNet2DCondition:
             pl_1 = 0
         pl_2 = npf(tb + ".attn2.to_q.kernel")
         pl_3 = npf(tb + ".ff.net_0.proj.kernel")
-        if inf and pl_3 != 1 and L.geglu_tall_pays(P[tb + ".ff.net_0.proj.kernel"], B * N):
+        if L.geglu_mx_layer(P[tb + ".ff.net_0.proj.kernel"]):
+            # FF1 registered as an f16mx layer (pack_bf16): norm3 writes f16mx planes; the training forward keeps fp32 for the weight gradient and
+            # linear_geglu splits it on the way in — the same planes, the same arithmetic
+            pl_3 = 2 if inf and L.planes_ok(P[tb + ".ff.net_0.proj.kernel"], C, B * N) else 0
+        elif inf and pl_3 != 1 and L.geglu_tall_pays(P[tb + ".ff.net_0.proj.kernel"], B * N):
             pl_3 = 1                               # FF1 + GEGLU on the 256 x 320 tile is plane-fed: norm3 writes bf16 hi / lo planes
         F = P[tb + ".ff.net_2.kernel"].shape[0]
         pl_ff2 = inf and L.PLANES_OUT and L.planes_pay(P[tb + ".ff.net_2.kernel"], F, B * N)       # GEGLU output stage -> planes -> plane-fed FF2

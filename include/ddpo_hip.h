@@ -181,7 +181,8 @@ typedef struct {
                                         [a_0 | gate_0 | a_1 | gate_1 ...]; out has N/2 columns,
                                         out[:, 32q + c] = (acc_a + bias_a) * gelu_tanh(acc_gate + bias_gate);
                                         needs N % 128 == 0, K % 32 == 0, no rowbias / residual, alpha == 1
-                                     2: GEGLU on the 256 x 320 tile (ABI v13; ddpo_gemm_conv_fwd_bf16_planes only).  The columns of W / bias come
+                                     2: GEGLU on the 256 x 320 tile (ABI v13; ddpo_gemm_conv_fwd_bf16_planes with both planes, and
+                                        ddpo_gemm_conv_fwd_f16mx_planes with its cross terms on a dense layer).  The columns of W / bias come
                                         as 320-column blocks [a (160) | gate (160)]: block t holds the value and gate columns of the output
                                         columns 160 t .. 160 t + 159; same formula, bit-identical results (aux_out included); needs N % 320 == 0 */
   /* plane-emitting output stage (ddpo_gemm_conv_fwd_bf16 / _planes on the buffer-addressed kernels only; NULL elsewhere).
@@ -260,12 +261,12 @@ int ddpo_gemm_conv_fwd_bf16_planes(const ddpo_gemm_desc* d, const uint16_t* a_hi
  *   a16 / a8  activation planes written by ddpo_split_planes_f16mx or a plane-emitting producer (planes_fmt = 1), (rows, lda) or
  *             k-blocked (lda == 0) like the bf16 planes;
  *   w16 / w8 / d->w_scale  weight planes of ddpo_pack_weights_f16mx (k-blocked only: d->w_layout must be 1).
- * Tiles, split-K, output stage (incl. epilogue = 1 and plane emission in either format) as ddpo_gemm_conv_fwd_bf16_planes;
+ * Tiles, split-K, output stage (incl. epilogue = 1 / 2 and plane emission in either format) as ddpo_gemm_conv_fwd_bf16_planes;
  * every tile class accumulates in the same order (bit-identical results for one layer whatever the batch).  Forward only:
  * data / weight gradients stay on bf16x3. 
  * ABI v14: a8 == NULL AND w8 == NULL (d->w_scale unused) runs the operator WITHOUT its cross terms — a_h * w_h on the f16 MFMA only, on the
  * single-plane kernels (four-stage ring on the 256 x 320 tile): one f16 pass per product, 7e-4 instead of 4e-5 on a U-Net forward and outside the 1e-3 gradient contract at full size.  Opt-in
- * (DDPO_MX_CROSS=0); exactly one of the two NULL is DDPO_EINVAL. */
+ * (DDPO_MX_CROSS=0); exactly one of the two NULL, or epilogue == 2 without the cross terms, is DDPO_EINVAL. */
 int ddpo_gemm_conv_fwd_f16mx_planes(const ddpo_gemm_desc* d, const uint16_t* a16, const uint16_t* a8, int lda,
                                     const uint16_t* w16, const uint16_t* w8, void* ws, size_t ws_bytes, void* stream);
 /* Folded nearest-2x up-sampler (additive to ABI v14): FlaxUpsample2D — jax.image.resize(nearest, 2x) followed by a 3x3 convolution, inside the
