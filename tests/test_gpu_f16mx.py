@@ -7,28 +7,10 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
+from _gemm_fwd_cases import dec_planes as _dec_planes, dec_weights as _dec_weights          # (shared with test_gpu_gemm_fwd_routes.py)
 from ddpo_amd import lib as L
 
 pytestmark = pytest.mark.gpu
-
-
-def _dec_planes(p16, p8):
-    """(h, h8, l8) as float64 (rows, C) from the activation planes."""
-    rows, C = p16.shape
-    h = p16.view(torch.float16).double()
-    b = p8.view(torch.float8_e5m2).double().view(rows, C // 32, 2, 2, 16)      # per block: [k half][h8 | l8][16]
-    return h, b[:, :, :, 0].reshape(rows, C), b[:, :, :, 1].reshape(rows, C) / 2048.0
-
-
-def _dec_weights(wp):
-    """(h, h8, l8) as float64 (K, N) from the weight planes (zero padded rows dropped)."""
-    K, N = wp["K"], wp["N"]
-    s = torch.pow(2.0, wp["scale"].double() - 127.0)                      # (N,)
-    h = wp["w16"].view(torch.float16).double().permute(0, 2, 1).reshape(-1, N)[:K]      # (Kb, N, 32) -> (Kb*32, N)
-    b = wp["w8"].view(torch.float8_e4m3fn).double().view(-1, N, 2, 2, 16)      # (Kb, N, k half, [l8 | h8], 16)
-    l8 = (b[:, :, :, 0].reshape(-1, N, 32) * s[None, :, None] / 2048.0).permute(0, 2, 1).reshape(-1, N)[:K]
-    h8 = (b[:, :, :, 1].reshape(-1, N, 32) * s[None, :, None]).permute(0, 2, 1).reshape(-1, N)[:K]
-    return h, h8, l8
 
 
 def test_activation_planes_are_f16_and_e5m2_of_the_split():
