@@ -60,7 +60,16 @@ _TRAIN_DEFAULTS = (
     ("per_prompt_weights", False), ("seed", 0),
 )
 
-base = {"sample": dict(_SAMPLE_DEFAULTS), "train": dict(_TRAIN_DEFAULTS), "pg": dict(_PG_DEFAULTS)}
+# engine-specific addition: the `dpo` experiment of pipeline/dpo.py, Diffusion-DPO on ranked pairs of the stored samples (Wallace et al.,
+# "Diffusion Model Alignment Using Direct Preference Optimization").  The `train` keys without the RWR weighting, plus:
+# dpo_beta 5000, the value the Diffusion-DPO authors ship for SD-1.5 with the error taken as a mean over the latent, as here — quoted from
+# memory of their release and not measured in a training run on this engine; pair_seed, the seed of the pairing (epoch e pairs with
+# pair_seed + e).  pair_seed is NOT offset by the rank (every host must build the same pairing); the parser offsets `seed`.
+_DPO_DEFAULTS = tuple(kv for kv in _TRAIN_DEFAULTS if kv[0] not in ("weighted_batch", "weighted_dataset", "per_prompt_weights")) + (
+    ("dpo_beta", 5000.0), ("pair_seed", 0),
+)
+
+base = {"sample": dict(_SAMPLE_DEFAULTS), "train": dict(_TRAIN_DEFAULTS), "pg": dict(_PG_DEFAULTS), "dpo": dict(_DPO_DEFAULTS)}
 
 # the two `sample` recipes of the reference's datasets: keep the top decile of 1024 identical-prompt batches (filter-finetune),
 # or keep all of 10240 samples (reward-weighted regression)
@@ -76,7 +85,7 @@ def _train(train_cfg=True, train_batch_size=1, num_train_epochs=50, save_freq=20
 _TRAIN_RWR = dict(num_train_epochs=5, weighted_dataset=True, temperature=1 / 5.0)
 
 
-def _dataset(logdir, prompt_fn, filter_field, prompt_kwargs=None, sample=None, train=None, **pg):
+def _dataset(logdir, prompt_fn, filter_field, prompt_kwargs=None, sample=None, train=None, dpo=None, **pg):
     common = {"logbase": f"{user.bucket}/logs/{logdir}", "prompt_fn": prompt_fn, "filter_field": filter_field}
     if prompt_kwargs is not None:
         common["prompt_kwargs"] = prompt_kwargs
@@ -85,6 +94,8 @@ def _dataset(logdir, prompt_fn, filter_field, prompt_kwargs=None, sample=None, t
         out["sample"] = dict(sample)
     if train is not None:
         out["train"] = dict(train)
+    if dpo is not None:
+        out["dpo"] = dict(dpo)
     return out
 
 
@@ -101,6 +112,10 @@ neg_compressed_animals_rwr = _dataset("rwr-neg-compressed-animals-s10k", "imagen
                                       train=_train(**_TRAIN_RWR))
 a_animals_rwr = _dataset("aesthetic_simple_animals_rwr_ppb", "from_file", "aesthetic", {"loadpath": "assets/common_animals.txt"},
                          sample=_SAMPLE_ALL, train=_train(train_batch_size=4, save_freq=10000000, per_prompt_weights=True, **_TRAIN_RWR))
+# Diffusion-DPO on ranked pairs of all samples (pipeline/sample.py, then pipeline/dpo.py)
+_DPO = dict(train_cfg=True, train_batch_size=4, num_train_epochs=5, save_freq=20, dtype="float32")
+compressed_animals_dpo = _dataset("dpo-compressed-animals-s10k", "imagenet_animals", "jpeg", sample=_SAMPLE_ALL, dpo=_DPO)
+a_animals_dpo = _dataset("aesthetic_simple_animals_dpo", "from_file", "aesthetic", _ANIMALS, sample=_SAMPLE_ALL, dpo=_DPO)
 llava_vqa = _dataset("llava-vqa-v2", "vqa_dataset", "llava_vqa", {"loadpath": "assets/vqa_v2.txt"},
                      per_prompt_stats_bufsize=128, per_prompt_stats_min_count=32, num_train_epochs=120)
 llava_counting = _dataset("llava-counting-v0-8", "counting", "llava_vqa",

@@ -311,3 +311,94 @@ def get_bucket_loader(loadpath, tokenizer, batch_size, resolution=None, max_trai
         dataset.subsample(max_train_samples)
     dataset.shard(host_id, n_hosts)
     return dataset, _Loader(dataset, tokenizer, batch_size)
+
+
+# ------------------------------------------------------------------------------------------------ ranked pairs (pipeline/dpo.py)
+def make_pairs(prompts, rewards, seed):
+    """Ranked pairs of stored samples for Diffusion-DPO: -> (idx (P, 2) int64 row indices, y (P,) float32 = sign(r[i0] - r[i1])).
+    For each prompt of np.unique(prompts), in that order, the ascending row indices of the prompt are permuted and paired off consecutively
+    (an odd leftover is dropped); pairs with equal rewards are dropped; the remaining pairs are permuted.  All draws come from
+    np.random.RandomState(seed), so every host builds the same pairing."""
+    rs = np.random.RandomState(seed)
+    prompts = np.asarray(prompts).reshape(-1)
+    r = np.asarray(rewards, dtype=np.float64).reshape(-1)
+    if prompts.size != r.size:
+        raise ValueError(f"{prompts.size} prompts for {r.size} rewards")
+    pairs = [np.zeros((0, 2), dtype=np.int64)]
+    for prompt in np.unique(prompts):
+        rows = rs.permutation(np.flatnonzero(prompts == prompt))
+        k = len(rows) // 2
+        pairs.append(rows[:2 * k].reshape(k, 2).astype(np.int64))
+    idx = np.concatenate(pairs)
+    y = np.sign(r[idx[:, 0]] - r[idx[:, 1]])
+    idx, y = idx[y != 0], y[y != 0]
+    if len(idx) == 0:
+        raise ValueError("no ranked pair in the sample store: no prompt occurs twice with different rewards — sample with "
+                         "--identical_batch True or a smaller prompt set")
+    perm = rs.permutation(len(idx))
+    return idx[perm], y[perm].astype(np.float32)
+
+
+def pair_counts(prompts, n_pairs):
+    """(ties dropped, rows left over) of a make_pairs result with n_pairs pairs: sum_k floor(n_k / 2) pairs are formed before ties leave."""
+    _, counts = np.unique(np.asarray(prompts).reshape(-1), return_counts=True)
+    formed = int((counts // 2).sum())
+    return formed - int(n_pairs), int(counts.sum()) - 2 * formed
+
+
+def shard_pairs(idx, y, host_id=0, n_hosts=1):
+    """Whole pairs per host: host h takes pairs [h n, (h + 1) n) with n = P // n_hosts of the pairing every host built from the same seed."""
+    n = len(idx) // n_hosts
+    return idx[host_id * n:(host_id + 1) * n], y[host_id * n:(host_id + 1) * n]
+
+
+class PairLoader:
+    """Batches of `batch_size` rows (even) with the two rows of a pair adjacent (2p, 2p+1), drop-last, in the order of make_pairs.  Each
+    batch is what collate_fn gives plus "pref" (batch_size,) float32: +y on row 2p and -y on row 2p+1 (preference.pair_labels).  One caption
+    is chosen per pair, so both rows carry the same `training_prompts` choice.  `pair(seed)` re-pairs (once per epoch)."""
+
+    def __init__(self, reader, tokenizer, batch_size, filter_field, max_train_samples=None, host_id=0, n_hosts=1,
+                 prompt_field="inference_prompts"):
+        if int(batch_size) % 2:
+            raise ValueError(f"pairs sit on adjacent rows: batch_size must be even, got {batch_size}")
+        self.reader, self.tokenizer, self.batch_size = reader, tokenizer, int(batch_size)
+        self.host_id, self.n_hosts = int(host_id), int(n_hosts)
+        n = len(reader) if max_train_samples is None else min(int(max_train_samples), len(reader))
+        self.n_rows = n
+        self.prompts = np.asarray(reader.get(slice(0, n), prompt_field)).reshape(n)          # as LocalReader.make_weights reads them
+        self.rewards = np.asarray(reader.get(slice(0, n), filter_field), dtype=np.float64).reshape(n)
+        self.idx, self.y, self.n_pairs_all = np.zeros((0, 2), dtype=np.int64), np.zeros(0, dtype=np.float32), 0
+
+    def pair(self, seed):
+        """-> (pairs kept, ties dropped, rows left over) over the whole store; this host keeps its shard of whole pairs."""
+        idx, y = make_pairs(self.prompts, self.rewards, seed)
+        self.n_pairs_all = len(idx)
+        self.idx, self.y = shard_pairs(idx, y, self.host_id, self.n_hosts)
+        return (len(idx),) + pair_counts(self.prompts, len(idx))
+
+    def __len__(self):
+        return 2 * len(self.idx) // self.batch_size
+
+    def __iter__(self):
+        per = self.batch_size // 2
+        for b in range(len(self)):
+            examples = []
+            for p in range(b * per, (b + 1) * per):
+                caption = self.reader[int(self.idx[p, 0])]["training_prompts"]
+                if isinstance(caption, (list, np.ndarray)):
+                    caption = random.choice(list(np.asarray(caption).reshape(-1)))          # select_caption, once per pair
+                for j in range(2):
+                    row = int(self.idx[p, j])
+                    x = dict(self.reader[row])
+                    x["text"] = caption
+                    x.update(idx=2 * p + j, shuffled_idx=row)
+                    examples.append(x)
+            batch = collate_fn(self.tokenizer, examples)
+            y = self.y[b * per:(b + 1) * per]
+            batch["pref"] = (np.stack([y, -y], 1).reshape(-1) + 0.0).astype(np.float32)
+            yield batch
+
+
+def get_pair_loader(loadpath, tokenizer, batch_size, filter_field, max_train_samples=None, host_id=0, n_hosts=1):
+    reader = LocalReader(loadpath)
+    return reader, PairLoader(reader, tokenizer, batch_size, filter_field, max_train_samples, host_id, n_hosts)

@@ -1,0 +1,129 @@
+#!/usr/bin/env python
+"""Diffusion-DPO fine-tuning on ranked pairs of the samples `pipeline/sample.py` stored — the offline counterpart of `--pg_loss d3po`.
+
+    python pipeline/dpo.py --dataset compressed-animals-dpo [--key value ...]
+    torchrun --nproc-per-node 8 pipeline/dpo.py --dataset a-animals-dpo       (one process per GPU)
+
+Mirrors pipeline/finetune.py: the `dpo` experiment of config/base.py; the dataset `pipeline/sample.py` wrote (stored VAE moments, prompts,
+rewards).  Per epoch the rows of each prompt are paired at random (`pair_seed + epoch`, the same pairing on every rank), each pair is
+ranked by the sign of its `filter_field` difference, ties and odd leftovers are dropped; per step
+`ddpo_amd.training.diffusion_dpo.train_step` (posterior samples, one DDPM noise and timestep per pair, U-Net forward [cond + uncond] of
+the policy with a tape and of the frozen pretrained copy without, the Diffusion-DPO pass, backward, clip + AdamW(bf16 mu) with the
+gradient all-reduce); checkpoints every `save_freq` epochs and at the end.  Sample with `--identical_batch True` or a small prompt set:
+a prompt that occurs once forms no pair."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import torch
+
+from ddpo_amd import utils
+from ddpo_amd.training import diffusion, diffusion_dpo, distributed as D
+from ddpo_amd.training.diffusion_dpo import INFO_KEYS, check_dpo_args
+from ddpo_amd.training.kl_reference import KLReference
+from ddpo_amd.training.policy_gradient import AccumulatingTrainState, AdamWConfig
+from ddpo_amd.utils import bucket, prng
+from ddpo_amd.utils.serialization import load_unet, save_checkpoint
+
+
+class Parser(utils.Parser):
+    config: str = "config.base"
+    dataset: str = "compressed_animals_dpo"
+
+
+def main(argv=None):
+    from ddpo_amd.models.lora import reject_lora_flags
+    reject_lora_flags(sys.argv[1:] if argv is None else argv)
+    worker_id, n_workers = D.init()
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if not torch.cuda.is_available():
+        raise SystemExit("pipeline/dpo.py needs a GPU: the DDPO engine has no CPU path")
+    torch.cuda.set_device(local_rank)
+    dev = torch.device("cuda", local_rank)
+    from ddpo_amd import lib as L
+    L.DATAPATH = L.shipped_datapath()
+
+    args = Parser(argv).parse_args("dpo", process_index=worker_id)      # offsets `seed` by the rank; `pair_seed` stays as given
+    utils.init_logging("dpo", args.verbose)
+    msg = check_dpo_args(args.dpo_beta, args.train_batch_size)
+    if msg:
+        raise SystemExit(msg)
+    modelpath = None if args.iteration == 0 else args.modelpath
+
+    # --------------------------------- models ---------------------------------#
+    load = lambda path: load_unet(path, epoch=args.load_epoch, pretrained_model=args.pretrained_model, dtype=args.dtype, cache=args.cache,
+                                  device=dev)
+    pipeline, params = load(None)
+    # the frozen reference: the PRETRAINED model, taken before a fine-tuned `modelpath` is loaded over the policy
+    ref = KLReference(pipeline.unet)
+    if modelpath is not None:
+        pipeline, params = load(modelpath)
+    unet, text_encoder, tokenizer = pipeline.unet, params["text_encoder"], pipeline.tokenizer
+    print(f"n unet params: {unet.params.n_params / 1e6:.3f}M | frozen reference U-Net of {ref.params.n_params} parameters")
+
+    # -------------------------------- dataset ---------------------------------#
+    worker_batch_size = args.train_batch_size * 1
+    pod_batch_size = worker_batch_size * n_workers
+    loadpath = args.loadpath.replace("gs://", "logs/")
+    reader, loader = bucket.get_pair_loader(loadpath, tokenizer, worker_batch_size, args.filter_field,
+                                            max_train_samples=args.max_train_samples, host_id=worker_id, n_hosts=n_workers)
+
+    # ------------------------------- optimizer --------------------------------#
+    state = AccumulatingTrainState(unet, AdamWConfig(learning_rate=args.learning_rate, b1=args.beta1, b2=args.beta2, eps=args.epsilon,
+                                                     weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm))
+    noise_scheduler = diffusion.DDPMNoiseScheduler(beta_start=0.00085, beta_end=0.012, num_train_timesteps=1000)
+    noise_scheduler_state = noise_scheduler.create_state(dev)
+
+    # -------------------------- generic training setup ------------------------#
+    rng = prng.PRNGKey(args.seed)
+    train_rng = prng.split(rng, 1)[0]
+    static_broadcasted = (noise_scheduler, text_encoder, args.train_cfg, args.guidance_scale)
+    print(f"[ dpo ] dataset size: {loader.n_rows} | batch size per device: {args.train_batch_size} | total pod batch size: {pod_batch_size} | "
+          f"n epochs: {args.num_train_epochs} | beta: {args.dpo_beta:g} | max steps: {args.max_train_steps}")
+
+    # -------------------------------- main loop -------------------------------#
+    savepath = args.savepath.replace("gs://", "logs/")
+    global_step, history, first_step = 0, [], None
+    done = lambda: args.max_train_steps is not None and global_step >= args.max_train_steps
+    for epoch in range(args.num_train_epochs):
+        kept, ties, leftover = loader.pair(args.pair_seed + epoch)
+        if worker_id == 0:
+            print(f"[ dpo ] Epoch {epoch} | pairs kept {kept} | ties dropped {ties} | rows left over {leftover} | "
+                  f"steps per epoch {len(loader)}")
+        if len(loader) == 0:
+            raise SystemExit(f"{kept} pairs over {n_workers} ranks do not fill one batch of {args.train_batch_size} rows")
+        infos = []
+        for batch in loader:
+            state, info, train_rng = diffusion_dpo.train_step(state, text_encoder, batch, train_rng, noise_scheduler_state,
+                                                              static_broadcasted, ref, args.dpo_beta)
+            infos.append(torch.stack([info[k] for k in INFO_KEYS]))
+            if first_step is None:
+                first_step = {k: float(v) for k, v in info.items()}
+            global_step += 1
+            if done():
+                break
+        mean = torch.stack(infos).mean(0)
+        avg = D.pmean_info({k: mean[i] for i, k in enumerate(INFO_KEYS)})
+        avg = {k: float(avg[k]) for k in INFO_KEYS}
+        history.append(dict(avg, epoch=epoch, pairs=kept, ties=ties, leftover=leftover))
+        if worker_id == 0:
+            print(f"[ dpo ] Epoch {epoch} | steps {global_step} | " + " | ".join(f"{k} {avg[k]:.6g}" for k in INFO_KEYS) +
+                  f" | cfg: {args.train_cfg} | scale: {args.guidance_scale}")
+        if (epoch + 1) % args.save_freq == 0 or epoch == args.num_train_epochs - 1 or done():
+            if worker_id == 0:
+                save_checkpoint(os.path.join(savepath, "checkpoints"), unet.params, (epoch + 1) // args.save_freq * args.save_freq,
+                                synthetic_weights=bool(pipeline.synthetic_weights))
+        if done():
+            break
+    if worker_id == 0:                                      # what main() returns, for a caller that only has the run directory
+        with open(os.path.join(savepath, "dpo_history.json"), "w") as f:
+            json.dump({"history": history, "first_step": first_step, "steps": global_step}, f, indent=2)
+    return {"history": history, "first_step": first_step, "state": state, "savepath": savepath, "loadpath": loadpath}
+
+
+if __name__ == "__main__":
+    main()
