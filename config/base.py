@@ -41,6 +41,12 @@ _PG_DEFAULTS = (
     # d3po_beta 0.1 is the value the D3PO authors ship (their log-prob is a mean over the latent, as here); it has not been measured in a
     # training run on this engine.
     ("pg_loss", "ppo"), ("d3po_beta", 0.1),
+    # engine-specific addition: rescaled classifier-free guidance (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed",
+    # §3.4; diffusers' `guidance_rescale`; ddpo_amd/lib_cfg_rescale.py): the guided prediction is scaled per sample towards the
+    # standard deviation of the conditional one, out = (1 - r + r std(cond) / std(guided)) * guided.  v-prediction checkpoints (SD-2.1 768)
+    # are normally sampled with 0.7; the sampler and every loss (PPO ratio, KL, D3PO log-ratio) then use the rescaled prediction.  0 = off
+    # (the reference's only mode): nothing new is launched.  In [0, 1]; a positive value needs train_cfg True.
+    ("guidance_rescale", 0.0),
 )
 
 _SAMPLE_DEFAULTS = (
@@ -70,6 +76,11 @@ _DPO_DEFAULTS = tuple(kv for kv in _TRAIN_DEFAULTS if kv[0] not in ("weighted_ba
 )
 
 base = {"sample": dict(_SAMPLE_DEFAULTS), "train": dict(_TRAIN_DEFAULTS), "pg": dict(_PG_DEFAULTS), "dpo": dict(_DPO_DEFAULTS)}
+
+# engine-specific additions to experiments whose table above is held EQUAL to the reference's (`sample`, `train`): kept beside it, and read by
+# the entry point's parser after the table and the dataset's overrides (pipeline/sample.py).  guidance_rescale: as in `pg` above.
+_SAMPLE_ENGINE_DEFAULTS = (("guidance_rescale", 0.0),)
+engine = {"sample": dict(_SAMPLE_ENGINE_DEFAULTS)}
 
 # the two `sample` recipes of the reference's datasets: keep the top decile of 1024 identical-prompt batches (filter-finetune),
 # or keep all of 10240 samples (reward-weighted regression)

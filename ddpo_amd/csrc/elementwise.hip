@@ -3,6 +3,7 @@
 // clip and accumulation scaling, plus the small layout / activation kernels of the U-Net.
 // Built with -ffp-contract=off so the fp32 operation order matches the CPU oracle.
 #include "common.h"
+#include "../../include/ddpo_cfg_rescale.h"
 #include <math.h>
 
 extern "C" int ddpo_abi_version(void) { return 15; }
@@ -485,6 +486,46 @@ extern "C" int ddpo_rwr_noisy_latents(const float* moments, const float* e1, con
     return DDPO_EINVAL;
   hipLaunchKernelGGL(rwr_noisy_latents_kernel, dim3(B), dim3(256), 0, as_stream(stream), moments, e1, noise, ts, alphas_cumprod,
                      num_train_timesteps, scale, latents, noisy, C, hw);
+  DDPO_LAUNCH_CHECK();
+  return DDPO_OK;
+}
+
+// The same pass with the regression target of the model's prediction type (include/ddpo_cfg_rescale.h): latents and noisy by the expressions
+// above (bit-equal), target = noise | sa noise - sb latents (the v of Salimans & Ho) | latents.
+__global__ void __launch_bounds__(256) rwr_noisy_latents_target_kernel(const float* __restrict__ moments, const float* __restrict__ e1,
+                                                                       const float* __restrict__ noise, const int32_t* __restrict__ ts,
+                                                                       const float* __restrict__ acp, int n_train, float scale,
+                                                                       int pred_type, float* __restrict__ latents,
+                                                                       float* __restrict__ noisy, float* __restrict__ target, int C, int hw) {
+  const int b = blockIdx.x;
+  int t = ts[b];
+  t = t < 0 ? 0 : (t >= n_train ? n_train - 1 : t);
+  const float a = acp[t];
+  const float sa = sqrtf(a), sb = sqrtf(1.0f - a);
+  const int64_t mbase = (int64_t)b * hw * 2 * C, ebase = (int64_t)b * hw * C, obase = (int64_t)b * C * hw;
+  for (int i = threadIdx.x; i < hw * C; i += blockDim.x) {
+    const int p = i / C, c = i - p * C;
+    const float mean = moments[mbase + (int64_t)p * 2 * C + c];
+    float logvar = moments[mbase + (int64_t)p * 2 * C + C + c];
+    logvar = fminf(fmaxf(logvar, -30.0f), 20.0f);
+    const float z = (mean + expf(0.5f * logvar) * e1[ebase + i]) * scale;
+    const int64_t o = obase + (int64_t)c * hw + p;
+    const float nz = noise[o];
+    latents[o] = z;
+    noisy[o] = sa * z + sb * nz;
+    target[o] = pred_type == DDPO_PRED_EPSILON ? nz : (pred_type == DDPO_PRED_V ? sa * nz - sb * z : z);
+  }
+}
+
+extern "C" int ddpo_rwr_noisy_latents_target(const float* moments, const float* e1, const float* noise, const int32_t* ts,
+                                             const float* alphas_cumprod, int num_train_timesteps, float scale, int pred_type,
+                                             float* latents, float* noisy, float* target, int B, int C, int hw, void* stream) {
+  if (!moments || !e1 || !noise || !ts || !alphas_cumprod || !latents || !noisy || !target || B <= 0 || C <= 0 || hw <= 0 ||
+      num_train_timesteps <= 0)
+    return DDPO_EINVAL;
+  if (pred_type != DDPO_PRED_EPSILON && pred_type != DDPO_PRED_V && pred_type != DDPO_PRED_SAMPLE) return DDPO_EINVAL;
+  hipLaunchKernelGGL(rwr_noisy_latents_target_kernel, dim3(B), dim3(256), 0, as_stream(stream), moments, e1, noise, ts, alphas_cumprod,
+                     num_train_timesteps, scale, pred_type, latents, noisy, target, C, hw);
   DDPO_LAUNCH_CHECK();
   return DDPO_OK;
 }

@@ -11,6 +11,7 @@ Trajectories never leave HBM: one (T+1, B, C, h, w) buffer holds x_T .. x_0; `la
 `next_latents` = buf[1:] are returned as (B, T, ...) views of it (the reference copies them to host numpy,
 /root/reference/pipeline/policy_gradient.py:292-295).
 """
+import math
 import os
 
 import numpy as np
@@ -41,8 +42,11 @@ class StableDiffusionPipeline:
         return text_input.input_ids
 
     def _generate(self, prompt_embeds, neg_prompt_embeds, params, rng, num_inference_steps, height, width,
-                  guidance_scale, eta, latents=None, jit=False):
+                  guidance_scale, eta, latents=None, jit=False, guidance_rescale=0.0):
         assert isinstance(self.scheduler, DDIMScheduler)
+        rescale = float(guidance_rescale)
+        if not (math.isfinite(rescale) and 0.0 <= rescale <= 1.0):
+            raise ValueError(f"`guidance_rescale` has to be a finite number in [0, 1] but is {guidance_rescale}.")
         if height % 8 != 0 or width % 8 != 0:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
         dev = self.unet.device
@@ -78,6 +82,12 @@ class StableDiffusionPipeline:
         consts = self.scheduler.kernel_consts(state, eta)
         z = torch.empty(shape, dtype=torch.float32, device=dev)
         lat2 = torch.empty((2 * B,) + shape[1:], dtype=torch.float32, device=dev)
+        if rescale > 0:
+            # not in the reference: the rescaled guidance of v-prediction checkpoints (lib_cfg_rescale.py).  One launch per step
+            # turns the two halves into the rescaled guided prediction; the step kernel then gets it as BOTH halves (u + g (u - u) is u exactly)
+            from .. import lib_cfg_rescale as LR
+            guided = torch.empty(shape, dtype=torch.float32, device=dev)
+            rstats = torch.empty(B, 4, dtype=torch.float32, device=dev)
         # jit=True (the reference's pmapped/jitted path): replay the U-Net as a captured HIP graph
         unet_fwd = self.unet.forward_graphed if jit else self.unet
         # the text context is the same for all T steps: project it through the cross-attention to_k / to_v once
@@ -104,6 +114,10 @@ class StableDiffusionPipeline:
                     lat2[B:].copy_(x)
                     noise_pred = unet_fwd(lat2, ts_dev[s], context, cfg_dup=True) if dedupe else unet_fwd(lat2, ts_dev[s], context)
                 L.threefry_normal(step_keys[s], shape, out=z)
+                if rescale > 0:
+                    LR.cfg_rescale_fwd(noise_pred[B:], noise_pred[:B], guidance_scale, rescale, out=guided, stats=rstats)
+                    L.ddim_step_fwd(guided, guided, x, z, ts_dev[s, :B], guidance_scale, consts, x_next=traj[s + 1], logp=log_probs[s])
+                    continue
                 L.ddim_step_fwd(noise_pred[:B], noise_pred[B:], x, z, ts_dev[s, :B], guidance_scale, consts,
                                 x_next=traj[s + 1], logp=log_probs[s])
         finally:
@@ -116,9 +130,11 @@ class StableDiffusionPipeline:
         return (final_latents, traj[:T].transpose(0, 1), traj[1:].transpose(0, 1), log_probs.transpose(0, 1), ts)
 
     def __call__(self, prompt_embeds, neg_prompt_embeds, params, prng_seed, num_inference_steps=50, height=None, width=None,
-                 guidance_scale=7.5, eta=0.0, latents=None, jit=False):
+                 guidance_scale=7.5, eta=0.0, latents=None, jit=False, guidance_rescale=0.0):
         """Same argument order as the reference (:272-285).  Inputs may carry the reference's leading device axis of
-        length 1; outputs then carry it too: (final_latents, latents, next_latents, log_probs, ts)."""
+        length 1; outputs then carry it too: (final_latents, latents, next_latents, log_probs, ts).
+        guidance_rescale (not in the reference; last, so that its order stays): the rescaled classifier-free guidance v-prediction
+        checkpoints are sampled with, in [0, 1]; the log-probs are then those of the rescaled prediction.  0: the reference's sampler."""
         height = height or 64 * self.vae_scale_factor
         width = width or 64 * self.vae_scale_factor
         dev_axis = prompt_embeds.ndim == 4
@@ -132,7 +148,7 @@ class StableDiffusionPipeline:
                 latents = latents[0]
         to_t = lambda a: a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
         outs = self._generate(to_t(prompt_embeds), to_t(neg_prompt_embeds), params, prng_seed, num_inference_steps,
-                              height, width, float(guidance_scale), float(eta), latents, jit=bool(jit))
+                              height, width, float(guidance_scale), float(eta), latents, jit=bool(jit), guidance_rescale=guidance_rescale)
         if dev_axis:
             outs = tuple(o.unsqueeze(0) for o in outs)
         return outs

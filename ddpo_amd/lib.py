@@ -644,6 +644,13 @@ def rwr_noisy_latents(moments, e1, noise, ts, alphas_cumprod_dev, scale=0.18215)
     return lat, noisy
 
 
+def rwr_noisy_latents_target(moments, e1, noise, ts, alphas_cumprod_dev, prediction_type, scale=0.18215):
+    """rwr_noisy_latents plus the regression target of `prediction_type` -> (latents, noisy_latents, target).  The entry is declared in
+    include/ddpo_cfg_rescale.h and bound by lib_cfg_rescale.py, which is imported only here: epsilon models never come this way."""
+    from . import lib_cfg_rescale as LR
+    return LR.rwr_noisy_latents_target(moments, e1, noise, ts, alphas_cumprod_dev, prediction_type, scale)
+
+
 def rwr_mse_fwd_bwd(eps_c, eps_u, noise, weights, guidance_scale, train_cfg):
     """Weighted denoising MSE + its closed-form gradient.  Returns (d_eps_c, d_eps_u | None, per_sample (B,2), loss (1,))."""
     B = eps_c.shape[0]

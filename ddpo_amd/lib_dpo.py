@@ -43,7 +43,7 @@ def load():
 
 def dpo_pair_fwd_bwd(eps_c, eps_u, ref_c, ref_u, target, pref, guidance_scale, beta, train_cfg):
     """The Diffusion-DPO loss of adjacent row pairs (2p, 2p+1) and its gradient, in the place of lib.rwr_mse_fwd_bwd on the current stream.
-    `target` (B, C, h, w): the regression target (the DDPM noise).  `pref` (B,): +1 winner, -1 loser, 0 tie.
+    `target` (B, C, h, w): the regression target of the model's prediction type (the DDPM noise; v for a v-prediction model).  `pref` (B,): +1 winner, -1 loser, 0 tie.
     Returns (d_eps_c, d_eps_u | None, per_row (B, 2) = {m, D}, per_pair (B // 2, 3) = {s, loss, q},
     info (5,) = {loss, implicit_acc, margin, mse, ref_mse})."""
     B = eps_c.shape[0]

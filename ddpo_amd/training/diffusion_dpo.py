@@ -30,10 +30,11 @@ def check_dpo_args(dpo_beta, train_batch_size):
     return None
 
 
-def prepare_pair_latents(vae_moments, train_rng, noise_scheduler_state):
+def prepare_pair_latents(vae_moments, train_rng, noise_scheduler_state, prediction_type=None):
     """The key tree of diffusion.prepare_latents with the diffusion noise and the timestep drawn per PAIR: vae_moments (B,h,w,2C) NHWC with
     pairs on adjacent rows -> (noise (B,C,h,w), timesteps (B,), noisy_latents, new_train_rng); rows 2p and 2p+1 share noise and timestep
-    (the authors' training code), each row has its own posterior sample."""
+    (the authors' training code), each row has its own posterior sample.  `prediction_type` given: the same draws and noisy latents, and a
+    fifth result, the regression target of such a model (diffusion.prepare_latents); rows of a pair share the noise, not the target."""
     dev = vae_moments.device
     B, h, w, C2 = vae_moments.shape
     if B % 2:
@@ -45,6 +46,10 @@ def prepare_pair_latents(vae_moments, train_rng, noise_scheduler_state):
     noise = prng.normal(noise_rng, (B // 2, C, h, w), device=dev).repeat_interleave(2, dim=0).contiguous()
     ts_host = np.repeat(prng.randint(timestep_rng, (B // 2,), 0, noise_scheduler_state.numel()), 2)
     ts = torch.from_numpy(ts_host).to(dev)
+    if prediction_type is not None:
+        _lat, noisy, target = L.rwr_noisy_latents_target(vae_moments.contiguous(), e1, noise, ts, noise_scheduler_state, prediction_type,
+                                                         VAE_SCALING)
+        return noise, ts, noisy, new_train_rng, target
     _lat, noisy = L.rwr_noisy_latents(vae_moments.contiguous(), e1, noise, ts, noise_scheduler_state, VAE_SCALING)
     return noise, ts, noisy, new_train_rng
 
@@ -56,7 +61,11 @@ def forward_backward(unet, text_encoder, batch, train_rng, noise_scheduler_state
     dev = unet.device
     moments = torch.as_tensor(batch["vae"], dtype=torch.float32, device=dev)
     pref = torch.as_tensor(batch["pref"], dtype=torch.float32, device=dev).reshape(-1).contiguous()
-    noise, ts, noisy, new_train_rng = prepare_pair_latents(moments, train_rng, noise_scheduler_state)
+    pred = unet.cfg.prediction_type
+    if pred == "epsilon":                                      # the target is the noise: today's launch
+        noise, ts, noisy, new_train_rng = prepare_pair_latents(moments, train_rng, noise_scheduler_state)
+    else:                                                      # v-prediction / sample models: the errors are taken against their own target
+        _, ts, noisy, new_train_rng, noise = prepare_pair_latents(moments, train_rng, noise_scheduler_state, prediction_type=pred)
     emb = batch["prompt_embeds"] if "prompt_embeds" in batch else text_encoder(batch["input_ids"])
     b = noisy.shape[0]
     tape = []

@@ -20,6 +20,9 @@ MI355X design notes
   * `--pg_loss d3po` (not in the reference): a DPO loss per DDIM step on adjacent row pairs ranked by preference, on the policy-to-pretrained
     log-ratio of each stored transition (lib_pref.py).  Its pass stands in the place of the PPO launch and reads the same
     frozen forward a KL penalty would; with the default `ppo` none of it is imported or launched.
+  * `--guidance_rescale` (not in the reference): the policy is the RESCALED guided prediction the sampler ran (lib_cfg_rescale.py,
+    DESIGN.md §4).  One launch between the U-Net forward and the loss passes, which then see a single prediction (their train_cfg = False
+    form), and one between them and the U-Net backward; with guidance_rescale == 0 neither exists.
 """
 import numpy as np
 import torch
@@ -36,6 +39,19 @@ ADV_CLIP_MAX = 10.0
 DEFAULT_TRAIN_FUSE = 16
 LOSSES = ("ppo", "d3po")
 D3PO_BETA = 0.1          # config/base.py `d3po_beta`: the D3PO authors' shipped value
+
+
+def check_rescale_args(guidance_rescale, train_cfg):
+    """The entrypoint's argument check, as a plain function: a message to exit with, or None.  `train_cfg` None: the sampling entry point,
+    which always runs both halves."""
+    import math
+    phi = float(guidance_rescale)
+    if not (math.isfinite(phi) and 0.0 <= phi <= 1.0):
+        return f"--guidance_rescale must be a finite number in [0, 1], got {phi}"
+    if phi > 0.0 and train_cfg is not None and not train_cfg:
+        return (f"--guidance_rescale {phi} needs --train_cfg True: without the unconditional half of the prediction there is nothing to "
+                f"rescale against")
+    return None
 
 
 def train_fuse_default(unet_rows_per_micro_step=None, latent_pixels=None):
@@ -166,7 +182,7 @@ class AccumulatingTrainState:
 
 
 def _fwd_bwd(state, batch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta, clip_range, group=None, on_ready=None,
-             kl_coef=0.0, ref_unet=None, loss="ppo", d3po_beta=None):
+             kl_coef=0.0, ref_unet=None, loss="ppo", d3po_beta=None, guidance_rescale=0.0):
     """U-Net forward (cond + uncond as one batch), scoring-mode log-prob + PPO-clip forward/backward, U-Net backward
     (parameter gradients accumulate in place).  Pure device work: capturable into a HIP graph.
     `group`: rows per PPO micro-batch when the batch holds several micro-batches (train_steps_fused); info is then (k, 3).
@@ -174,7 +190,14 @@ def _fwd_bwd(state, batch, noise_scheduler_state, noise_scheduler, train_cfg, gu
     gradient to the PPO gradient and kl_coef * kl to info's loss column; the third result is the per-micro-batch KL (else None).
     loss == "d3po": the preference-pair pass (lib_pref.py) stands in the place of the PPO launch; batch["advantages"] carries the labels
     (+1 winner, -1 loser, 0 tie; rows in adjacent pairs), batch["log_probs"] is not read, info is {pref_acc, pref_margin, loss} and the second
-    result is per_pair (b / 2, 4).  The one frozen forward serves this pass and the KL pass alike."""
+    result is per_pair (b / 2, 4).  The one frozen forward serves this pass and the KL pass alike.
+    guidance_rescale > 0 (needs train_cfg): the policy's prediction, and the frozen one's, is the rescaled guided prediction of
+    lib_cfg_rescale.cfg_rescale_fwd; the passes above run on it in their train_cfg = False form and cfg_rescale_bwd turns its cotangent
+    into those of the two U-Net halves."""
+    bad = check_rescale_args(guidance_rescale, train_cfg)
+    if bad:
+        raise ValueError(bad.replace("--", ""))
+    rescale = float(guidance_rescale)
     if loss not in LOSSES:
         raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
     d3po = loss == "d3po"
@@ -205,20 +228,31 @@ def _fwd_bwd(state, batch, noise_scheduler_state, noise_scheduler, train_cfg, gu
         if need_ref:
             ref_u, ref_c = None, ref_unet.forward(lat, ts, batch["prompt_embeds"])
     consts = noise_scheduler.kernel_consts(noise_scheduler_state, eta)
+    loss_cfg = train_cfg
+    if rescale > 0:
+        from .. import lib_cfg_rescale as LR
+        pol_c, pol_u = eps_c, eps_u
+        eps_c, rstats = LR.cfg_rescale_fwd(pol_c, pol_u, guidance_scale, rescale)
+        if need_ref:
+            ref_c, _ = LR.cfg_rescale_fwd(ref_c, ref_u, guidance_scale, rescale)
+        eps_u = ref_u = None
+        loss_cfg = False                        # the passes below see ONE prediction: the rescaled one
     if d3po:
         from .. import lib_pref as LP
         d_c, d_u, per_sample, info = LP.ddim_pref_fwd_bwd(eps_c, eps_u, ref_c, ref_u, lat, batch["next_latents"], ts, batch["advantages"],
-                                                          guidance_scale, D3PO_BETA if d3po_beta is None else d3po_beta, train_cfg, consts,
+                                                          guidance_scale, D3PO_BETA if d3po_beta is None else d3po_beta, loss_cfg, consts,
                                                           group=group)
     else:
         d_c, d_u, per_sample, info = L.ddim_logprob_ppo_fwd_bwd(eps_c, eps_u, lat, batch["next_latents"], ts, batch["log_probs"],
-                                                                batch["advantages"], guidance_scale, clip_range, train_cfg, consts,
+                                                                batch["advantages"], guidance_scale, clip_range, loss_cfg, consts,
                                                                 group=group)
     kl = None
     if kl_coef > 0:
         from .. import lib_ppo_kl as LK
-        _, kl = LK.ddim_kl_ref_fwd_bwd(eps_c, eps_u, ref_c, ref_u, ts, guidance_scale, kl_coef, train_cfg, consts, d_c, d_u, loss_info=info,
+        _, kl = LK.ddim_kl_ref_fwd_bwd(eps_c, eps_u, ref_c, ref_u, ts, guidance_scale, kl_coef, loss_cfg, consts, d_c, d_u, loss_info=info,
                                        group=group)
+    if rescale > 0:
+        d_c, d_u = LR.cfg_rescale_bwd(pol_c, pol_u, d_c, rstats, guidance_scale, rescale)
     d_out = torch.cat([d_u, d_c]) if train_cfg else d_c
     unet.backward(tape, d_out, on_ready=on_ready)
     return info, per_sample, kl
@@ -228,7 +262,7 @@ _KEYS = ("latents", "next_latents", "ts", "log_probs", "advantages", "prompt_emb
 
 
 def _graphed_fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale, eta, clip_range, group=None, kl_coef=0.0, ref_unet=None,
-                     loss="ppo", d3po_beta=None):
+                     loss="ppo", d3po_beta=None, guidance_rescale=0.0):
     """Replay of _fwd_bwd as a captured HIP graph (one per batch geometry / hyper-parameter set): ~3000 kernel launches per
     micro-step become one graph launch.  Gradients still accumulate into the same flat buffer."""
     key = (tuple(batch["latents"].shape), tuple(batch["prompt_embeds"].shape), bool(train_cfg), float(guidance_scale), float(eta),
@@ -238,6 +272,9 @@ def _graphed_fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale
     if loss != "ppo":
         key += (loss, float(D3PO_BETA if d3po_beta is None else d3po_beta))
         klkw.update(loss=loss, d3po_beta=d3po_beta)
+    if guidance_rescale > 0:
+        key += ("guidance_rescale", float(guidance_rescale))
+        klkw.update(guidance_rescale=float(guidance_rescale))
     cache = state.__dict__.setdefault("_graphs", {})
     ent = cache.get(key)
     if ent == "eager":
@@ -271,13 +308,15 @@ def _graphed_fwd_bwd(state, batch, sched_state, sched, train_cfg, guidance_scale
     return info.clone(), per_sample.clone(), None if kl is None else kl.clone()
 
 
-def _loss_kwargs(kl_coef, ref_unet, loss, d3po_beta):
-    """Keyword arguments of _fwd_bwd beyond the default step's: none at all for PPO without a penalty."""
+def _loss_kwargs(kl_coef, ref_unet, loss, d3po_beta, guidance_rescale=0.0):
+    """Keyword arguments of _fwd_bwd beyond the default step's: none at all for PPO without a penalty and without rescale."""
     if loss not in LOSSES:
         raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
     kw = dict(kl_coef=float(kl_coef), ref_unet=ref_unet) if kl_coef > 0 else {}
     if loss != "ppo":
         kw.update(loss=loss, d3po_beta=d3po_beta, ref_unet=ref_unet)
+    if guidance_rescale > 0:
+        kw.update(guidance_rescale=float(guidance_rescale))
     return kw
 
 
@@ -296,14 +335,15 @@ def _info_dict(loss, info, per_sample, rows=None):
 
 
 def train_step(state: AccumulatingTrainState, batch, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale,
-               eta, clip_range, do_opt_update, jit=True, kl_coef=0.0, ref_unet=None, loss="ppo", d3po_beta=None):
+               eta, clip_range, do_opt_update, jit=True, kl_coef=0.0, ref_unet=None, loss="ppo", d3po_beta=None, guidance_rescale=0.0):
     """One PPO micro-step (reference :63-146).  batch: latents, next_latents (b,4,h,w), ts (b,) int32, log_probs,
     advantages (b,), prompt_embeds, uncond_embeds (b,77,D) — device tensors.  Returns (state, info) with info a dict
     of device scalars {approx_kl, clipfrac, loss}.
     kl_coef > 0 (with ref_unet, the frozen pretrained policy): loss includes kl_coef * KL to it and info gains "kl_ref", that KL.
     loss="d3po" (with ref_unet): rows are adjacent preference pairs, batch["advantages"] their labels (+1 / -1 / 0), batch["log_probs"] is
-    ignored and may be absent; info is {pref_acc, pref_margin, loss} (+ kl_ref), d3po_beta the DPO temperature (default D3PO_BETA)."""
-    klkw = _loss_kwargs(kl_coef, ref_unet, loss, d3po_beta)
+    ignored and may be absent; info is {pref_acc, pref_margin, loss} (+ kl_ref), d3po_beta the DPO temperature (default D3PO_BETA).
+    guidance_rescale > 0 (with train_cfg): the value the sampler ran with; log-prob, ratio, KL and log-ratio are the rescaled prediction's."""
+    klkw = _loss_kwargs(kl_coef, ref_unet, loss, d3po_beta, guidance_rescale)
     assert isinstance(state, AccumulatingTrainState)
     b = batch["latents"].shape[0]
     assert b == batch["ts"].shape[0] == batch["next_latents"].shape[0] == batch["advantages"].shape[0]
@@ -331,7 +371,7 @@ def train_step(state: AccumulatingTrainState, batch, noise_scheduler_state, nois
 
 
 def train_steps_fused(state: AccumulatingTrainState, batches, noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale,
-                      eta, clip_range, do_opt_update, jit=True, kl_coef=0.0, ref_unet=None, loss="ppo", d3po_beta=None):
+                      eta, clip_range, do_opt_update, jit=True, kl_coef=0.0, ref_unet=None, loss="ppo", d3po_beta=None, guidance_rescale=0.0):
     """k consecutive PPO micro-steps that see the SAME parameters — no optimizer update between them, i.e. any run of
     `train_step(..., do_opt_update=False)` calls optionally closed by one with `do_opt_update=True` — executed as ONE U-Net
     forward/backward over the concatenated rows.  The reference runs them one by one and sums their gradients in
@@ -342,16 +382,18 @@ def train_steps_fused(state: AccumulatingTrainState, batches, noise_scheduler_st
     (`ddpo_ddim_logprob_ppo_fwd_bwd` with `group`) and its own info row, and n_acc advances by k.
 
     batches: list of k dicts as for `train_step`, all with the same shapes.  `do_opt_update` applies after the LAST one.
-    `loss` / `d3po_beta` as for `train_step`: with "d3po" every micro-batch is a whole number of adjacent preference pairs.
+    `loss` / `d3po_beta` / `guidance_rescale` as for `train_step`: with "d3po" every micro-batch is a whole number of adjacent preference
+    pairs; the rescale is per row, so the fused rows need nothing of their own.
     Returns (state, [info_0, ..., info_{k-1}])."""
     assert isinstance(state, AccumulatingTrainState)
     k = len(batches)
     assert k >= 1
     if k == 1:
         state, info = train_step(state, batches[0], noise_scheduler_state, noise_scheduler, train_cfg, guidance_scale, eta,
-                                 clip_range, do_opt_update, jit=jit, kl_coef=kl_coef, ref_unet=ref_unet, loss=loss, d3po_beta=d3po_beta)
+                                 clip_range, do_opt_update, jit=jit, kl_coef=kl_coef, ref_unet=ref_unet, loss=loss, d3po_beta=d3po_beta,
+                                 guidance_rescale=guidance_rescale)
         return state, [info]
-    klkw = _loss_kwargs(kl_coef, ref_unet, loss, d3po_beta)
+    klkw = _loss_kwargs(kl_coef, ref_unet, loss, d3po_beta, guidance_rescale)
     batches = [_with_log_probs(bt, loss) for bt in batches]
     b = batches[0]["latents"].shape[0]
     for bt in batches:

@@ -3,8 +3,8 @@
  *
  * Diffusion-DPO (Wallace et al., "Diffusion Model Alignment Using Direct Preference Optimization"): two samples of one prompt are ranked
  * and the policy is trained so that its denoising error drops faster on the winner than on the loser, relative to the frozen pretrained
- * model.  Rows come in adjacent pairs (2p, 2p+1), as in ddpo_pref.h.  Per row b, with `target` the regression target (the DDPM noise, as
- * in ddpo_rwr_mse_fwd_bwd) and g the guidance scale (Diffusion-DPO):
+ * model.  Rows come in adjacent pairs (2p, 2p+1), as in ddpo_pref.h.  Per row b, with `target` the regression target (the DDPM noise for
+ * an epsilon model, v for a v-prediction model: ddpo_rwr_noisy_latents_target) and g the guidance scale (Diffusion-DPO):
  *   e       = eps_u + g (eps_c - eps_u)                                                     (train_cfg == 0: e = eps_c)
  *   delta   = delta_u + g (delta_c - delta_u), delta_c = eps_c - ref_c, delta_u = eps_u - ref_u   (differences per branch first)
  *   a       = target - e

@@ -19,7 +19,8 @@ gradients are all-reduced once per optimizer update instead of every micro-step 
 `info` is fetched once per inner epoch instead of a blocking device_get + assert_equal per step (:442-445).
 Not in the reference: `--kl_coef c` adds c * KL(policy || frozen pretrained policy) per DDIM step to the PPO loss (DESIGN.md §4);
 `--pg_loss d3po` trains on preference pairs instead: prompts are drawn once per two adjacent rows, each pair is ranked by the sign of its reward
-difference, and a DPO loss per DDIM step on the policy-to-pretrained log-ratio stands in the place of PPO-clip.
+difference, and a DPO loss per DDIM step on the policy-to-pretrained log-ratio stands in the place of PPO-clip (DESIGN.md §4);
+`--guidance_rescale r` samples and trains with the rescaled classifier-free guidance v-prediction checkpoints expect.
 """
 import json
 import os
@@ -94,6 +95,12 @@ def check_d3po_args(args):
     return check(pg_loss, getattr(args, "d3po_beta", 0.1), args.eta, args.sample_batch_size, args.train_batch_size)
 
 
+def check_rescale_args(args):
+    """A message to exit with, or None: --guidance_rescale must be finite and in [0, 1], and a positive one needs --train_cfg True."""
+    from ddpo_amd.training.policy_gradient import check_rescale_args as check
+    return check(getattr(args, "guidance_rescale", 0.0), args.train_cfg)
+
+
 def check_resume_optimizer(rs, tx, where):
     """A resume bundle carries the moments of the optimizer that wrote it (bundles from before the field existed are AdamW's)."""
     wrote = rs.get("optimizer", "adamw")
@@ -120,14 +127,16 @@ def main(argv=None):
     args = Parser(argv).parse_args("pg", process_index=dp.seed_process_index)
     utils.init_logging("policy_gradient", args.verbose)
 
-    bad = check_kl_args(args) or check_d3po_args(args)
+    bad = check_kl_args(args) or check_d3po_args(args) or check_rescale_args(args)
     if bad:
         raise SystemExit(bad)
     kl_coef = float(args.kl_coef)
+    rescale = float(args.guidance_rescale)
     d3po = args.pg_loss == "d3po"
     # keyword arguments of the prompt draw, the shuffles and the training step beyond the default run's: none at all for --pg_loss ppo
     pairkw = dict(pairs=True) if d3po else {}
     losskw = dict(loss="d3po", d3po_beta=float(args.d3po_beta)) if d3po else {}
+    rescalekw = dict(guidance_rescale=rescale) if rescale > 0 else {}      # the sampler's and the training step's, alike
 
     rng = prng.PRNGKey(args.seed)
     n_devices = 1                                            # one process drives one GPU
@@ -158,7 +167,7 @@ def main(argv=None):
     with open(f"{localpath}/args.json", "w") as f:      # after loading: says which weights the run really started from
         json.dump(dict(args._dict, synthetic_weights=bool(pipeline.synthetic_weights), weights_source=pipeline.weights_source,
                        param_dtype=pipeline.param_dtype, datapath=L.DATAPATH, optimizer=args.optimizer, kl_coef=kl_coef,
-                       pg_loss=args.pg_loss, d3po_beta=float(args.d3po_beta)), f, indent=4,
+                       pg_loss=args.pg_loss, d3po_beta=float(args.d3po_beta), guidance_rescale=rescale), f, indent=4,
                   default=str)
     pipeline.safety_checker = None
     unet, vae = pipeline.unet, pipeline.vae
@@ -262,7 +271,7 @@ def main(argv=None):
             final_latents, latents, next_latents, log_probs, ts = pipeline(
                 sample_prompt_embeds, sample_uncond_prompt_embeds, {"unet": state.params, "scheduler": sampling_scheduler_params},
                 dp.sample_key(sample_seeds), args.n_inference_steps, jit=True, height=args.resolution, width=args.resolution,
-                guidance_scale=args.guidance_scale, eta=args.eta)
+                guidance_scale=args.guidance_scale, eta=args.eta, **rescalekw)
             # ----------------------------- decode latents ----------------------------- #
             if device_images:
                 images_dev = vae.decode(final_latents)
@@ -355,7 +364,7 @@ def main(argv=None):
                         print(f"opt update at {i}, {js[-1]}")
                     state, infos_k = train_steps_fused(state, batches, noise_scheduler_state, pipeline.scheduler, args.train_cfg,
                                                        args.guidance_scale, args.eta, args.ppo_clip_range, do_opt_update,
-                                                       kl_coef=kl_coef, ref_unet=ref_unet, **losskw)
+                                                       kl_coef=kl_coef, ref_unet=ref_unet, **losskw, **rescalekw)
                     all_infos += [torch.stack([info[k] for k in info_keys]) for info in infos_k]
                 for j in (range(num_train_ts) if train_fuse <= 1 else ()):
                     batch = {"prompt_embeds": mine["embeds"][sl], "uncond_embeds": train_uncond_prompt_embeds,
@@ -368,7 +377,7 @@ def main(argv=None):
                         print(f"opt update at {i}, {j}")
                     state, info = train_step(state, batch, noise_scheduler_state, pipeline.scheduler, args.train_cfg,
                                              args.guidance_scale, args.eta, args.ppo_clip_range, do_opt_update,
-                                             kl_coef=kl_coef, ref_unet=ref_unet, **losskw)
+                                             kl_coef=kl_coef, ref_unet=ref_unet, **losskw, **rescalekw)
                     all_infos.append(torch.stack([info[k] for k in info_keys]))
             assert do_opt_update
             infos = torch.stack(all_infos).cpu().numpy()            # ONE host sync per inner epoch

@@ -30,6 +30,14 @@ class Parser(utils.Parser):
     config: str = "config.base"
     dataset: str = "compressed_dogs"
 
+    def read_config(self, args, experiment):
+        """The reference's `sample` table and overrides, then the engine's own keys of config/base.py `engine` (--guidance_rescale)."""
+        super().read_config(args, experiment)
+        import importlib
+        for key, val in getattr(importlib.import_module(args.config), "engine", {}).get(experiment, {}).items():
+            if key not in args:
+                args.set(key, val)
+
 
 def main(argv=None):
     worker_id, n_workers = D.init()
@@ -42,6 +50,11 @@ def main(argv=None):
     L.DATAPATH = L.shipped_datapath()
 
     args = Parser(argv).parse_args("sample", process_index=worker_id)
+    from ddpo_amd.training.policy_gradient import check_rescale_args
+    bad = check_rescale_args(args.guidance_rescale, None)
+    if bad:
+        raise SystemExit(bad)
+    rescalekw = dict(guidance_rescale=float(args.guidance_rescale)) if args.guidance_rescale > 0 else {}
     rng = prng.PRNGKey(args.seed)
     n_devices = 1
     batch_size = n_devices * args.n_samples_per_device
@@ -88,7 +101,8 @@ def main(argv=None):
         print(f"[ sample ] prompts: {inference_prompts[:2]}")
         prompt_embeds = text_encode(pipeline.prepare_inputs(inference_prompts))
         final_latents, *_ = pipeline(prompt_embeds, uncond_prompt_embeds, params, prng_seeds[0], args.n_inference_steps, jit=True,
-                                     height=args.resolution, width=args.resolution, guidance_scale=args.guidance_scale, eta=args.eta)
+                                     height=args.resolution, width=args.resolution, guidance_scale=args.guidance_scale, eta=args.eta,
+                                     **rescalekw)
         images = pipeline.vae.decode(final_latents).cpu().numpy().astype(np.float32)
         print(f"[ sample ] {len(images)} samples in {timer():.2f} seconds | eval: {args.evaluate}")
         infos = training.evaluate_callbacks(callback_fns, images, training_prompts, prompt_metadata)
@@ -110,7 +124,7 @@ def main(argv=None):
         if args.max_samples is not None and n_samples >= args.max_samples:
             break
     writer.close(world=n_workers, metadata={"guidance_scale": args.guidance_scale, "filter_field": args.filter_field, "n_samples": int(n_samples),
-                           "synthetic_weights": bool(pipeline.synthetic_weights)})
+                           "synthetic_weights": bool(pipeline.synthetic_weights), **rescalekw})
     return savepath
 
 
