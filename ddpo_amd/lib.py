@@ -561,6 +561,38 @@ def _f32(t, name="tensor"):
     return t
 
 
+def bind_side(sigs, version_symbol, expected, what, module):
+    """The loader of the side bindings (lib_optim.py, lib_pref.py, lib_dpo.py, lib_cfg_rescale.py), each versioned on its
+    own: bind the table `sigs` on libddpo_hip.so and hold `version_symbol()` to `expected`.  `what` / `module` name the binding in the
+    version error.  A library without one of the entries is an error: there is no other path."""
+    load()                                      # "not built" is reported once, there
+    lib = ctypes.CDLL(LIB_PATH)
+    for name, (res, args) in sigs.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise DdpoHipError(f"libddpo_hip.so does not export {name}: rebuild with `python __graft_entry__.py`") from None
+        fn.restype = res
+        fn.argtypes = args
+    have = getattr(lib, version_symbol)()
+    if have != expected:
+        raise DdpoHipError(f"libddpo_hip.so has {what} ABI version {have}, {module} expects {expected}")
+    return lib
+
+
+def check_rows(B, chw, train_cfg, **rows):
+    """Shared check of the loss wrappers of the side bindings: every tensor of `rows`, in the order given, is there, float32 on the device
+    and of B x chw elements.  A name ending in `_u` is the unconditional half: looked at under train_cfg only."""
+    for name, t in rows.items():
+        if name.endswith("_u") and not train_cfg:
+            continue
+        if t is None:
+            raise DdpoHipError(f"{name} is required" + (" under train_cfg" if name.endswith("_u") else ""))
+        _f32(t, name)
+        if t.numel() != B * chw:
+            raise DdpoHipError(f"{name} has {t.numel()} elements, expected {B} x {chw}")
+
+
 # ------------------------------------------------------------------------------------------------ PRNG
 def threefry_bits_host(key, n):
     """uint32 words of jax `random_bits(key, n)` computed on the host (key bookkeeping)."""

@@ -3,7 +3,6 @@ classifier-free guidance of `--guidance_rescale` (forward and backward) and the 
 the model's prediction type.  Versioned on its own beside lib.py (ABI_VERSION here is ddpo_cfg_rescale_abi_version(), not lib.ABI_VERSION).
 Bound only when asked for: with guidance_rescale == 0 and an epsilon model nothing of this module is loaded or launched.
 """
-import ctypes
 import math
 from ctypes import c_float, c_int, c_void_p
 
@@ -27,22 +26,9 @@ _lib = None
 def load():
     """Bind the entry points of include/ddpo_cfg_rescale.h (idempotent).  A library without them is an error: there is no other path."""
     global _lib
-    if _lib is not None:
-        return _lib
-    L.load()                                    # "not built" is reported once, there
-    lib = ctypes.CDLL(L.LIB_PATH)
-    for name, (res, args) in _SIGS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise L.DdpoHipError(f"libddpo_hip.so does not export {name}: rebuild with `python __graft_entry__.py`") from None
-        fn.restype = res
-        fn.argtypes = args
-    if lib.ddpo_cfg_rescale_abi_version() != ABI_VERSION:
-        raise L.DdpoHipError(f"libddpo_hip.so has guidance-rescale ABI version {lib.ddpo_cfg_rescale_abi_version()}, "
-                             f"lib_cfg_rescale.py expects {ABI_VERSION}")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = L.bind_side(_SIGS, "ddpo_cfg_rescale_abi_version", ABI_VERSION, "guidance-rescale", "lib_cfg_rescale.py")
+    return _lib
 
 
 def _rows(eps_c, eps_u, guidance_rescale, extra=()):

@@ -2,7 +2,6 @@
 versioned on its own beside lib.py (ABI_VERSION here is ddpo_dpo_abi_version(), not lib.ABI_VERSION).  Bound only when that experiment is
 asked for: importing pipeline/finetune.py or pipeline/policy_gradient.py loads nothing of this module.
 """
-import ctypes
 import math
 from ctypes import c_float, c_int, c_void_p
 
@@ -24,21 +23,9 @@ _lib = None
 def load():
     """Bind the Diffusion-DPO entry points of libddpo_hip.so (idempotent).  A library without them is an error: there is no other path."""
     global _lib
-    if _lib is not None:
-        return _lib
-    L.load()                                    # "not built" is reported once, there
-    lib = ctypes.CDLL(L.LIB_PATH)
-    for name, (res, args) in _SIGS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise L.DdpoHipError(f"libddpo_hip.so does not export {name}: rebuild with `python __graft_entry__.py`") from None
-        fn.restype = res
-        fn.argtypes = args
-    if lib.ddpo_dpo_abi_version() != ABI_VERSION:
-        raise L.DdpoHipError(f"libddpo_hip.so has Diffusion-DPO ABI version {lib.ddpo_dpo_abi_version()}, lib_dpo.py expects {ABI_VERSION}")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = L.bind_side(_SIGS, "ddpo_dpo_abi_version", ABI_VERSION, "Diffusion-DPO", "lib_dpo.py")
+    return _lib
 
 
 def dpo_pair_fwd_bwd(eps_c, eps_u, ref_c, ref_u, target, pref, guidance_scale, beta, train_cfg):
@@ -52,15 +39,7 @@ def dpo_pair_fwd_bwd(eps_c, eps_u, ref_c, ref_u, target, pref, guidance_scale, b
         raise ValueError(f"beta must be finite and > 0, got {beta}")
     if B <= 0 or B % 2:
         raise ValueError(f"batch of {B} rows is not a whole number of adjacent pairs")
-    need = [("eps_c", eps_c), ("ref_c", ref_c), ("target", target)]
-    if train_cfg:
-        need += [("eps_u", eps_u), ("ref_u", ref_u)]
-    for name, t in need:
-        if t is None:
-            raise L.DdpoHipError(f"{name} is required" + (" under train_cfg" if name.endswith("_u") else ""))
-        L._f32(t, name)
-        if t.numel() != B * chw:
-            raise L.DdpoHipError(f"{name} has {t.numel()} elements, expected {B} x {chw}")
+    L.check_rows(B, chw, train_cfg, eps_c=eps_c, ref_c=ref_c, target=target, eps_u=eps_u, ref_u=ref_u)
     if L._f32(pref, "pref").numel() != B:
         raise L.DdpoHipError(f"pref must be {B} labels, got shape {tuple(pref.shape)}")
     dev = eps_c.device

@@ -48,23 +48,12 @@ _lib = None
 def load():
     """Bind the optimizer entry points of libddpo_hip.so (idempotent).  A library without them is an error: there is no other path."""
     global _lib
-    if _lib is not None:
-        return _lib
-    L.load()                                    # "not built" is reported once, there
-    lib = ctypes.CDLL(L.LIB_PATH)
-    for name, (res, args) in _SIGS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise L.DdpoHipError(f"libddpo_hip.so does not export {name}: rebuild with `python __graft_entry__.py`") from None
-        fn.restype = res
-        fn.argtypes = args
-    if lib.ddpo_optim_abi_version() != ABI_VERSION:
-        raise L.DdpoHipError(f"libddpo_hip.so has optimizer ABI version {lib.ddpo_optim_abi_version()}, lib_optim.py expects {ABI_VERSION}")
-    if lib.ddpo_sizeof_adafactor_tensor() != ctypes.sizeof(AdafactorTensor):
-        raise L.DdpoHipError("struct layout mismatch between include/ddpo_optim.h and ddpo_amd/lib_optim.py")
-    _lib = lib
-    return lib
+    if _lib is None:
+        lib = L.bind_side(_SIGS, "ddpo_optim_abi_version", ABI_VERSION, "optimizer", "lib_optim.py")
+        if lib.ddpo_sizeof_adafactor_tensor() != ctypes.sizeof(AdafactorTensor):
+            raise L.DdpoHipError("struct layout mismatch between include/ddpo_optim.h and ddpo_amd/lib_optim.py")
+        _lib = lib
+    return _lib
 
 
 def factored_dims(shape, min_dim_size_to_factor=MIN_DIM_SIZE_TO_FACTOR):

@@ -2,7 +2,6 @@
 versioned on its own beside lib.py (ABI_VERSION here is ddpo_pref_abi_version(), not lib.ABI_VERSION).  Bound only when that loss is asked
 for: with the default `ppo` nothing of this module is loaded or called (training/policy_gradient.py).
 """
-import ctypes
 import math
 from ctypes import POINTER, byref, c_float, c_int, c_void_p
 
@@ -24,21 +23,9 @@ _lib = None
 def load():
     """Bind the preference-loss entry points of libddpo_hip.so (idempotent).  A library without them is an error: there is no other path."""
     global _lib
-    if _lib is not None:
-        return _lib
-    L.load()                                    # "not built" is reported once, there
-    lib = ctypes.CDLL(L.LIB_PATH)
-    for name, (res, args) in _SIGS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise L.DdpoHipError(f"libddpo_hip.so does not export {name}: rebuild with `python __graft_entry__.py`") from None
-        fn.restype = res
-        fn.argtypes = args
-    if lib.ddpo_pref_abi_version() != ABI_VERSION:
-        raise L.DdpoHipError(f"libddpo_hip.so has preference-loss ABI version {lib.ddpo_pref_abi_version()}, lib_pref.py expects {ABI_VERSION}")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = L.bind_side(_SIGS, "ddpo_pref_abi_version", ABI_VERSION, "preference-loss", "lib_pref.py")
+    return _lib
 
 
 def ddim_pref_fwd_bwd(eps_c, eps_u, ref_c, ref_u, x, x_next, ts, pref, guidance_scale, beta, train_cfg, consts, group=None):
@@ -53,15 +40,7 @@ def ddim_pref_fwd_bwd(eps_c, eps_u, ref_c, ref_u, x, x_next, ts, pref, guidance_
     g = B if group is None else int(group)
     if B <= 0 or B % 2 or g <= 0 or g % 2 or B % g:
         raise ValueError(f"batch of {B} rows is not a whole number of micro-batches of {g} rows in adjacent pairs")
-    need = [("eps_c", eps_c), ("ref_c", ref_c), ("x", x), ("x_next", x_next)]
-    if train_cfg:
-        need += [("eps_u", eps_u), ("ref_u", ref_u)]
-    for name, t in need:
-        if t is None:
-            raise L.DdpoHipError(f"{name} is required" + (" under train_cfg" if name.endswith("_u") else ""))
-        L._f32(t, name)
-        if t.numel() != B * chw:
-            raise L.DdpoHipError(f"{name} has {t.numel()} elements, expected {B} x {chw}")
+    L.check_rows(B, chw, train_cfg, eps_c=eps_c, ref_c=ref_c, x=x, x_next=x_next, eps_u=eps_u, ref_u=ref_u)
     if ts.dtype != torch.int32 or ts.numel() != B:
         raise L.DdpoHipError(f"ts must be {B} int32 timesteps, got {ts.numel()} of {ts.dtype}")
     if L._f32(pref, "pref").numel() != B:

@@ -9,12 +9,9 @@ ddpo_rwr_mse_fwd_bwd, plus one inference forward of the frozen copy (training/kl
 """
 import math
 
-import numpy as np
 import torch
 
-from .. import lib as L
-from ..utils import prng
-from .diffusion import VAE_SCALING
+from .diffusion import noised_with_target, prepare_latents
 from .policy_gradient import AccumulatingTrainState
 
 INFO_KEYS = ("loss", "implicit_acc", "margin", "mse", "ref_mse")
@@ -35,23 +32,7 @@ def prepare_pair_latents(vae_moments, train_rng, noise_scheduler_state, predicti
     pairs on adjacent rows -> (noise (B,C,h,w), timesteps (B,), noisy_latents, new_train_rng); rows 2p and 2p+1 share noise and timestep
     (the authors' training code), each row has its own posterior sample.  `prediction_type` given: the same draws and noisy latents, and a
     fifth result, the regression target of such a model (diffusion.prepare_latents); rows of a pair share the noise, not the target."""
-    dev = vae_moments.device
-    B, h, w, C2 = vae_moments.shape
-    if B % 2:
-        raise ValueError(f"pairs sit on adjacent rows: the batch must be even, got {B}")
-    C = C2 // 2
-    _dropout_rng, sample_rng, new_train_rng = prng.split(np.asarray(train_rng, dtype=np.uint32), 3)
-    e1 = prng.normal(sample_rng, (B, h, w, C), device=dev)               # one posterior sample per row
-    noise_rng, timestep_rng = prng.split(sample_rng)
-    noise = prng.normal(noise_rng, (B // 2, C, h, w), device=dev).repeat_interleave(2, dim=0).contiguous()
-    ts_host = np.repeat(prng.randint(timestep_rng, (B // 2,), 0, noise_scheduler_state.numel()), 2)
-    ts = torch.from_numpy(ts_host).to(dev)
-    if prediction_type is not None:
-        _lat, noisy, target = L.rwr_noisy_latents_target(vae_moments.contiguous(), e1, noise, ts, noise_scheduler_state, prediction_type,
-                                                         VAE_SCALING)
-        return noise, ts, noisy, new_train_rng, target
-    _lat, noisy = L.rwr_noisy_latents(vae_moments.contiguous(), e1, noise, ts, noise_scheduler_state, VAE_SCALING)
-    return noise, ts, noisy, new_train_rng
+    return prepare_latents(vae_moments, train_rng, noise_scheduler_state, prediction_type, pairs=True)
 
 
 def forward_backward(unet, text_encoder, batch, train_rng, noise_scheduler_state, train_cfg, guidance_scale, ref, beta):
@@ -61,11 +42,8 @@ def forward_backward(unet, text_encoder, batch, train_rng, noise_scheduler_state
     dev = unet.device
     moments = torch.as_tensor(batch["vae"], dtype=torch.float32, device=dev)
     pref = torch.as_tensor(batch["pref"], dtype=torch.float32, device=dev).reshape(-1).contiguous()
-    pred = unet.cfg.prediction_type
-    if pred == "epsilon":                                      # the target is the noise: today's launch
-        noise, ts, noisy, new_train_rng = prepare_pair_latents(moments, train_rng, noise_scheduler_state)
-    else:                                                      # v-prediction / sample models: the errors are taken against their own target
-        _, ts, noisy, new_train_rng, noise = prepare_pair_latents(moments, train_rng, noise_scheduler_state, prediction_type=pred)
+    # `noise`: the target of the model's prediction type, against which both networks' errors are taken
+    noise, ts, noisy, new_train_rng = noised_with_target(unet, moments, train_rng, noise_scheduler_state, pairs=True)
     emb = batch["prompt_embeds"] if "prompt_embeds" in batch else text_encoder(batch["input_ids"])
     b = noisy.shape[0]
     tape = []

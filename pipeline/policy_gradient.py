@@ -39,8 +39,7 @@ import torch
 from ddpo_amd import training, utils
 from ddpo_amd.training import distributed as D
 from ddpo_amd.training.dp import DataParallel
-from ddpo_amd.training.policy_gradient import (AccumulatingTrainState, AdafactorConfig, AdamWConfig, train_fuse_default, train_step,
-                                               train_steps_fused)
+from ddpo_amd.training.policy_gradient import AccumulatingTrainState, AdafactorConfig, AdamWConfig, train_fuse_default, train_steps_fused
 from ddpo_amd.utils import prng
 from ddpo_amd.utils.serialization import load_params_file, load_resume, load_unet, mark_synthetic, save_checkpoint, save_rank_resume
 from ddpo_amd.utils.stat_tracking import PerPromptStatTracker
@@ -132,11 +131,7 @@ def main(argv=None):
         raise SystemExit(bad)
     kl_coef = float(args.kl_coef)
     rescale = float(args.guidance_rescale)
-    d3po = args.pg_loss == "d3po"
-    # keyword arguments of the prompt draw, the shuffles and the training step beyond the default run's: none at all for --pg_loss ppo
-    pairkw = dict(pairs=True) if d3po else {}
-    losskw = dict(loss="d3po", d3po_beta=float(args.d3po_beta)) if d3po else {}
-    rescalekw = dict(guidance_rescale=rescale) if rescale > 0 else {}      # the sampler's and the training step's, alike
+    d3po = args.pg_loss == "d3po"        # prompts, shuffles and the training step then work on adjacent pairs of rows
 
     rng = prng.PRNGKey(args.seed)
     n_devices = 1                                            # one process drives one GPU
@@ -261,7 +256,7 @@ def main(argv=None):
         for i in range(args.num_sample_batches_per_epoch):
             # ----------------------------- make prompts ----------------------------- #
             sample_prompts, training_prompts, prompt_metadata = dp.make_prompts(
-                args.prompt_fn, n_devices * args.sample_batch_size, args.identical_batch, evaluate=args.evaluate, **pairkw, **args.prompt_kwargs)
+                args.prompt_fn, n_devices * args.sample_batch_size, args.identical_batch, evaluate=args.evaluate, pairs=d3po, **args.prompt_kwargs)
             # ----------------------------- sample ----------------------------- #
             sample_rng, sample_seed = prng.split(sample_rng)
             sample_seeds = prng.split(sample_seed, dp.n_key_devices)
@@ -271,7 +266,7 @@ def main(argv=None):
             final_latents, latents, next_latents, log_probs, ts = pipeline(
                 sample_prompt_embeds, sample_uncond_prompt_embeds, {"unet": state.params, "scheduler": sampling_scheduler_params},
                 dp.sample_key(sample_seeds), args.n_inference_steps, jit=True, height=args.resolution, width=args.resolution,
-                guidance_scale=args.guidance_scale, eta=args.eta, **rescalekw)
+                guidance_scale=args.guidance_scale, eta=args.eta, guidance_rescale=rescale)
             # ----------------------------- decode latents ----------------------------- #
             if device_images:
                 images_dev = vae.decode(final_latents)
@@ -334,11 +329,11 @@ def main(argv=None):
             assert num_timesteps == args.n_inference_steps
             # shuffle samples along the batch dimension, then along time independently for each sample; keep this rank's rows
             if args.num_inner_epochs == 1:
-                mine = dp.shuffled_rows(devs, args.train_batch_size, **pairkw)          # same draws, only this rank's rows gathered
+                mine = dp.shuffled_rows(devs, args.train_batch_size, pairs=d3po)         # same draws, only this rank's rows gathered
                 if dp.single_host:
                     devs = None                                               # the gathered global copy is not needed again this epoch
             else:
-                devs = dp.shuffle(devs, **pairkw)
+                devs = dp.shuffle(devs, pairs=d3po)
                 mine = dp.my_rows(devs, args.train_batch_size)
             total_batch_size = mine["log_probs"].shape[0]
             num_train_ts = int(num_timesteps * args.train_timestep_ratio)
@@ -346,39 +341,29 @@ def main(argv=None):
             all_infos = []
             info_keys = (("pref_acc", "pref_margin", "loss") if d3po else ("approx_kl", "clipfrac", "loss")) + (("kl_ref",) if kl_coef > 0 else ())
             do_opt_update = False
-            train_fuse = train_fuse_default(args.train_batch_size * (2 if args.train_cfg else 1),
-                                            mine["latents"].shape[-1] * mine["latents"].shape[-2])
+            train_fuse = max(1, train_fuse_default(args.train_batch_size * (2 if args.train_cfg else 1),
+                                                   mine["latents"].shape[-1] * mine["latents"].shape[-2]))
             t_train = time.time()
             for i in range(n_mini):
                 sl = slice(i * args.train_batch_size, (i + 1) * args.train_batch_size)
-                for j0 in (range(0, num_train_ts, train_fuse) if train_fuse > 1 else ()):
+                for j0 in range(0, num_train_ts, train_fuse):
                     # DDPO_TRAIN_FUSE=k (default 16): k consecutive timesteps of this mini-batch (same parameters: the optimizer only
-                    # steps at the last timestep) as one U-Net forward/backward over k micro-batches (train_steps_fused)
+                    # steps at the last timestep) as one U-Net forward/backward over k micro-batches (train_steps_fused); k = 1: one
+                    # micro-step per launch, which train_steps_fused hands to train_step
                     js = range(j0, min(j0 + train_fuse, num_train_ts))
                     batches = [{"prompt_embeds": mine["embeds"][sl], "uncond_embeds": train_uncond_prompt_embeds,
                                 "advantages": mine["advantages"][sl], "latents": mine["latents"][sl, j],
                                 "next_latents": mine["next_latents"][sl, j], "log_probs": mine["log_probs"][sl, j],
                                 "ts": mine["ts"][sl, j]} for j in js]
+                    # update at the last timestep of a sequence once enough samples are accumulated
                     do_opt_update = (js[-1] == num_train_ts - 1) and ((i + 1) % args.train_accumulation_steps == 0)
                     if do_opt_update:
                         print(f"opt update at {i}, {js[-1]}")
                     state, infos_k = train_steps_fused(state, batches, noise_scheduler_state, pipeline.scheduler, args.train_cfg,
                                                        args.guidance_scale, args.eta, args.ppo_clip_range, do_opt_update,
-                                                       kl_coef=kl_coef, ref_unet=ref_unet, **losskw, **rescalekw)
+                                                       kl_coef=kl_coef, ref_unet=ref_unet, loss=args.pg_loss,
+                                                       d3po_beta=float(args.d3po_beta) if d3po else None, guidance_rescale=rescale)
                     all_infos += [torch.stack([info[k] for k in info_keys]) for info in infos_k]
-                for j in (range(num_train_ts) if train_fuse <= 1 else ()):
-                    batch = {"prompt_embeds": mine["embeds"][sl], "uncond_embeds": train_uncond_prompt_embeds,
-                             "advantages": mine["advantages"][sl], "latents": mine["latents"][sl, j],
-                             "next_latents": mine["next_latents"][sl, j], "log_probs": mine["log_probs"][sl, j],
-                             "ts": mine["ts"][sl, j]}
-                    # update at the last timestep of a sequence once enough samples are accumulated
-                    do_opt_update = (j == num_train_ts - 1) and ((i + 1) % args.train_accumulation_steps == 0)
-                    if do_opt_update:
-                        print(f"opt update at {i}, {j}")
-                    state, info = train_step(state, batch, noise_scheduler_state, pipeline.scheduler, args.train_cfg,
-                                             args.guidance_scale, args.eta, args.ppo_clip_range, do_opt_update,
-                                             kl_coef=kl_coef, ref_unet=ref_unet, **losskw, **rescalekw)
-                    all_infos.append(torch.stack([info[k] for k in info_keys]))
             assert do_opt_update
             infos = torch.stack(all_infos).cpu().numpy()            # ONE host sync per inner epoch
             if n_workers > 1:

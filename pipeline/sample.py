@@ -54,7 +54,7 @@ def main(argv=None):
     bad = check_rescale_args(args.guidance_rescale, None)
     if bad:
         raise SystemExit(bad)
-    rescalekw = dict(guidance_rescale=float(args.guidance_rescale)) if args.guidance_rescale > 0 else {}
+    rescale = float(args.guidance_rescale)
     rng = prng.PRNGKey(args.seed)
     n_devices = 1
     batch_size = n_devices * args.n_samples_per_device
@@ -102,7 +102,7 @@ def main(argv=None):
         prompt_embeds = text_encode(pipeline.prepare_inputs(inference_prompts))
         final_latents, *_ = pipeline(prompt_embeds, uncond_prompt_embeds, params, prng_seeds[0], args.n_inference_steps, jit=True,
                                      height=args.resolution, width=args.resolution, guidance_scale=args.guidance_scale, eta=args.eta,
-                                     **rescalekw)
+                                     guidance_rescale=rescale)
         images = pipeline.vae.decode(final_latents).cpu().numpy().astype(np.float32)
         print(f"[ sample ] {len(images)} samples in {timer():.2f} seconds | eval: {args.evaluate}")
         infos = training.evaluate_callbacks(callback_fns, images, training_prompts, prompt_metadata)
@@ -124,7 +124,8 @@ def main(argv=None):
         if args.max_samples is not None and n_samples >= args.max_samples:
             break
     writer.close(world=n_workers, metadata={"guidance_scale": args.guidance_scale, "filter_field": args.filter_field, "n_samples": int(n_samples),
-                           "synthetic_weights": bool(pipeline.synthetic_weights), **rescalekw})
+                           "synthetic_weights": bool(pipeline.synthetic_weights),
+                           **({"guidance_rescale": rescale} if rescale > 0 else {})})      # metadata of earlier datasets has no such key
     return savepath
 
 

@@ -11,6 +11,8 @@ import pytest
 from ddpo_amd import lib as L
 from oracle import prng as OP, unet as OU
 
+from _abi_check import check_signatures
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -28,21 +30,30 @@ def test_library_exports_every_declared_symbol():
 def test_signatures_match_the_header_prototypes():
     """Every `int|size_t ddpo_*( ... );` prototype of the header against its row of L._SIGS: the parameter count, the return type, a pointer
     exactly where the binding passes one, and the same scalar kind elsewhere — ctypes checks none of this on a positional call."""
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ddpo_hip.h")).read(), flags=re.S)
-    protos = re.findall(r"\b(int|size_t)\s+(ddpo_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert len(protos) == len(L._SIGS) == 83 and {name for _, name, _ in protos} == set(L._SIGS)
-    scalars = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
-               "uint32_t": ctypes.c_uint32, "int": ctypes.c_int}
-    for ret, name, params in protos:
-        restype, argtypes = L._SIGS[name]
-        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
-        assert len(params) == len(argtypes), name
-        assert (restype is ctypes.c_size_t) == (ret == "size_t") and restype in (ctypes.c_size_t, ctypes.c_int), name
-        for i, (p, t) in enumerate(zip(params, argtypes)):
-            if "*" in p:
-                assert t is ctypes.c_void_p or issubclass(t, ctypes._Pointer), f"{name} argument {i}: {p}"
-            else:
-                assert t is scalars[p.split()[0]], f"{name} argument {i}: {p}"
+    check_signatures(os.path.join(ROOT, "include", "ddpo_hip.h"), L._SIGS, 83)
+
+
+@pytest.mark.parametrize("module", ["lib_optim", "lib_ppo_kl", "lib_pref", "lib_dpo", "lib_cfg_rescale"])
+def test_side_binding_refuses_a_library_without_one_of_its_entries(module, monkeypatch):
+    """A row of _SIGS that the built library does not export (a binding newer than the library): load() names the symbol, asks for a
+    rebuild and binds nothing.  lib_optim's own check, the struct size, fails the same way."""
+    import importlib
+    M = importlib.import_module(f"ddpo_amd.{module}")
+    monkeypatch.setattr(M, "_lib", None)
+    monkeypatch.setitem(M._SIGS, "ddpo_entry_of_a_later_build", (ctypes.c_int, [ctypes.c_void_p]))
+    with pytest.raises(L.DdpoHipError, match="does not export ddpo_entry_of_a_later_build: rebuild"):
+        M.load()
+    assert M._lib is None
+    monkeypatch.delitem(M._SIGS, "ddpo_entry_of_a_later_build")
+    if module == "lib_optim":
+        class Wider(ctypes.Structure):
+            _fields_ = M.AdafactorTensor._fields_ + [("one_more", ctypes.c_int64)]
+        monkeypatch.setattr(M, "AdafactorTensor", Wider)
+        with pytest.raises(L.DdpoHipError, match="struct layout mismatch between include/ddpo_optim.h"):
+            M.load()
+        assert M._lib is None
+        monkeypatch.undo()
+    assert M.load() is M._lib and M._lib is not None            # and the untouched table binds
 
 
 def test_struct_mirrors():

@@ -15,6 +15,7 @@ from ddpo_amd import lib_ppo_kl as LK
 from oracle.ddim import DDIMOracle
 
 import _kl_oracle as KO
+from _abi_check import check_signatures
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "ddpo_ppo_kl.h")
@@ -26,20 +27,7 @@ def _header():
 
 def test_signatures_match_the_header_prototypes():
     """tests/test_abi_cpu.py::test_signatures_match_the_header_prototypes, applied to include/ddpo_ppo_kl.h and lib_ppo_kl._SIGS."""
-    protos = re.findall(r"\b(int|size_t)\s+(ddpo_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header())
-    assert len(protos) == len(LK._SIGS) == 2 and {name for _, name, _ in protos} == set(LK._SIGS)
-    scalars = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
-               "uint32_t": ctypes.c_uint32, "int": ctypes.c_int}
-    for ret, name, params in protos:
-        restype, argtypes = LK._SIGS[name]
-        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
-        assert len(params) == len(argtypes), name
-        assert (restype is ctypes.c_size_t) == (ret == "size_t") and restype in (ctypes.c_size_t, ctypes.c_int), name
-        for i, (p, t) in enumerate(zip(params, argtypes)):
-            if "*" in p:
-                assert t is ctypes.c_void_p or issubclass(t, ctypes._Pointer), f"{name} argument {i}: {p}"
-            else:
-                assert t is scalars[p.split()[0]], f"{name} argument {i}: {p}"
+    check_signatures(HDR, LK._SIGS, 2)
 
 
 def test_library_exports_every_declared_symbol_under_its_own_version():

@@ -15,6 +15,7 @@ from ddpo_amd import lib as L
 from oracle.ddim import DDIMOracle
 
 import _pref_oracle as PO
+from _abi_check import check_signatures
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "ddpo_pref.h")
@@ -27,20 +28,7 @@ def _header():
 def test_signatures_match_the_header_prototypes():
     """tests/test_abi_cpu.py::test_signatures_match_the_header_prototypes, applied to include/ddpo_pref.h and lib_pref._SIGS."""
     from ddpo_amd import lib_pref as LP
-    protos = re.findall(r"\b(int|size_t)\s+(ddpo_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header())
-    assert len(protos) == len(LP._SIGS) == 2 and {name for _, name, _ in protos} == set(LP._SIGS)
-    scalars = {"float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
-               "uint32_t": ctypes.c_uint32, "int": ctypes.c_int}
-    for ret, name, params in protos:
-        restype, argtypes = LP._SIGS[name]
-        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
-        assert len(params) == len(argtypes), name
-        assert restype is ctypes.c_int and ret == "int", name
-        for i, (p, t) in enumerate(zip(params, argtypes)):
-            if "*" in p:
-                assert t is ctypes.c_void_p or issubclass(t, ctypes._Pointer), f"{name} argument {i}: {p}"
-            else:
-                assert t is scalars[p.split()[0]], f"{name} argument {i}: {p}"
+    check_signatures(HDR, LP._SIGS, 2, returns=("int",))
 
 
 def test_library_exports_every_declared_symbol_under_its_own_version():
