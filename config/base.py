@@ -30,6 +30,10 @@ _PG_DEFAULTS = (
     # (the reference's only mode); lora_alpha None = lora_rank (scale alpha / rank = 1).  LoRA usually wants a far higher learning_rate than
     # the 1e-5 default of full fine-tuning; the default is not changed here.
     ("lora_rank", 0), ("lora_alpha", None),
+    # engine-specific addition: which layers --lora_rank adapts.  "attn" = the 128 attention projections; "attn_ff" = those and the two GEGLU
+    # feed-forward layers of every transformer block (160 layers, 1.9 times the adapter parameters for SD-1.5; the wide layers' adapter
+    # gradients come from csrc/lora_wide.hip).  proj_in / proj_out and the convolutions are never adapted.  Needs lora_rank > 0.
+    ("lora_targets", "attn"),
     # engine-specific addition: KL penalty to the frozen pretrained policy (DPOK's regulariser; ddpo_amd/training/kl_reference.py,
     # DESIGN.md §4): loss += kl_coef * KL(policy || pretrained) per DDIM step, in the units of the PPO loss.  0 = off (the reference's
     # only mode): no second U-Net is built and the training step is unchanged.  Needs eta > 0.

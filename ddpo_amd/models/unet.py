@@ -439,11 +439,13 @@ class UNet2DCondition:
         return d_x
 
     def _lora_wgrad(self, x, dy, kernel_name):
-        """Adapter gradients of an adapted layer (x: its forward input, fp32 or the norm's bf16 planes; dy: the gradient of its output)."""
+        """Adapter gradients of an adapted layer (x: its forward input, fp32 or the norm's bf16 planes; dy: the gradient of its output), through
+        models/lora.lora_wgrad: the kernel of lib.py inside its width limits, the wide one (lib_lora_wide.py) for the feed-forward layers."""
+        from .lora import lora_wgrad
         A, B_, dA, dB = self.lora.layer(kernel_name)
         if isinstance(x, L.Planes) and x.fmt != 0:
             x = x.float()
-        L.lora_wgrad(x, dy, A, B_, dA, dB, self.lora.scale)
+        lora_wgrad(x, dy, A, B_, dA, dB, self.lora.scale)
 
     def _transformer(self, name, x: Act, ctx, ctx_len, heads, tape=None, emit_planes=0, dest=None, full_B=None):
         """dest / strided x.t: as in resnet_forward (sampling: the block output lands in its consumer's concat buffer).
@@ -535,6 +537,7 @@ class UNet2DCondition:
         tb = name + ".transformer_blocks_0"
         gw = lambda n: G[n + ".kernel"]
         tr = _trains(G)                    # False under LoRA: adapter gradients of the four projections, no base-weight gradient
+        lff = not tr and self.lora.has_ff  # --lora_targets attn_ff: adapter gradients of the two feed-forward layers as well (no bias gradient)
         # out = proj_out(h3) + x
         if cfg.use_linear_projection:
             if tr:
@@ -547,10 +550,14 @@ class UNet2DCondition:
         # h3 = ff2(geglu(ff1(LN3(h2)))) + h2
         if tr:
             L.linear_wgrad(r["gg"], d_h3, gw(tb + ".ff.net_2"), dbias=G[tb + ".ff.net_2.bias"])
+        elif lff:
+            self._lora_wgrad(r["gg"], d_h3, tb + ".ff.net_2.kernel")
         d_gg = L.linear_dgrad(d_h3, P[tb + ".ff.net_2.kernel"])
         d_f = L.geglu_bwd(r["f"], d_gg)
         if tr:
             L.linear_wgrad(r["l3"], d_f, gw(tb + ".ff.net_0.proj"), dbias=G[tb + ".ff.net_0.proj.bias"])
+        elif lff:
+            self._lora_wgrad(r["l3"], d_f, tb + ".ff.net_0.proj.kernel")
         d_l3 = L.linear_dgrad(d_f, P[tb + ".ff.net_0.proj.kernel"])
         d_h2 = L.layernorm_bwd(r["h2"], d_l3, P[tb + ".norm3.scale"], G[tb + ".norm3.scale"], G[tb + ".norm3.bias"], 1e-5, dx_add=d_h3)
         # h2 = to_out(attn2(LN2(h1), ctx)) + h1

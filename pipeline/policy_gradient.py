@@ -100,6 +100,16 @@ def check_rescale_args(args):
     return check(getattr(args, "guidance_rescale", 0.0), args.train_cfg)
 
 
+def check_lora_args(args):
+    """A message to exit with, or None: --lora_targets is attn or attn_ff, and attn_ff needs --lora_rank > 0."""
+    targets = getattr(args, "lora_targets", "attn")
+    if targets not in ("attn", "attn_ff"):
+        return f"--lora_targets must be attn or attn_ff, got {targets!r}"
+    if targets != "attn" and not args.lora_rank:
+        return f"--lora_targets {targets} needs --lora_rank > 0: with lora_rank 0 every U-Net parameter is trained and there are no adapters"
+    return None
+
+
 def check_resume_optimizer(rs, tx, where):
     """A resume bundle carries the moments of the optimizer that wrote it (bundles from before the field existed are AdamW's)."""
     wrote = rs.get("optimizer", "adamw")
@@ -126,7 +136,7 @@ def main(argv=None):
     args = Parser(argv).parse_args("pg", process_index=dp.seed_process_index)
     utils.init_logging("policy_gradient", args.verbose)
 
-    bad = check_kl_args(args) or check_d3po_args(args) or check_rescale_args(args)
+    bad = check_kl_args(args) or check_d3po_args(args) or check_rescale_args(args) or check_lora_args(args)
     if bad:
         raise SystemExit(bad)
     kl_coef = float(args.kl_coef)
@@ -180,11 +190,12 @@ def main(argv=None):
     tx = make_optimizer(args)
     lora = None
     if args.lora_rank:
-        # adapters on the attention projections; the pretrained weights are W0.  Drawn on the host from the BASE seed (args.seed carries the
+        # adapters on the attention projections (and, --lora_targets attn_ff, the feed-forward layers); the pretrained weights are W0.  Drawn on the host from the BASE seed (args.seed carries the
         # per-process offset of parser.set_seed), so every rank starts from the same adapters and applies the same all-reduced updates to them
         from ddpo_amd.models.lora import LoraStore
-        lora = LoraStore(unet, args.lora_rank, alpha=args.lora_alpha, seed=lora_seed(args, dp))
-        print(f"[ policy_gradient ] LoRA rank {lora.rank}, scale {lora.scale:g}: {lora.n_params} trainable parameters on {len(lora.targets)} layers")
+        lora = LoraStore(unet, args.lora_rank, alpha=args.lora_alpha, seed=lora_seed(args, dp), targets=args.lora_targets)
+        print(f"[ policy_gradient ] LoRA rank {lora.rank}, scale {lora.scale:g}, targets {lora.target_set}: {lora.n_params} trainable parameters "
+              f"on {len(lora.targets)} layers")
     state = AccumulatingTrainState(unet, tx, lora=lora)
     sampling_scheduler_params = params["scheduler"]
 
@@ -225,6 +236,9 @@ def main(argv=None):
             if int(rs["lora_rank"]) != lora.rank or rs["lora_alpha"] != lora.alpha:
                 raise SystemExit(f"DDPO_RESUME: the run was trained with lora_rank {rs['lora_rank']}, lora_alpha {rs['lora_alpha']}; "
                                  f"this one asks for lora_rank {lora.rank}, lora_alpha {lora.alpha}")
+            if rs.get("lora_targets", "attn") != lora.target_set:          # bundles from before the field existed are attention-only
+                raise SystemExit(f"DDPO_RESUME: the run was trained with lora_targets {rs.get('lora_targets', 'attn')}; "
+                                 f"this one asks for lora_targets {lora.target_set}")
             lora.params.flat.copy_(rs["lora_params"])
             lora.merge()
             rs["params_path"] = os.path.join(os.environ["DDPO_RESUME"], f"lora_{rs['epoch']}.safetensors")
@@ -396,7 +410,7 @@ def main(argv=None):
                     lora.save(os.path.join(ckdir, f"lora_{epoch}.safetensors"), synthetic_weights=pipeline.synthetic_weights)
                     if pipeline.synthetic_weights:        # as save_checkpoint does: adapters of random-init weights must not pass for a fine-tune
                         mark_synthetic(ckdir)
-                    resume.update(lora_params=lora.params.flat.cpu(), lora_rank=lora.rank, lora_alpha=lora.alpha,
+                    resume.update(lora_params=lora.params.flat.cpu(), lora_rank=lora.rank, lora_alpha=lora.alpha, lora_targets=lora.target_set,
                                   synthetic_weights=bool(pipeline.synthetic_weights))
                     torch.save(resume, os.path.join(ckdir, f"resume_{epoch}.pt"))
                 else:
